@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — cells aggregated / s on drillUp(sum), MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).
+`--full` adds the kernel-only timing and roofline, the box's read and write ceilings, the other configurations,
+precisions and shapes, and the CPU baselines.  `--dump-outputs DIR` writes what the last timed step computed
+as DIR/<name>.npy (float32 cells).
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its N ranks itself (a child
 `python -m torch.distributed.run`, before anything here touches the GPU) and relays rank 0's line;
@@ -300,6 +305,20 @@ def write_ceiling(pkg, engine, torch, buf, n_bytes):
     return n_bytes / (us * 1e-6) / 1e9
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: host array} as dirname/<name>.npy in float32, at most 64 MB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """N > 1 without a launcher: start the ranks as a child process tree BEFORE this process touches the GPU
     (never an exec of a process that has initialised HIP) and relay what they print."""
@@ -327,8 +346,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: only the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-only timing and roofline, ceilings, other configurations and shapes, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N = 1: only the headline workload")
     ap.add_argument("--serial-steps", action="store_true", help="N > 1: no overlap between consecutive steps")
     ap.add_argument("--force-sharded", action="store_true",
                     help="developer aid: run the N > 1 code path (sharded store, RCCL communicator, reduce-scatter) with the ranks given, "
@@ -337,6 +359,8 @@ def main():
                     help="developer aid: the N ranks share cuda:0 and gloo carries the payloads (exercises the N > 1 code path on "
                          "a 1-GPU box with a 10x smaller cube; the numbers are meaningless)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)
@@ -413,6 +437,9 @@ def main():
 
         def finish():
             pass
+
+        def outputs():
+            return {"drillup_sum": partial.cpu().numpy()}
         collective, pipelined, transport = "none", False, "none"
     else:
         lens = list(FRIENDLY_SHAPE)
@@ -470,6 +497,13 @@ def main():
 
         def finish():
             op.wait([stream])
+
+        def outputs():
+            values_, status_, _first = op.result_host(0)
+            out = {"drillup_sum_rank%d" % rank: values_}
+            if status_ is not None:
+                out["drillup_sum_status_rank%d" % rank] = status_
+            return out
     torch.cuda.synchronize()
 
     # ---- the timed region: W warm-up steps, then exactly K steps between barriers, max over ranks
@@ -483,24 +517,29 @@ def main():
     finish()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
-
-    # kernel-only duration on the launch stream (HIP events), separately from the step loop
-    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    k0.record()
-    for _ in range(args.steps):
-        kernel_only()
-    k1.record()
-    torch.cuda.synchronize()
-    kernel_ms = k0.elapsed_time(k1) / args.steps
-
     total_cells = float(np.prod(lens))
-    # bytes = N_in*4 (read) + N_out*4 (write); the Int32 mask is neither read nor written here
-    # because for Float32 cells over a 0 default it is a function of the values
-    alg_bytes = local_cells * 4 + n_out * 4
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
 
-    if sharded_path and transport == "rccl" and pipelined:
+    # what the last timed step computed, before anything below reuses the output buffers
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs())
+
+    if args.full:
+        # kernel-only duration on the launch stream (HIP events), separately from the step loop
+        k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        k0.record()
+        for _ in range(args.steps):
+            kernel_only()
+        k1.record()
+        torch.cuda.synchronize()
+        kernel_ms = k0.elapsed_time(k1) / args.steps
+
+        # bytes = N_in*4 (read) + N_out*4 (write); the Int32 mask is neither read nor written here
+        # because for Float32 cells over a 0 default it is a function of the values
+        alg_bytes = local_cells * 4 + n_out * 4
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+
+    if args.full and sharded_path and transport == "rccl" and pipelined:
         # the same steps strictly one after the other (no overlap between the exchange of one query and the local
         # reduction of the next): what a single query costs end to end
         sop = store.plan_drillup_dim0(np.zeros(lens[0], np.uint32), 1, "sum", placement=capi.PLACE_SCATTER, depth=1)
@@ -516,7 +555,7 @@ def main():
         extra["serial_steps"] = {"steps": k_ser, "ms_per_step": ser_elapsed / k_ser * 1e3, "cells_per_s": total_cells * k_ser / ser_elapsed,
                                  "note": "depth 1: local reduction, reduce-scatter and finish of each step before the next one starts"}
         del sop
-    if sharded_path and transport == "rccl":
+    if args.full and sharded_path and transport == "rccl":
         # the literal [10]^9 shape of configs[3] beside the headline: rows split 2,2,1,1,... at N = 8 and every
         # rank ships a 400 MB partial, so the collective dominates; fewer steps, same protocol
         del op, store
@@ -541,7 +580,7 @@ def main():
         del lop, lit
 
     kernel_ms_per_rank = None
-    if sharded_path:
+    if args.full and sharded_path:
         # every rank's local reduction (HIP events on its own launch stream)
         if world > 1:
             t = torch.tensor([kernel_ms], dtype=torch.float64, device="cpu" if args.rehearse else "cuda")
@@ -569,7 +608,7 @@ def main():
     with_mask = None
     ceiling = None
     w_ceiling = None
-    if not sharded_path:
+    if args.full and not sharded_path:
         ceiling = read_ceiling(pkg, engine, torch, values, n * 4)
         w_ceiling = write_ceiling(pkg, engine, torch, partial, n_out * 4)  # (the output buffer: rewritten by every step anyway)
         if not args.no_extras:
@@ -708,24 +747,26 @@ def main():
             "data": "synthetic (seeded mulberry32, values in [0.5,1.5), generated on device)",
             "config": {"workload": workload, "shape": lens, "cells_per_gpu": local_cells, "cell_type": "float32",
                        "kernel": kernel_name, "collective": collective, "transport": transport, "steps_pipelined": bool(pipelined)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "kernel_ms": kernel_ms, "algorithmic_bytes": alg_bytes,
-                         "hbm_read_frac": local_cells * 4 / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
         }
-        if not sharded_path:
-            traffic = read_traffic()
-            if traffic:
-                line["roofline"]["traffic"] = traffic[0]
-                line["roofline"]["traffic_source"] = ("%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (gfx950 x2 FETCH_SIZE correction), "
-                                                      "recorded when the profile was taken — NOT measured in this run" % traffic[1])
-        else:
+        if sharded_path:
             # what travels: every rank ships its float64 ACCUMULATORS (the reference never rounds between contributions)
             line["config"].update({"partial_type": "float64", "partial_bytes_per_rank": int(n_out) * 8,
                                    "result_cells_per_rank": int(n_out) // world if world else int(n_out)})
-            line["roofline"]["kernel_ms_per_rank"] = kernel_ms_per_rank
-            line["cpu_baseline_ref"] = ("timed on rank 0 at N = 1 only (the contract): see `cpu_baseline` of the N = 1 line of this sweep "
-                                        "(BENCH_rNN.json); a reported baseline, not a target")
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                                "kernel_ms": kernel_ms, "algorithmic_bytes": alg_bytes,
+                                "hbm_read_frac": local_cells * 4 / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            if not sharded_path:
+                traffic = read_traffic()
+                if traffic:
+                    line["roofline"]["traffic"] = traffic[0]
+                    line["roofline"]["traffic_source"] = ("%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (gfx950 x2 FETCH_SIZE "
+                                                          "correction), recorded when the profile was taken — NOT measured in this run" % traffic[1])
+            else:
+                line["roofline"]["kernel_ms_per_rank"] = kernel_ms_per_rank
+                line["cpu_baseline_ref"] = ("timed on rank 0 at N = 1 only (the contract): see `cpu_baseline` of the N = 1 line of this sweep "
+                                            "(BENCH_rNN.json); a reported baseline, not a target")
         if ceiling:
             line["roofline"].update({"read_ceiling": ceiling, "frac_of_read_ceiling": achieved / ceiling,
                                      "read_ceiling_note": "plain 16-byte streaming read of the same 400 MB buffer, same run"})
@@ -740,7 +781,7 @@ def main():
         if with_mask:
             line["with_status_mask"] = with_mask
         line.update(extra)
-        if not sharded_path and not args.no_cpu_baseline:
+        if args.full and not sharded_path and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
             line["cpu_baseline_flat"] = cpu_baseline_flat()
             line["cpu_baseline_js"] = cpu_baseline_js()

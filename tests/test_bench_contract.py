@@ -4,14 +4,50 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from golden_util import mulberry32_at
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def seeded_dim0_sums(shape, cells, seed=20240807):
+    """drillUp(sum) of dimension 0 -> 'all' at the given output cells of bench.py's seeded cube (values fround(0.5 + u),
+    every cell set), float64 accumulation in ascending row order, rounded once to float32."""
+    inner = int(np.prod(shape[1:]))
+    acc = np.zeros(len(cells), np.float64)
+    for row in range(shape[0]):
+        acc += (0.5 + mulberry32_at(seed, 2 * (row * inner + cells.astype(np.uint64)) + 1)).astype(np.float32)
+    return acc.astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps, prints the headline fields only, and --dump-outputs writes what the last
+    timed step computed: the 10^7 output cells of the [10]^8 roll-up, checked on a seeded sample against a host recomputation."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key, kind in [("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str)]:
+        assert isinstance(d[key], kind), (key, d[key])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["unit"] == "cells/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - d["config"]["cells_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for moved in ("roofline", "cpu_baseline", "cpu_baseline_flat", "with_status_mask", "cache_resident_1e6", "config4_single_gpu"):
+        assert moved not in d, moved  # measured with --full only
+    assert sorted(os.listdir(tmp_path)) == ["drillup_sum.npy"]
+    out = np.load(os.path.join(tmp_path, "drillup_sum.npy"))
+    assert out.dtype == np.float32 and out.shape == (10 ** 7,)
+    cells = np.sort(np.random.default_rng(11).choice(10 ** 7, 4096, replace=False))
+    assert np.array_equal(out[cells], seeded_dim0_sums([10] * 8, cells))
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], stdout=subprocess.PIPE,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -37,12 +73,12 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 
 
 @pytest.mark.gpu
-def test_bench_sharded_code_path_on_one_rank():
-    """`--force-sharded` drives every line of bench.py's N > 1 path — sharded store, RCCL communicator made with
+def test_bench_sharded_code_path_on_one_rank(tmp_path):
+    """`--force-sharded --full` drives every line of bench.py's N > 1 path — sharded store, RCCL communicator made with
     olap_comm_init_rank, pipelined reduce-scatter steps, the serial-steps figure, the literal [10]^9 shape — with a
     one-rank communicator, so API misuse shows up on a 1-GPU box and not on the driver's 8-GPU run."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--steps", "4", "--warmup", "1"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-sharded", "--full", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[:2000]  # RCCL's version banner must not reach standard output
@@ -58,6 +94,11 @@ def test_bench_sharded_code_path_on_one_rank():
     assert d["config"]["partial_type"] == "float64" and d["config"]["partial_bytes_per_rank"] == 8 * 10 ** 9 // 320
     assert len(d["roofline"]["kernel_ms_per_rank"]) == 1 and isinstance(d["cpu_baseline_ref"], str)
     assert d["literal_shape"]["partial_bytes_per_rank"] == 8 * 10 ** 8
+    # the one rank's share of the last timed step: the whole 10^9 / 320 result, checked on a seeded sample
+    out = np.load(os.path.join(tmp_path, "drillup_sum_rank0.npy"))
+    assert out.dtype == np.float32 and out.shape == (10 ** 9 // 320,)
+    cells = np.sort(np.random.default_rng(12).choice(out.size, 512, replace=False))
+    assert np.array_equal(out[cells], seeded_dim0_sums(d["config"]["shape"], cells))
 
 
 @pytest.mark.gpu
