@@ -323,6 +323,24 @@ int olap_store_from_sparse(olap_store **store, uint64_t size, int dtype, int def
 int olap_store_totals(const olap_store *store, int ndim, const uint32_t *lens, const int *methods, double *host_values,
                       int32_t *host_status, int *launches, uint64_t *bytes_read);
 
+/* Filtered totals and copies over a cartesian selection given as nlev LEVELS in nesting order, the first outermost
+ * (getCombinations, src/cube.js:19-32: the filter's keys in their own order, then the unfiltered dimensions in cube
+ * order).  axis[l] is a cube dimension (each exactly once) or -1 for a filter key that is not a dimension (it only
+ * multiplies the combinations); sel[l] holds n_sel[l] item indices, repeats allowed, -1 = a cell that does not exist
+ * (read as the default).  An empty level gives no combination.  lens[ndim] describes the store's cells.
+ * getTotalForDimensionItems (src/cube.js:679-707): *total = the float64 sum, from +0 in nesting order, of getValue
+ * (in-memory.js:118-120: the default for an unset cell) over the combinations.  One order-free reduction with an
+ * exactness certificate; when the certificate cannot prove the result equal to the sequential sum, the values are
+ * gathered in nesting order and added on the host.  *exact_path (optional): 1 = the reduction's result, 0 = the
+ * sequential one.  DESIGN.md §3 K8. */
+int olap_store_select_total(const olap_store *store, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                            const uint32_t *n_sel, const int32_t *const *sel, double *total, int *exact_path);
+/* copyMeasureData (src/cube.js:859-888): target.setValue(pos, source.getValue(pos)) for every combination in nesting
+ * order, with setValue's conversion and delete-on-default (in-memory.js:122-133); cell types and defaults of the two
+ * stores may differ, both live on one device.  Entries must be >= 0.  A tracked target gets the reference's key order. */
+int olap_store_copy_select(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev,
+                           const int *axis, const uint32_t *n_sel, const int32_t *const *sel);
+
 /* olap_eval_formula over stores (all of the same size) into a host float64 array */
 int olap_store_eval_formula(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
                             const olap_store *const *inputs, const double *scalars, int n_scalars,
@@ -527,6 +545,14 @@ int olap_sharded_store_dice(const olap_sharded_store *store, olap_sharded_store 
 int olap_sharded_store_drilldown(const olap_sharded_store *store, olap_sharded_store **out, const uint32_t *new_len,
                                  const uint32_t *const *maps, int method, const double *distributions, uint64_t n_dist);
 int olap_sharded_store_reorder(const olap_sharded_store *store, olap_sharded_store **out, const int32_t *perm);
+/* olap_store_select_total / olap_store_copy_select over sharded stores (one-process communicators).  The total adds
+ * the shards' certified partials on the host; when the certificate fails the sequential order needs the whole measure:
+ * OLAP_ERR_INVALID_ARGUMENT, message "sharded: ..." (gather first).  The copy runs per shard and needs source and target
+ * partitioned alike and a target that does not track its order (otherwise "sharded: ..."). */
+int olap_sharded_store_select_total(const olap_sharded_store *store, int nlev, const int *axis, const uint32_t *n_sel,
+                                    const int32_t *const *sel, double *total, int *exact_path);
+int olap_sharded_store_copy_select(olap_sharded_store *target, const olap_sharded_store *source, int nlev, const int *axis,
+                                   const uint32_t *n_sel, const int32_t *const *sel);
 
 #ifdef __cplusplus
 }

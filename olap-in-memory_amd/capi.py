@@ -107,6 +107,8 @@ SIGNATURES = {
     "olap_store_dice_drillup": (_i32, [_vp, _pvp, _i32, _pu32, _pu32, _pu32, _ppi32, _ppu32, _i32]),
     "olap_store_reorder": (_i32, [_vp, _pvp, _i32, _pu32, _pi32]),
     "olap_store_load": (_i32, [_vp, _vp, _i32, _pu32, _pu32, _ppi32]),
+    "olap_store_select_total": (_i32, [_vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
+    "olap_store_copy_select": (_i32, [_vp, _vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),
     "olap_memcpy_to_host": (_i32, [_vp, _vp, _u64]),
     "olap_memcpy_to_device": (_i32, [_vp, _vp, _u64]),
     "olap_diag_read_ceiling": (_i32, [_vp, _u64, _vp, _vp]),
@@ -162,6 +164,8 @@ SIGNATURES = {
     "olap_sharded_store_dice": (_i32, [_vp, _pvp, _pu32, _ppi32]),
     "olap_sharded_store_drilldown": (_i32, [_vp, _pvp, _pu32, _ppu32, _i32, _pdbl, _u64]),
     "olap_sharded_store_reorder": (_i32, [_vp, _pvp, _pi32]),
+    "olap_sharded_store_select_total": (_i32, [_vp, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
+    "olap_sharded_store_copy_select": (_i32, [_vp, _vp, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),
 }
 
 

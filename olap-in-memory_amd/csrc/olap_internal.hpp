@@ -112,8 +112,23 @@ OLAP_INTERNAL int order_after_drilldown(const olap_store *s, olap_store *out);
 OLAP_INTERNAL int order_before_load(olap_store *mine);
 OLAP_INTERNAL int order_after_load(olap_store *mine, const olap_store *his, int ndim, const uint32_t *my_len, const uint32_t *his_len,
                                    const int32_t *const *his_to_mine);
+// a copy_select (olap_select.hip) is about to write n distinct cells of a tracked store: the order is made explicit and
+// *seq / *seq_base say where the newly set cells go (nullptr: the store keeps no order)
+OLAP_INTERNAL int order_before_select_write(olap_store *s, uint64_t n, uint32_t **seq, uint32_t *seq_base);
+OLAP_INTERNAL void order_after_select_write(olap_store *s);
 // host copy of the set cells' indices in insertion order (ascending when the store has no seq)
 OLAP_INTERNAL int order_sorted_keys(const olap_store *s, std::vector<uint64_t> &keys);
 // the untracked operations of olap_capi.hip (what the public entry points do for a store that is not tracked)
 OLAP_INTERNAL int store_drillup_plain(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len, const uint32_t *new_len,
                                       const uint32_t *const *maps, int method);
+
+// ---- filtered totals and copies (olap_select.hip) --------------------------------------------------
+OLAP_INTERNAL int select_validate(const olap_store *store, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                                  const int32_t *const *sel, bool for_copy);
+// order-free sum of one copy of the selected terms with its exactness certificate (lists per cube dimension)
+OLAP_INTERNAL int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint32_t *n_by_dim, const int32_t *const *sel_by_dim,
+                              double *sum, double *abs_sum, int *min_exp, unsigned *flags);
+// 1 and *total when the certificate proves the order-free sum (times m) equal to the sequential one
+OLAP_INTERNAL int select_certified_total(double sum, double abs_sum, int min_exp, unsigned flags, double m, double *total);
+OLAP_INTERNAL int select_copy(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                              const uint32_t *n_sel, const int32_t *const *sel);

@@ -412,6 +412,25 @@ int order_after_set_value(olap_store *s, uint64_t index) {
   return launched("seq_set_cell_kernel");
 }
 
+// copy_select writes n distinct cells in nesting order: newly set ones are appended by their rank (seq_base + rank)
+int order_before_select_write(olap_store *s, uint64_t n, uint32_t **seq, uint32_t *seq_base) {
+  *seq = nullptr;
+  *seq_base = 0;
+  if (!s->track_order) return OLAP_OK;
+  int rc = seq_materialise(s);
+  if (rc) return rc;
+  if ((rc = seq_renumber_if_needed(s, n + 1))) return rc;
+  *seq = s->seq;
+  *seq_base = (uint32_t)s->next_seq;
+  s->next_seq += n + 1;
+  return OLAP_OK;
+}
+
+void order_after_select_write(olap_store *s) {
+  s->maybe_nonempty = true;
+  s->hi_index = s->size ? s->size - 1 : 0;
+}
+
 // deserialize: the blob lists the cells in Map order (in-memory.js:94-100, :103-116)
 int order_after_from_sparse(olap_store *s, const uint32_t *idx, uint64_t n) {
   s->maybe_nonempty = n > 0;

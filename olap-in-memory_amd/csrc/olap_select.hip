@@ -1,0 +1,593 @@
+// olap_select.hip — Cube.getTotalForDimensionItems / getDistribution / copyMeasureData on the device.
+//
+// The reference (the reference's src/cube.js:679-707, :665-673, :859-888, :19-32) enumerates the cartesian
+// product of a filter (getCombinations) and calls getValue / setValue (src/store/in-memory.js:118-133) once per
+// combination.  A selection is given here as LEVELS in nesting order (the first level outermost): level l is a
+// cube dimension axis[l] with an index list sel[l] (repeats allowed; -1 = a cell that does not exist, read as the
+// default: what a pending dice composes into), or a free filter key (axis -1) that only multiplies the count.
+//
+//   select_total   float64 sum, in nesting order, of getValue over the combinations: one reduction that streams
+//                  the contiguous trailing runs with 16-byte loads and gathers the rest, with an exactness
+//                  certificate; when the certificate fails, the values are gathered in nesting order and added
+//                  on the host left to right (the reference's order, always).
+//   copy_select    target.setValue(pos, source.getValue(pos)) for every combination, as one scatter.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstddef>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "olap_device.hpp"
+#include "olap_internal.hpp"
+
+using namespace olap;
+
+namespace {
+
+#define SEL_DISPATCH(dtype, T, CALL)                      \
+  switch (dtype) {                                        \
+    case OLAP_INT32: { using T = int32_t; CALL; break; }  \
+    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
+    case OLAP_FLOAT32: { using T = float; CALL; break; }  \
+    default: { using T = double; CALL; break; }           \
+  }
+
+constexpr int kSelMaxLevels = 64;    // cube dimensions (OLAP_MAX_DIMS) + free filter keys
+constexpr int kSelInline = 512;      // index entries that travel in the kernel arguments (no upload)
+constexpr unsigned kSelBlocks = 2048;
+constexpr uint32_t kFlagNaN = 1, kFlagPosInf = 2, kFlagNegInf = 4;
+
+// Exactness certificate of a set of float64 terms (see select_total_kernel).
+struct Cert {
+  double sum;       // the finite terms, added in whatever order the reduction ran
+  double abs_sum;   // A: sum of |x| over the finite terms
+  int32_t min_exp;  // E: every non-zero finite term is an integer multiple of 2^E (INT_MAX: no such term)
+  uint32_t flags;   // kFlagNaN | kFlagPosInf | kFlagNegInf
+};
+
+__device__ __forceinline__ int32_t low_bit_exponent(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const int be = (int)((b >> 52) & 0x7ff);
+  const unsigned long long man = b & ((1ull << 52) - 1);
+  if (be == 0) return -1074 + __builtin_ctzll(man);  // subnormal (x != 0: man != 0)
+  return be - 1075 + __builtin_ctzll(man | (1ull << 52));
+}
+
+__device__ __forceinline__ void cert_add(Cert &c, double x) {
+  if (x != x) {
+    c.flags |= kFlagNaN;
+  } else if (__builtin_isinf(x)) {
+    c.flags |= x > 0 ? kFlagPosInf : kFlagNegInf;
+  } else if (x != 0.0) {
+    c.sum += x;
+    c.abs_sum += fabs(x);
+    c.min_exp = min(c.min_exp, low_bit_exponent(x));
+  }
+}
+
+__device__ __forceinline__ void cert_merge(Cert &a, const Cert &b) {
+  a.sum += b.sum;
+  a.abs_sum += b.abs_sum;
+  a.min_exp = min(a.min_exp, b.min_exp);
+  a.flags |= b.flags;
+}
+
+// getValue (in-memory.js:118-120) as a JS number: the cell, or the default when it is unset
+template <typename T>
+__device__ __forceinline__ double read_cell(const T *values, const int32_t *status, uint64_t i, bool def_nan) {
+  const T v = values[i];
+  return cell_is_set<T>(v, status ? status[i] : OLAP_STATUS_SET, status != nullptr, def_nan) ? Cell<T>::to_f64(v)
+                                                                                               : (def_nan ? __builtin_nan("") : 0.0);
+}
+
+// The gathered part of a selection: `ngl` levels (cube order, outermost first) in front of a contiguous run of `run`
+// cells that the trailing identity levels fold into.  Row g of the rows x run view starts at the cell
+// sum_l idx[off[l] + digit_l(g)] * stride[l], or does not exist when one of those entries is -1.
+struct GatherPlan {
+  uint64_t rows, run;
+  uint64_t chunk, chunks;  // ROW mode: a work unit is `chunk` cells of one row
+  int ngl;
+  int flat;                // FLAT mode (short runs): one lane per cell of the rows x run view
+  uint32_t len[OLAP_MAX_DIMS];
+  uint32_t off[OLAP_MAX_DIMS];
+  uint64_t stride[OLAP_MAX_DIMS];
+  const int32_t *idx;      // device copy of the lists, or nullptr: they are in `inl`
+  int32_t inl[kSelInline];
+};
+
+__device__ __forceinline__ int64_t row_base(const GatherPlan &p, uint64_t g) {
+  int64_t base = 0;
+  bool ok = true;
+  for (int l = p.ngl - 1; l >= 0; --l) {
+    const uint64_t d = g % p.len[l];
+    g /= p.len[l];
+    const int32_t e = p.idx ? p.idx[p.off[l] + d] : p.inl[p.off[l] + d];
+    if (e < 0) ok = false;
+    else base += (int64_t)e * (int64_t)p.stride[l];
+  }
+  return ok ? base : -1;
+}
+
+// Every workgroup reduces its share of the selection into one Cert slot.
+//
+// Why the result can be exact whatever the order of the additions.  Let the selection hold the finite terms x_i
+// (each taken m times: the free filter keys repeat the whole product), A = sum |x_i| and E the exponent of the lowest
+// set mantissa bit over the non-zero x_i, so that every x_i is an integer multiple of 2^E.  When no NaN is present, A*m
+// is finite and A*m <= 2^(52+E), every partial sum of the m-fold term list, in ANY order, is a multiple of 2^E of
+// magnitude at most A*m < 2^(53+E) (the one bit of margin covers the rounding of the computed A itself: if the true A
+// exceeded 2^(53+E) the computed one, a monotone rounding of increasing partial sums, would too), hence exactly
+// representable: every addition is exact, the device's sum S of one copy of the terms equals the sequential one, and
+// m*S is exact as well.  Non-finite terms: a NaN gives NaN in any order; +inf with -inf gives NaN in any order (once
+// both have been added nothing finite can bring the sum back); a single-signed inf gives that inf, because under the
+// condition the finite partial sums never overflow.  Otherwise (the condition fails) the host re-adds the values in
+// nesting order (select_gather_kernel).
+template <typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void select_total_kernel(const T *__restrict__ values, const int32_t *__restrict__ status, int def_nan_i,
+                                                              GatherPlan p, Cert *__restrict__ partial) {
+  constexpr int V = 16 / sizeof(T);
+  const bool def_nan = def_nan_i != 0;
+  Cert c{0.0, 0.0, INT_MAX, 0u};
+  if (p.flat) {
+    const uint64_t cells = p.rows * p.run;
+    for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < cells; t += (uint64_t)gridDim.x * kBlock) {
+      const uint64_t g = t / p.run, r = t - g * p.run;
+      const int64_t base = row_base(p, g);
+      cert_add(c, base < 0 ? (def_nan ? __builtin_nan("") : 0.0) : read_cell<T>(values, status, (uint64_t)base + r, def_nan));
+    }
+  } else {
+    const uint64_t units = p.rows * p.chunks;
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {
+      const uint64_t g = u / p.chunks, k = u - g * p.chunks;
+      const int64_t base = row_base(p, g);
+      const uint64_t lo = k * p.chunk, hi = lo + p.chunk < p.run ? lo + p.chunk : p.run;
+      if (base < 0) {  // a row that does not exist: every cell reads the default
+        if (def_nan && threadIdx.x == 0) c.flags |= kFlagNaN;
+        continue;
+      }
+      const uint64_t first = (uint64_t)base + lo, n = hi - lo;
+      uint64_t done = 0;
+      if (VEC && (first % V) == 0) {
+        const uint64_t groups = n / V;
+        for (uint64_t q = threadIdx.x; q < groups; q += kBlock) {
+          const Vec<T, V> x = load_stream<T, V>(values + first + q * V);
+          Vec<int32_t, V> sx;
+          if (status) sx = load_stream<int32_t, V>(status + first + q * V);
+#pragma unroll
+          for (int e = 0; e < V; ++e) {
+            const bool set = cell_is_set<T>(x.v[e], status ? sx.v[e] : OLAP_STATUS_SET, status != nullptr, def_nan);
+            cert_add(c, set ? Cell<T>::to_f64(x.v[e]) : (def_nan ? __builtin_nan("") : 0.0));
+          }
+        }
+        done = groups * V;
+      }
+      for (uint64_t i = done + threadIdx.x; i < n; i += kBlock) cert_add(c, read_cell<T>(values, status, first + i, def_nan));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    Cert o;
+    o.sum = __shfl_down(c.sum, off, 64);
+    o.abs_sum = __shfl_down(c.abs_sum, off, 64);
+    o.min_exp = __shfl_down(c.min_exp, off, 64);
+    o.flags = (uint32_t)__shfl_down((int)c.flags, off, 64);
+    cert_merge(c, o);
+  }
+  __shared__ Cert s_c[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Cert a = s_c[0];
+    for (int w = 1; w < kBlock / 64; ++w) cert_merge(a, s_c[w]);
+    partial[blockIdx.x] = a;
+  }
+}
+
+// folds the workgroup slots in a fixed order (one workgroup) and hands the result to the host
+__global__ __launch_bounds__(kBlock) void select_finish_kernel(const Cert *__restrict__ partial, uint32_t n, Cert *out) {
+  Cert c{0.0, 0.0, INT_MAX, 0u};
+  for (uint32_t i = threadIdx.x; i < n; i += kBlock) cert_merge(c, partial[i]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    Cert o;
+    o.sum = __shfl_down(c.sum, off, 64);
+    o.abs_sum = __shfl_down(c.abs_sum, off, 64);
+    o.min_exp = __shfl_down(c.min_exp, off, 64);
+    o.flags = (uint32_t)__shfl_down((int)c.flags, off, 64);
+    cert_merge(c, o);
+  }
+  __shared__ Cert s_c[kBlock / 64];
+  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    Cert a = s_c[0];
+    for (int w = 1; w < kBlock / 64; ++w) cert_merge(a, s_c[w]);
+    *out = a;
+  }
+}
+
+// Levels in nesting order (free levels included, stride 0 and no list), for the sequential fallback and the copy.
+struct NestPlan {
+  int nlev;
+  uint32_t len[kSelMaxLevels];
+  uint32_t off[kSelMaxLevels];
+  uint64_t stride[kSelMaxLevels];
+  uint32_t is_free[kSelMaxLevels];
+  const int32_t *idx;
+  int32_t inl[kSelInline / 2];
+};
+
+__device__ __forceinline__ int64_t nest_cell(const NestPlan &p, uint64_t rank) {
+  int64_t cell = 0;
+  bool ok = true;
+  for (int l = p.nlev - 1; l >= 0; --l) {
+    const uint64_t d = rank % p.len[l];
+    rank /= p.len[l];
+    if (p.is_free[l]) continue;
+    const int32_t e = p.idx ? p.idx[p.off[l] + d] : p.inl[p.off[l] + d];
+    if (e < 0) ok = false;
+    else cell += (int64_t)e * (int64_t)p.stride[l];
+  }
+  return ok ? cell : -1;
+}
+
+// the value of every combination of ranks [first, first + n) in nesting order, as a JS number
+template <typename T>
+__global__ __launch_bounds__(kBlock) void select_gather_kernel(const T *__restrict__ values, const int32_t *__restrict__ status, int def_nan_i,
+                                                               NestPlan p, uint64_t first, uint64_t n, double *__restrict__ out) {
+  const bool def_nan = def_nan_i != 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
+    const int64_t cell = nest_cell(p, first + t);
+    out[t] = cell < 0 ? (def_nan ? __builtin_nan("") : 0.0) : read_cell<T>(values, status, (uint64_t)cell, def_nan);
+  }
+}
+
+// target.setValue(pos, source.getValue(pos)) (src/cube.js:859-888) for every combination; the levels are free of
+// repeats, so every lane owns a distinct cell.  Same conversion and delete-on-default as set_cell_kernel.  A tracked
+// target (seq != nullptr) appends a newly set cell at seq_base + its rank in nesting order, drops a cell that becomes
+// unset, and leaves a cell that stays set where it was (Map.set, in-memory.js:132).
+template <typename S, typename T>
+__global__ __launch_bounds__(kBlock) void copy_select_kernel(const S *__restrict__ src, const int32_t *__restrict__ src_status, int src_nan_i,
+                                                             T *dst, int32_t *dst_status, uint32_t *dst_seq, uint32_t seq_base, int dst_nan_i,
+                                                             NestPlan p, uint64_t n) {
+  const bool src_nan = src_nan_i != 0, dst_nan = dst_nan_i != 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t cell = (uint64_t)nest_cell(p, t);
+    const double x = read_cell<S>(src, src_status, cell, src_nan);
+    T ov;
+    int32_t os;
+    emit_cell<T>(x, !is_default_f64(x, dst_nan), dst_nan, ov, os);
+    dst[cell] = ov;
+    if (dst_status) dst_status[cell] = os;
+    if (dst_seq) {
+      const uint32_t old = dst_seq[cell];
+      dst_seq[cell] = os ? (old ? old : seq_base + (uint32_t)t) : 0u;
+    }
+  }
+}
+
+unsigned grid_for(uint64_t n) {
+  const uint64_t want = (n + kBlock - 1) / kBlock;
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, kSelBlocks));
+}
+
+// index lists either inline (small) or uploaded; `dev` is freed by the caller
+template <typename P>
+int place_lists(P &p, int cap, const std::vector<int32_t> &all, int32_t **dev) {
+  *dev = nullptr;
+  p.idx = nullptr;
+  if ((int)all.size() <= cap) {
+    if (!all.empty()) memcpy(p.inl, all.data(), all.size() * sizeof(int32_t));
+    return OLAP_OK;
+  }
+  HIP_TRY(dev_alloc((void **)dev, all.size() * sizeof(int32_t)));
+  hipError_t e = hipMemcpy(*dev, all.data(), all.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    dev_free(*dev);
+    *dev = nullptr;
+    return hip_fail(e, "select lists");
+  }
+  p.idx = *dev;
+  return OLAP_OK;
+}
+
+uint64_t product_of(const std::vector<uint32_t> &v) {
+  uint64_t n = 1;
+  for (uint32_t x : v) n *= x;
+  return n;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------------- host side
+
+int select_validate(const olap_store *store, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                    const int32_t *const *sel, bool for_copy) {
+  if (!store) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (ndim < 1 || ndim > OLAP_MAX_DIMS || !lens) return fail(OLAP_ERR_INVALID_ARGUMENT, "a selection needs 1..%d dimensions", OLAP_MAX_DIMS);
+  uint64_t size = 1;
+  for (int d = 0; d < ndim; ++d) size *= lens[d];
+  if (size != store->size) return fail(OLAP_ERR_LENGTH_MISMATCH, "dimension lengths give %llu cells, the store has %llu", (unsigned long long)size,
+                                       (unsigned long long)store->size);
+  if (nlev < ndim || nlev > kSelMaxLevels) return fail(OLAP_ERR_INVALID_ARGUMENT, "a selection has %d..%d levels, got %d", ndim, kSelMaxLevels, nlev);
+  if (!axis || !n_sel || !sel) return fail(OLAP_ERR_INVALID_ARGUMENT, "axis/n_sel/sel is NULL");
+  int seen[OLAP_MAX_DIMS] = {0};
+  for (int l = 0; l < nlev; ++l) {
+    const int d = axis[l];
+    if (d < -1 || d >= ndim) return fail(OLAP_ERR_INVALID_ARGUMENT, "level %d names dimension %d of %d", l, d, ndim);
+    if (d < 0) continue;
+    if (seen[d]++) return fail(OLAP_ERR_INVALID_ARGUMENT, "dimension %d has two levels", d);
+    if (n_sel[l] && !sel[l]) return fail(OLAP_ERR_INVALID_ARGUMENT, "sel[%d] is NULL", l);
+    for (uint32_t j = 0; j < n_sel[l]; ++j) {
+      const int32_t e = sel[l][j];
+      if (e >= (int64_t)lens[d] || e < -1 || (for_copy && e < 0))
+        return fail(OLAP_ERR_INDEX_RANGE, "selection entry %d of level %d is outside dimension %d", e, l, d);
+    }
+  }
+  for (int d = 0; d < ndim; ++d)
+    if (!seen[d]) return fail(OLAP_ERR_INVALID_ARGUMENT, "dimension %d has no level", d);
+  return OLAP_OK;
+}
+
+// The order-free part of select_total over ONE store: lists per cube dimension (cube order, repeats and -1 allowed).
+// Free levels are not seen here.  *cert receives the certificate of one copy of the terms.
+int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint32_t *n_by_dim, const int32_t *const *sel_by_dim, double *sum,
+                double *abs_sum, int *min_exp, unsigned *flags) {
+  OnStoreDevice on_device__(s);
+  *sum = 0.0;
+  *abs_sum = 0.0;
+  *min_exp = INT_MAX;
+  *flags = 0;
+  for (int d = 0; d < ndim; ++d)
+    if (!n_by_dim[d]) return OLAP_OK;
+  int rc = require_device();
+  if (rc) return rc;
+  // trailing dimensions selected whole and in order fold into one contiguous run
+  int t = ndim;
+  uint64_t run = 1;
+  while (t > 0) {
+    const int d = t - 1;
+    bool ident = n_by_dim[d] == lens[d];
+    for (uint32_t j = 0; ident && j < n_by_dim[d]; ++j) ident = sel_by_dim[d][j] == (int32_t)j;
+    if (!ident) break;
+    run *= lens[d];
+    --t;
+  }
+  static thread_local GatherPlan p;  // (3 KB: off the host stack)
+  memset(&p, 0, offsetof(GatherPlan, inl));
+  p.ngl = t;
+  p.run = run;
+  p.rows = 1;
+  std::vector<int32_t> all;
+  uint64_t stride = run;
+  for (int d = t - 1; d >= 0; --d) {
+    p.len[d] = n_by_dim[d];
+    p.stride[d] = stride;
+    stride *= lens[d];
+    p.rows *= n_by_dim[d];
+  }
+  for (int d = 0; d < t; ++d) {
+    p.off[d] = (uint32_t)all.size();
+    all.insert(all.end(), sel_by_dim[d], sel_by_dim[d] + n_by_dim[d]);
+  }
+  const uint64_t cells = p.rows * run;
+  unsigned blocks;
+  if (run < 1024) {
+    p.flat = 1;
+    blocks = grid_for(cells);
+  } else {
+    p.flat = 0;
+    // about kSelBlocks units, each a contiguous piece of one row of at least 1024 cells (a multiple of 16 cells)
+    const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>((kSelBlocks + p.rows - 1) / p.rows, run / 1024));
+    p.chunk = ((run + want - 1) / want + 15) / 16 * 16;
+    p.chunks = (run + p.chunk - 1) / p.chunk;
+    blocks = (unsigned)std::min<uint64_t>(p.rows * p.chunks, kSelBlocks);
+  }
+  int32_t *dev_lists = nullptr;
+  if ((rc = place_lists(p, kSelInline, all, &dev_lists))) return rc;
+  static thread_local Cert *pinned = nullptr;
+  static thread_local bool pinned_tried = false;
+  if (!pinned_tried) {
+    pinned_tried = true;
+    void *q = nullptr;
+    if (hipHostMalloc(&q, sizeof(Cert), hipHostMallocPortable | hipHostMallocMapped) == hipSuccess) pinned = (Cert *)q;
+    else (void)hipGetLastError();
+  }
+  Cert *partial = nullptr;
+  hipError_t e = dev_alloc((void **)&partial, (blocks + 1) * sizeof(Cert));
+  if (e == hipSuccess) {
+    const bool vec = (((uintptr_t)s->values | (uintptr_t)mask_needed(s)) & 15u) == 0;
+    const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
+    SEL_DISPATCH(s->dtype, T, {
+      if (vec) hipLaunchKernelGGL((select_total_kernel<T, true>), blocks, kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), def_nan, p, partial);
+      else hipLaunchKernelGGL((select_total_kernel<T, false>), blocks, kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), def_nan, p, partial);
+    });
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(select_finish_kernel, 1, kBlock, 0, nullptr, partial, blocks, pinned ? pinned : partial + blocks);
+      e = hipGetLastError();
+    }
+    Cert c{};
+    if (e == hipSuccess) {
+      if (pinned) {
+        e = hipStreamSynchronize(nullptr);
+        c = *pinned;
+      } else {
+        e = hipMemcpy(&c, partial + blocks, sizeof(Cert), hipMemcpyDeviceToHost);
+      }
+    }
+    dev_free(partial);
+    *sum = c.sum;
+    *abs_sum = c.abs_sum;
+    *min_exp = c.min_exp;
+    *flags = c.flags;
+  }
+  if (dev_lists) dev_free(dev_lists);
+  if (e != hipSuccess) return hip_fail(e, "select_total");
+  return OLAP_OK;
+}
+
+// Applies the certificate.  Returns 1 and sets *total when the order-free result is the sequential one; 0 otherwise.
+int select_certified_total(double sum, double abs_sum, int min_exp, unsigned flags, double m, double *total) {
+  if ((flags & kFlagNaN) || ((flags & kFlagPosInf) && (flags & kFlagNegInf))) {
+    *total = NAN;
+    return 1;
+  }
+  if (min_exp == INT_MAX) {  // no non-zero finite term
+    *total = (flags & kFlagPosInf) ? INFINITY : (flags & kFlagNegInf) ? -INFINITY : 0.0;
+    return 1;
+  }
+  const double am = abs_sum * m;
+  if (!std::isfinite(am)) return 0;
+  if (min_exp + 52 <= 1023 && am > std::ldexp(1.0, min_exp + 52)) return 0;  // (above: every finite A*m is below the bound)
+  *total = (flags & kFlagPosInf) ? INFINITY : (flags & kFlagNegInf) ? -INFINITY : sum * m + 0.0;  // (+0.0: never -0)
+  return 1;
+}
+
+// lists of the selection in cube order (the dimension levels); m = product of the free levels' lengths
+static void by_dimension(int ndim, int nlev, const int *axis, const uint32_t *n_sel, const int32_t *const *sel, std::vector<uint32_t> &n_by_dim,
+                         std::vector<const int32_t *> &sel_by_dim, double *m, bool *empty) {
+  n_by_dim.assign(ndim, 0);
+  sel_by_dim.assign(ndim, nullptr);
+  *m = 1.0;
+  *empty = false;
+  for (int l = 0; l < nlev; ++l) {
+    if (!n_sel[l]) *empty = true;
+    if (axis[l] < 0) {
+      *m *= (double)n_sel[l];
+    } else {
+      n_by_dim[axis[l]] = n_sel[l];
+      sel_by_dim[axis[l]] = sel[l];
+    }
+  }
+}
+
+// The reference's order, always: every combination's value in nesting order, added left to right from +0.
+static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim, int nlev, const int *axis, const uint32_t *n_sel,
+                             const int32_t *const *sel, double *total) {
+  OnStoreDevice on_device__(s);
+  static thread_local NestPlan p;
+  memset(&p, 0, offsetof(NestPlan, inl));
+  std::vector<uint64_t> stride(ndim);
+  uint64_t st = 1;
+  for (int d = ndim - 1; d >= 0; --d) {
+    stride[d] = st;
+    st *= lens[d];
+  }
+  std::vector<int32_t> all;
+  uint64_t n = 1;
+  p.nlev = nlev;
+  for (int l = 0; l < nlev; ++l) {
+    p.len[l] = n_sel[l];
+    n *= n_sel[l];
+    p.is_free[l] = axis[l] < 0;
+    p.stride[l] = axis[l] < 0 ? 0 : stride[axis[l]];
+    p.off[l] = (uint32_t)all.size();
+    if (axis[l] >= 0) all.insert(all.end(), sel[l], sel[l] + n_sel[l]);
+  }
+  int32_t *dev_lists = nullptr;
+  int rc = place_lists(p, kSelInline / 2, all, &dev_lists);
+  if (rc) return rc;
+  const uint64_t chunk = std::min<uint64_t>(n, 1ull << 23);  // 64 MB of float64 per round trip
+  double *dev = nullptr;
+  std::vector<double> host(chunk ? chunk : 1);
+  hipError_t e = dev_alloc((void **)&dev, (chunk ? chunk : 1) * sizeof(double));
+  double acc = 0.0;
+  for (uint64_t first = 0; e == hipSuccess && first < n; first += chunk) {
+    const uint64_t k = std::min(chunk, n - first);
+    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((select_gather_kernel<T>), grid_for(k), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
+                                                 s->default_kind == OLAP_DEFAULT_NAN, p, first, k, dev));
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(host.data(), dev, k * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+      for (uint64_t i = 0; i < k; ++i) acc += host[i];  // src/cube.js:705: `total += this.getSingleData(...)`
+  }
+  if (dev) dev_free(dev);
+  if (dev_lists) dev_free(dev_lists);
+  if (e != hipSuccess) return hip_fail(e, "select_total (sequential)");
+  *total = acc;
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_select_total(const olap_store *s, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                                       const int32_t *const *sel, double *total, int *exact_path) {
+  int rc = select_validate(s, ndim, lens, nlev, axis, n_sel, sel, false);
+  if (rc) return rc;
+  if (!total) return fail(OLAP_ERR_INVALID_ARGUMENT, "total is NULL");
+  std::vector<uint32_t> nd;
+  std::vector<const int32_t *> sd;
+  double m;
+  bool empty;
+  by_dimension(ndim, nlev, axis, n_sel, sel, nd, sd, &m, &empty);
+  if (exact_path) *exact_path = 1;
+  if (empty) {  // no combination: the reduce starts and ends at 0 (src/cube.js:704)
+    *total = 0.0;
+    return OLAP_OK;
+  }
+  double sum, abs_sum;
+  int min_exp;
+  unsigned flags;
+  if ((rc = select_cert(s, ndim, lens, nd.data(), sd.data(), &sum, &abs_sum, &min_exp, &flags))) return rc;
+  if (select_certified_total(sum, abs_sum, min_exp, flags, m, total)) return OLAP_OK;
+  if (exact_path) *exact_path = 0;
+  return select_sequential(s, lens, ndim, nlev, axis, n_sel, sel, total);
+}
+
+// copy over ONE pair of stores on one device; levels already validated (entries >= 0)
+int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                const int32_t *const *sel) {
+  OnStoreDevice on_device__(t);
+  if (t->device != src->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "copy_select: source and target live on different devices");
+  // every level without repeats (first occurrence kept), free levels dropped: each combination is a distinct cell
+  // and its rank among the distinct combinations is its place among the keys the copy creates
+  std::vector<uint64_t> stride(ndim);
+  uint64_t st = 1;
+  for (int d = ndim - 1; d >= 0; --d) {
+    stride[d] = st;
+    st *= lens[d];
+  }
+  static thread_local NestPlan p;
+  memset(&p, 0, offsetof(NestPlan, inl));
+  std::vector<int32_t> all;
+  uint64_t n = 1;
+  for (int l = 0; l < nlev; ++l) {
+    if (!n_sel[l]) return OLAP_OK;  // no combination: nothing is written
+    if (axis[l] < 0) continue;
+    const uint32_t at = (uint32_t)all.size();
+    std::vector<char> seen(lens[axis[l]], 0);
+    for (uint32_t j = 0; j < n_sel[l]; ++j)
+      if (!seen[sel[l][j]]++) all.push_back(sel[l][j]);
+    const int k = p.nlev++;
+    p.len[k] = (uint32_t)all.size() - at;
+    p.off[k] = at;
+    p.stride[k] = stride[axis[l]];
+    n *= p.len[k];
+  }
+  int rc = require_device();
+  if (rc) return rc;
+  uint32_t *seq = nullptr;
+  uint32_t seq_base = 0;
+  if ((rc = order_before_select_write(t, n, &seq, &seq_base))) return rc;
+  int32_t *dev_lists = nullptr;
+  if ((rc = place_lists(p, kSelInline / 2, all, &dev_lists))) return rc;
+  const int sn = src->default_kind == OLAP_DEFAULT_NAN, tn = t->default_kind == OLAP_DEFAULT_NAN;
+  SEL_DISPATCH(src->dtype, S, SEL_DISPATCH(t->dtype, T, hipLaunchKernelGGL((copy_select_kernel<S, T>), grid_for(n), kBlock, 0, nullptr,
+                                                                          (const S *)src->values, mask_needed(src), sn, (T *)t->values, t->status,
+                                                                          seq, seq_base, tn, p, n)));
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  if (dev_lists) dev_free(dev_lists);
+  if (e != hipSuccess) return hip_fail(e, "copy_select");
+  order_after_select_write(t);
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_copy_select(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                                      const uint32_t *n_sel, const int32_t *const *sel) {
+  int rc = select_validate(target, ndim, lens, nlev, axis, n_sel, sel, true);
+  if (rc) return rc;
+  if ((rc = select_validate(source, ndim, lens, nlev, axis, n_sel, sel, true))) return rc;
+  return select_copy(target, source, ndim, lens, nlev, axis, n_sel, sel);
+}

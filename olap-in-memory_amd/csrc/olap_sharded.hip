@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
@@ -2014,4 +2015,108 @@ extern "C" int olap_sharded_store_reorder(const olap_sharded_store *s, olap_shar
   }
   *out = o;
   return OLAP_OK;
+}
+
+// ---- filtered totals and copies (olap_select.hip) over the shards ----------------------------------
+// The level of dimension 0 is split by owner: rank r sees the entries in [bounds[r], bounds[r+1]) rebased to its slab
+// (repeats kept); the -1 entries (cells that do not exist) are counted once, by the first rank.
+static void shard_rows(const olap_sharded_store *s, int i, const int32_t *sel0, uint32_t n0, bool keep_missing, std::vector<int32_t> &rows) {
+  const int r = s->comm->local[i].rank;
+  const int64_t lo = s->bounds[r], hi = s->bounds[r + 1];
+  rows.clear();
+  for (uint32_t j = 0; j < n0; ++j) {
+    const int32_t e = sel0[j];
+    if (e < 0) {
+      if (keep_missing && r == 0) rows.push_back(-1);
+    } else if (e >= lo && e < hi) {
+      rows.push_back((int32_t)(e - lo));
+    }
+  }
+}
+
+extern "C" int olap_sharded_store_select_total(const olap_sharded_store *s, int nlev, const int *axis, const uint32_t *n_sel,
+                                               const int32_t *const *sel, double *total, int *exact_path) {
+  if (!s) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (!total) return fail(OLAP_ERR_INVALID_ARGUMENT, "total is NULL");
+  const int ndim = (int)s->lens.size();
+  if (s->shard.empty()) return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: this process drives no rank");
+  // (validated against the whole measure: a shard-sized store with the global lengths)
+  olap_store whole_frame = *s->shard[0];
+  whole_frame.size = s->size;
+  int rc = select_validate(&whole_frame, ndim, s->lens.data(), nlev, axis, n_sel, sel, false);
+  if (rc) return rc;
+  if ((int)s->comm->local.size() != s->comm->world)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: a filtered total over one process per GPU needs the whole measure");
+  std::vector<uint32_t> nd(ndim, 0);
+  std::vector<const int32_t *> sd(ndim, nullptr);
+  double m = 1.0;
+  bool empty = false;
+  for (int l = 0; l < nlev; ++l) {
+    if (!n_sel[l]) empty = true;
+    if (axis[l] < 0) m *= (double)n_sel[l];
+    else {
+      nd[axis[l]] = n_sel[l];
+      sd[axis[l]] = sel[l];
+    }
+  }
+  if (exact_path) *exact_path = 1;
+  if (empty) {
+    *total = 0.0;
+    return OLAP_OK;
+  }
+  double sum = 0.0, abs_sum = 0.0;
+  int min_exp = INT_MAX;
+  unsigned flags = 0;
+  rc = for_each_shard(s, [&](int i, olap_store *sh) -> int {
+    std::vector<int32_t> rows;
+    shard_rows(s, i, sd[0], nd[0], true, rows);
+    if (rows.empty()) return OLAP_OK;
+    std::vector<uint32_t> ll = local_lens(s, i, s->lens.data()), ln(nd);
+    std::vector<const int32_t *> ls(sd);
+    ln[0] = (uint32_t)rows.size();
+    ls[0] = rows.data();
+    double ps, pa;
+    int pe;
+    unsigned pf;
+    int e = select_cert(sh, ndim, ll.data(), ln.data(), ls.data(), &ps, &pa, &pe, &pf);
+    sum += ps;
+    abs_sum += pa;
+    min_exp = std::min(min_exp, pe);
+    flags |= pf;
+    return e;
+  }, /*in_order=*/true);
+  if (rc) return rc;
+  if (select_certified_total(sum, abs_sum, min_exp, flags, m, total)) return OLAP_OK;
+  if (exact_path) *exact_path = 0;
+  return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: this total needs the sequential order over the whole measure");
+}
+
+extern "C" int olap_sharded_store_copy_select(olap_sharded_store *t, const olap_sharded_store *s, int nlev, const int *axis, const uint32_t *n_sel,
+                                              const int32_t *const *sel) {
+  if (!t || !s) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  const int ndim = (int)t->lens.size();
+  if (t->shard.empty()) return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: this process drives no rank");
+  olap_store whole_frame = *t->shard[0];
+  whole_frame.size = t->size;
+  int rc = select_validate(&whole_frame, ndim, t->lens.data(), nlev, axis, n_sel, sel, true);
+  if (rc) return rc;
+  if (s->comm != t->comm || s->lens != t->lens || s->bounds != t->bounds)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: source and target are not partitioned alike");
+  for (olap_store *sh : t->shard)
+    if (sh->track_order) return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: the target keeps its insertion order");
+  int l0 = -1;
+  for (int l = 0; l < nlev; ++l) {
+    if (!n_sel[l]) return OLAP_OK;
+    if (axis[l] == 0) l0 = l;
+  }
+  return for_each_shard(t, [&](int i, olap_store *sh) -> int {
+    std::vector<int32_t> rows;
+    shard_rows(t, i, sel[l0], n_sel[l0], false, rows);
+    if (rows.empty()) return OLAP_OK;
+    std::vector<uint32_t> ll = local_lens(t, i, t->lens.data()), ln(n_sel, n_sel + nlev);
+    std::vector<const int32_t *> ls(sel, sel + nlev);
+    ln[l0] = (uint32_t)rows.size();
+    ls[l0] = rows.data();
+    return select_copy(sh, s->shard[i], ndim, ll.data(), nlev, axis, ln.data(), ls.data());
+  });
 }

@@ -32,6 +32,15 @@ def _tables(rows, np_dtype, c_type):
     return keep, arr
 
 
+def _levels(lens, levels):
+    """(lens, axis array, n_sel array, keepalive, sel pointer table) of a selection given as [(axis, entries), ...]"""
+    lv = _u32(lens)
+    ax = (C.c_int * max(len(levels), 1))(*[int(a) for a, _ in levels])
+    n = _u32([len(e) for _, e in levels])
+    keep, arr = _tables([e for _, e in levels], np.int32, C.c_int32)
+    return lv, ax, n, keep, arr
+
+
 def _default_kind(default):
     if isinstance(default, str):
         return capi.DEFAULT_NAN if default == "NaN" else capi.DEFAULT_ZERO
@@ -425,6 +434,24 @@ class HipStore:
         check(self._lib.olap_store_reorder(self._h, C.byref(h), len(ol), ol.ctypes.data_as(capi._pu32),
                                            p.ctypes.data_as(capi._pi32)))
         return HipStore(0, _handle=h)
+
+    # ---- filtered totals and copies (olap_store_select_total / olap_store_copy_select)
+    def select_total(self, lens, levels):
+        """getTotalForDimensionItems (src/cube.js:679-707) over a selection given as levels in nesting order:
+        [(axis, entries), ...], axis = cube dimension or -1 (a free filter key), entries = item indices (-1 = a cell that
+        does not exist).  Returns (total, path): path "device" (the certified order-free reduction) or "sequential"."""
+        lv, ax, n, keep, arr = _levels(lens, levels)
+        total, path = C.c_double(), C.c_int()
+        check(self._lib.olap_store_select_total(self._h, len(lv), lv.ctypes.data_as(capi._pu32), len(levels), ax, n.ctypes.data_as(capi._pu32), arr,
+                                                C.byref(total), C.byref(path)))
+        return total.value, ("device" if path.value else "sequential")
+
+    def copy_select(self, source, lens, levels):
+        """copyMeasureData (src/cube.js:859-888): self.set_value(pos, source.get_value(pos)) over the selection."""
+        lv, ax, n, keep, arr = _levels(lens, levels)
+        check(self._lib.olap_store_copy_select(self._h, source._h, len(lv), lv.ctypes.data_as(capi._pu32), len(levels), ax,
+                                               n.ctypes.data_as(capi._pu32), arr))
+        return self
 
     def load(self, other, my_len, his_len, his_to_mine):
         ml, hl = _u32(my_len), _u32(his_len)

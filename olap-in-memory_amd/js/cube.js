@@ -23,6 +23,7 @@ const { toNestedArray, fromNestedArray, toNestedObject, fromNestedObject } = req
 const { toBuffer, fromBuffer, toArrayBuffer } = require('./wire');
 const { getParser } = require('./formula');
 const backend = require('./backend');
+const { selectionLevels, copyLevels } = require('./selection');
 
 const MEASURE_ID = /^[a-z][_a-z0-9]+$|^[_a-z0-9]+__total$/i;
 
@@ -407,7 +408,21 @@ class Cube {
     return cartesian(options);
   }
 
+  /**
+   * src/cube.js:679-707.  A stored measure and a filter whose every combination is valid (./selection.js): one device
+   * reduction over the selection, bit for bit the per-cell sum in nesting order.  Anything else takes the per-cell
+   * path, for its exact messages.
+   */
   getTotalForDimensionItems(measureId, dimensionsFilter = {}) {
+    const store = this.storedMeasures[measureId];
+    if (store !== undefined) {
+      const levels = selectionLevels(this.dimensions, dimensionsFilter);
+      if (levels.valid) return store.selectTotal(Uint32Array.from(this.dimensions, (d) => d.numItems), levels);
+    }
+    return this._getTotalForDimensionItemsPerCell(measureId, dimensionsFilter);
+  }
+
+  _getTotalForDimensionItemsPerCell(measureId, dimensionsFilter = {}) {
     return this._combinations(dimensionsFilter).reduce((sum, coords) => sum + this.getSingleData(measureId, coords), 0);
   }
 
@@ -417,7 +432,26 @@ class Cube {
     return whole === 0 ? part : part / whole;
   }
 
+  /**
+   * src/cube.js:859-888.  Two stored measures and a filter whose every combination is valid: one device scatter, the
+   * same cells, values and key order as the per-cell loop.  Anything else takes the per-cell loop (its messages, and
+   * the writes it makes before it throws).
+   */
   copyMeasureData(sourceMeasureId, targetMeasureId, dimensionsFilter = {}) {
+    const source = this.storedMeasures[sourceMeasureId];
+    const target = this.storedMeasures[targetMeasureId];
+    if (source !== undefined && target !== undefined) {
+      const levels = selectionLevels(this.dimensions, dimensionsFilter);
+      if (levels.valid) {
+        const copy = copyLevels(levels);
+        if (copy.count === 0) return;
+        if (target.copySelect(source, Uint32Array.from(this.dimensions, (d) => d.numItems), copy)) return;
+      }
+    }
+    this._copyMeasureDataPerCell(sourceMeasureId, targetMeasureId, dimensionsFilter);
+  }
+
+  _copyMeasureDataPerCell(sourceMeasureId, targetMeasureId, dimensionsFilter = {}) {
     for (const coords of this._combinations(dimensionsFilter)) this.setSingleData(targetMeasureId, coords, this.getSingleData(sourceMeasureId, coords));
   }
 

@@ -390,6 +390,60 @@ class HipStore {
     return new HipStore(size, this._type, this._defaultValue, { source, oldLen: lengthsOf(oldDimensions), midLen, sel: composed });
   }
 
+  /**
+   * getTotalForDimensionItems (src/cube.js:679-707) over a selection in nesting order (./selection.js: `axis` per level,
+   * a cube dimension or -1, and Int32Array `lists` of item indices, -1 = a cell that does not exist): the float64 sum of
+   * getValue from +0 in that order, bit for bit.  A pending dice composes the levels through its selection instead of
+   * being materialised.  HipStore.lastSelectPath says what ran: 'device' (the certified order-free reduction) or
+   * 'sequential' (the values gathered in nesting order and added on the host).
+   */
+  selectTotal(lengths, levels) {
+    const pathOut = new Int32Array(1);
+    let native = null;
+    let lens = lengths;
+    let axis = levels.axis;
+    let lists = levels.lists;
+    const at = this._pending ? visibleDims(this._pending, lengths) : null;
+    if (at) {
+      const p = this._pending;
+      const dropped = [];
+      for (let d = 0; d < p.midLen.length; ++d) if (!at.includes(d)) dropped.push(d); // single-item dimensions
+      axis = Int32Array.from([...Array.from(levels.axis, (v) => (v < 0 ? -1 : at[v])), ...dropped]);
+      lists = [...levels.lists.map((list, l) => (levels.axis[l] < 0 ? list : Int32Array.from(list, (j) => (j < 0 ? -1 : p.sel[at[levels.axis[l]]][j])))),
+        ...dropped.map((d) => p.sel[d])];
+      native = p.source;
+      lens = p.oldLen;
+    } else {
+      native = this._native;
+    }
+    const total = onShards(native, 'selectTotal', [lens, axis, lists, pathOut]);
+    HipStore.lastSelectPath = pathOut[0] ? 'device' : 'sequential';
+    return total;
+  }
+
+  /**
+   * copyMeasureData (src/cube.js:859-888): this.setValue(pos, source.getValue(pos)) over a selection of distinct cells
+   * (./selection.js copyLevels), in nesting order, in one launch.  The target never leaves its devices: a sharded
+   * source is gathered for a target on one device, a source on one device is spread like a sharded target.  Returns
+   * false when the stores cannot meet that way (partitioned differently): the caller copies cell by cell.
+   */
+  copySelect(source, lengths, levels) {
+    const target = this._writable;
+    const from = source._native;
+    if (!target.isSharded) {
+      target.copySelect(from.isSharded ? from.gather() : from, lengths, levels.axis, levels.lists);
+      return true;
+    }
+    const spread = from.isSharded ? from : backend.load().shardStore(from, lengths);
+    try {
+      target.copySelect(spread, lengths, levels.axis, levels.lists);
+    } catch (e) {
+      if (!/^sharded:/.test(e.message)) throw e;
+      return false;
+    }
+    return true;
+  }
+
   /** in-memory.js:178-211 */
   reorder(oldDimensions, newDimensions) {
     const perm = Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
@@ -438,6 +492,8 @@ class HipStore {
     return new HipStore(data.size, type, defaultValue, native);
   }
 }
+
+HipStore.lastSelectPath = null;
 
 module.exports = HipStore;
 module.exports.toPlainArray = toPlainArray;

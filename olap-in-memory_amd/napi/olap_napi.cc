@@ -627,6 +627,61 @@ static napi_value StoreLoad(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// ---- filtered totals and copies (olap_store_select_total / olap_store_copy_select) ----------------------
+// A selection: lens (Uint32Array, the cells' dimensions), axis (Int32Array: cube dimension or -1 per level, nesting
+// order) and lists (Int32Array[] of item indices, -1 = a cell that does not exist).
+struct SelectArgs {
+  std::vector<uint32_t> lens, n_sel;
+  std::vector<int32_t> axis;
+  std::vector<std::vector<uint32_t>> lists;
+  std::vector<const int32_t *> ptrs;
+  bool decode(napi_env env, napi_value l, napi_value a, napi_value t) {
+    std::vector<uint32_t> ax;
+    if (!get_u32_vec(env, l, lens) || !get_u32_vec(env, a, ax) || !get_tables(env, t, lists) || lists.size() != ax.size()) return false;
+    axis.assign(ax.begin(), ax.end());
+    for (auto &v : lists) {
+      n_sel.push_back((uint32_t)v.size());
+      ptrs.push_back(v.empty() ? (const int32_t *)&OpArgs::dummy : (const int32_t *)v.data());
+    }
+    return true;
+  }
+};
+
+static void set_path(napi_env env, napi_value out, int path) {
+  bool is_ta = false;
+  if (napi_is_typedarray(env, out, &is_ta) != napi_ok || !is_ta) return;
+  napi_typedarray_type type;
+  size_t len;
+  void *data;
+  if (napi_get_typedarray_info(env, out, &type, &len, &data, nullptr, nullptr) == napi_ok && type == napi_int32_array && len >= 1)
+    ((int32_t *)data)[0] = path;
+}
+
+// selectTotal(lens, axis, lists, pathOut?: Int32Array) -> number; pathOut[0] = 1 (certified reduction) | 0 (sequential)
+static napi_value StoreSelectTotal(napi_env env, napi_callback_info info) {
+  STORE_METHOD_PROLOGUE(4)
+  SelectArgs a;
+  if (argc < 3 || !a.decode(env, argv[0], argv[1], argv[2])) return bad_args(env, "selectTotal(lens: Uint32Array, axis: Int32Array, lists: Int32Array[])");
+  double total = 0;
+  int path = 1;
+  int rc = olap_store_select_total(s, (int)a.lens.size(), a.lens.data(), (int)a.axis.size(), a.axis.data(), a.n_sel.data(), a.ptrs.data(), &total, &path);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 3) set_path(env, argv[3], path);
+  return num(env, total);
+}
+
+// copySelect(source: Store, lens, axis, lists): this.setValue(pos, source.getValue(pos)) over the selection
+static napi_value StoreCopySelect(napi_env env, napi_callback_info info) {
+  STORE_METHOD_PROLOGUE(4)
+  olap_store *src = argc > 0 ? unwrap(env, argv[0]) : nullptr;
+  if (!src) return nullptr;
+  SelectArgs a;
+  if (argc < 4 || !a.decode(env, argv[1], argv[2], argv[3])) return bad_args(env, "copySelect(source: Store, lens: Uint32Array, axis: Int32Array, lists: Int32Array[])");
+  int rc = olap_store_copy_select(s, src, (int)a.lens.size(), a.lens.data(), (int)a.axis.size(), a.axis.data(), a.n_sel.data(), a.ptrs.data());
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
+}
+
 // evalFormula(code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array) -> Float64Array
 static napi_value EvalFormula(napi_env env, napi_callback_info info) {
   size_t argc = 4;
@@ -1026,6 +1081,32 @@ static napi_value ShardedReorder(napi_env env, napi_callback_info info) {
   return wrap_new_sharded(env, os, box->comm);
 }
 
+// selectTotal(lens, axis, lists, pathOut?) over the shards ("sharded: ..." when only the whole measure can answer)
+static napi_value ShardedSelectTotal(napi_env env, napi_callback_info info) {
+  SHARDED_PROLOGUE(4)
+  if (argc < 1 || !sharded_view(env, s, argv[0])) return nullptr;
+  SelectArgs a;
+  if (argc < 3 || !a.decode(env, argv[0], argv[1], argv[2])) return bad_args(env, "selectTotal(lens, axis, lists)");
+  double total = 0;
+  int path = 1;
+  int rc = olap_sharded_store_select_total(s, (int)a.axis.size(), a.axis.data(), a.n_sel.data(), a.ptrs.data(), &total, &path);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 3) set_path(env, argv[3], path);
+  return num(env, total);
+}
+// copySelect(source: ShardedStore, lens, axis, lists): per shard (both partitioned alike)
+static napi_value ShardedCopySelect(napi_env env, napi_callback_info info) {
+  SHARDED_PROLOGUE(4)
+  ShardedBox *src = argc > 0 ? unwrap_sharded(env, argv[0]) : nullptr;
+  if (!src) return nullptr;
+  if (argc < 2 || !sharded_view(env, s, argv[1]) || !sharded_view(env, src->store, argv[1])) return nullptr;
+  SelectArgs a;
+  if (argc < 4 || !a.decode(env, argv[1], argv[2], argv[3])) return bad_args(env, "copySelect(source: ShardedStore, lens, axis, lists)");
+  int rc = olap_sharded_store_copy_select(s, src->store, (int)a.axis.size(), a.axis.data(), a.n_sel.data(), a.ptrs.data());
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
+}
+
 // shardStore(store: Store, lens: Uint32Array) -> ShardedStore (olap_sharded_store_scatter)
 static napi_value ShardStore(napi_env env, napi_callback_info info) {
   size_t argc = 2;
@@ -1184,6 +1265,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"diceDrillUp", nullptr, StoreDiceDrillUp, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reorder", nullptr, StoreReorder, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"load", nullptr, StoreLoad, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"selectTotal", nullptr, StoreSelectTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"copySelect", nullptr, StoreCopySelect, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_value ctor;
   if (napi_define_class(env, "Store", NAPI_AUTO_LENGTH, StoreNew, nullptr, sizeof(props) / sizeof(props[0]), props, &ctor) != napi_ok) return nullptr;
@@ -1209,6 +1292,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"drillDown", nullptr, ShardedDrillDown, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"dice", nullptr, ShardedDice, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reorder", nullptr, ShardedReorder, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"selectTotal", nullptr, ShardedSelectTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"copySelect", nullptr, ShardedCopySelect, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_value sctor;
   if (napi_define_class(env, "ShardedStore", NAPI_AUTO_LENGTH, ShardedNew, nullptr, sizeof(sprops) / sizeof(sprops[0]), sprops, &sctor) != napi_ok) return nullptr;

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import capi
 from .capi import check
-from .hipstore import HipStore, Plan, _default_kind, _method_code, _tables, _u32
+from .hipstore import HipStore, Plan, _default_kind, _levels, _method_code, _tables, _u32
 
 NP_OF_DTYPE = {0: np.int32, 1: np.uint32, 2: np.float32, 3: np.float64}
 NAME_OF_DTYPE = {0: "int32", 1: "uint32", 2: "float32", 3: "float64"}
@@ -387,6 +387,20 @@ class ShardedStore:
         hs, hw = C.c_void_p(), C.c_void_p()
         check(self._lib.olap_sharded_store_drillup(self._h, C.byref(hs), C.byref(hw), nl.ctypes.data_as(capi._pu32), arr, _method_code(method)))
         return self._wrap(hs) if hs.value else HipStore(0, _handle=hw)
+
+    def select_total(self, levels):
+        """HipStore.select_total over the shards: certified per-shard partials added on the host.  Raises an
+        OlapError whose message starts with "sharded:" when only the whole measure can answer (gather first)."""
+        _lv, ax, n, keep, arr = _levels(self.lens, levels)
+        total, path = C.c_double(), C.c_int()
+        check(self._lib.olap_sharded_store_select_total(self._h, len(levels), ax, n.ctypes.data_as(capi._pu32), arr, C.byref(total), C.byref(path)))
+        return total.value, ("device" if path.value else "sequential")
+
+    def copy_select(self, source, levels):
+        """HipStore.copy_select per shard; source partitioned like this store."""
+        _lv, ax, n, keep, arr = _levels(self.lens, levels)
+        check(self._lib.olap_sharded_store_copy_select(self._h, source._h, len(levels), ax, n.ctypes.data_as(capi._pu32), arr))
+        return self
 
     def dice(self, new_len, sel):
         nl = _u32(new_len)
