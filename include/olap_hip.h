@@ -297,6 +297,13 @@ int olap_store_count_set(const olap_store *store, uint64_t *n_set);
 int olap_store_get_keys(const olap_store *store, uint64_t *host_keys, uint64_t cap, uint64_t *n_keys);
 int olap_store_get_value(const olap_store *store, uint64_t index, double *value, int *is_set); /* :118-120 */
 int olap_store_set_value(olap_store *store, uint64_t index, double value, int is_null);       /* :122-133 */
+/* n sequential setValue calls (in-memory.js:122-133) in one call: entry i writes values[i] to cell indexes[i], or unsets
+ * it when is_null (may be NULL) has is_null[i] != 0.  The store ends bit for bit as n olap_store_set_value calls in list
+ * order leave it (values, mask, conversions, delete-on-default, a tracked store's key order).  Duplicates allowed: the
+ * last write decides.  Every index is checked on the host first: one >= size gives OLAP_ERR_INDEX_RANGE and nothing is
+ * written.  n == 0 does nothing.  DESIGN.md §3 K9. */
+int olap_store_set_values(olap_store *store, uint64_t n, const uint64_t *indexes, const double *values,
+                          const uint8_t *is_null);
 int olap_store_fill(olap_store *store, double value);                                         /* :135-137 */
 int olap_store_total(const olap_store *store, double *total);                                 /* :22-28 */
 
@@ -513,6 +520,10 @@ int olap_sharded_store_get_data_f64(const olap_sharded_store *store, double *hos
 int olap_sharded_store_get_status(const olap_sharded_store *store, int32_t *host_status);
 int olap_sharded_store_get_value(const olap_sharded_store *store, uint64_t index, double *value, int *is_set);
 int olap_sharded_store_set_value(olap_sharded_store *store, uint64_t index, double value, int is_null);
+/* olap_store_set_values: the entries are split by shard on the host (list order kept within a shard) and written
+ * per shard; an index of a rank this process does not drive gives OLAP_ERR_INDEX_RANGE before anything is written */
+int olap_sharded_store_set_values(olap_sharded_store *store, uint64_t n, const uint64_t *indexes,
+                                  const double *values, const uint8_t *is_null);
 int olap_sharded_store_fill(olap_sharded_store *store, double value);
 /* sum of the set cells of the WHOLE measure: with one process per GPU over RCCL every rank must call it (a
  * collective); on a detached communicator it is the sum of this process' slabs only */

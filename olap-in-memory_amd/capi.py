@@ -94,6 +94,7 @@ SIGNATURES = {
     "olap_store_get_keys": (_i32, [_vp, _pu64, _u64, _pu64]),
     "olap_store_get_value": (_i32, [_vp, _u64, _pdbl, C.POINTER(C.c_int)]),
     "olap_store_set_value": (_i32, [_vp, _u64, _dbl, _i32]),
+    "olap_store_set_values": (_i32, [_vp, _u64, _pu64, _pdbl, C.POINTER(C.c_uint8)]),
     "olap_store_fill": (_i32, [_vp, _dbl]),
     "olap_store_total": (_i32, [_vp, _pdbl]),
     "olap_store_to_sparse": (_i32, [_vp, _pu32, _vp, _u64, _pu64]),
@@ -154,6 +155,7 @@ SIGNATURES = {
     "olap_sharded_store_get_status": (_i32, [_vp, _pi32]),
     "olap_sharded_store_get_value": (_i32, [_vp, _u64, _pdbl, C.POINTER(C.c_int)]),
     "olap_sharded_store_set_value": (_i32, [_vp, _u64, _dbl, _i32]),
+    "olap_sharded_store_set_values": (_i32, [_vp, _u64, _pu64, _pdbl, C.POINTER(C.c_uint8)]),
     "olap_sharded_store_fill": (_i32, [_vp, _dbl]),
     "olap_sharded_store_total": (_i32, [_vp, _pdbl]),
     "olap_sharded_store_eval_formula": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _pdbl, _i32, _pdbl]),

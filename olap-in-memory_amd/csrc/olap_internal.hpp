@@ -132,3 +132,8 @@ OLAP_INTERNAL int select_cert(const olap_store *s, int ndim, const uint32_t *len
 OLAP_INTERNAL int select_certified_total(double sum, double abs_sum, int min_exp, unsigned flags, double m, double *total);
 OLAP_INTERNAL int select_copy(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
                               const uint32_t *n_sel, const int32_t *const *sel);
+
+// ---- batched setValue (olap_select.hip) ------------------------------------------------------------------------------
+// the host checks of olap_store_set_values (NULL arguments, every index < size), before any device work
+OLAP_INTERNAL int set_values_validate(const olap_store *store, uint64_t n, const uint64_t *indexes, const double *values);
+OLAP_INTERNAL int set_values(olap_store *store, uint64_t n, const uint64_t *indexes, const double *values, const uint8_t *is_null);

@@ -11,7 +11,11 @@
 //                  certificate; when the certificate fails, the values are gathered in nesting order and added
 //                  on the host left to right (the reference's order, always).
 //   copy_select    target.setValue(pos, source.getValue(pos)) for every combination, as one scatter.
+//   set_values     a list of setValue calls (Cube.hydrateFromSparseNestedObject), duplicates allowed: the entries
+//                  are sorted by cell, each cell's run is reduced to its last write and its place in the key order,
+//                  and the distinct cells are written by the same per-cell code as copy_select.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <climits>
@@ -244,10 +248,27 @@ __global__ __launch_bounds__(kBlock) void select_gather_kernel(const T *__restri
   }
 }
 
+// The last setValue (in-memory.js:122-133) a batch makes to one distinct cell: x, or an unset when !has.  Same
+// conversion and delete-on-default as set_cell_kernel.  A tracked store (seq != nullptr) drops a cell that ends unset,
+// leaves one that was set and keeps_place where it was, and appends any other set cell at `appended` (Map.set,
+// in-memory.js:132).
+template <typename T>
+__device__ __forceinline__ void write_cell(T *dst, int32_t *dst_status, uint32_t *dst_seq, bool dst_nan, uint64_t cell, double x, bool has,
+                                           bool keeps_place, uint32_t appended) {
+  T ov;
+  int32_t os;
+  emit_cell<T>(x, has, dst_nan, ov, os);
+  dst[cell] = ov;
+  if (dst_status) dst_status[cell] = os;
+  if (dst_seq) {
+    const uint32_t old = dst_seq[cell];
+    dst_seq[cell] = os ? (old && keeps_place ? old : appended) : 0u;
+  }
+}
+
 // target.setValue(pos, source.getValue(pos)) (src/cube.js:859-888) for every combination; the levels are free of
-// repeats, so every lane owns a distinct cell.  Same conversion and delete-on-default as set_cell_kernel.  A tracked
-// target (seq != nullptr) appends a newly set cell at seq_base + its rank in nesting order, drops a cell that becomes
-// unset, and leaves a cell that stays set where it was (Map.set, in-memory.js:132).
+// repeats, so every lane owns a distinct cell.  A tracked target appends a newly set cell at seq_base + its rank in
+// nesting order.
 template <typename S, typename T>
 __global__ __launch_bounds__(kBlock) void copy_select_kernel(const S *__restrict__ src, const int32_t *__restrict__ src_status, int src_nan_i,
                                                              T *dst, int32_t *dst_status, uint32_t *dst_seq, uint32_t seq_base, int dst_nan_i,
@@ -256,15 +277,56 @@ __global__ __launch_bounds__(kBlock) void copy_select_kernel(const S *__restrict
   for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
     const uint64_t cell = (uint64_t)nest_cell(p, t);
     const double x = read_cell<S>(src, src_status, cell, src_nan);
-    T ov;
-    int32_t os;
-    emit_cell<T>(x, !is_default_f64(x, dst_nan), dst_nan, ov, os);
-    dst[cell] = ov;
-    if (dst_status) dst_status[cell] = os;
-    if (dst_seq) {
-      const uint32_t old = dst_seq[cell];
-      dst_seq[cell] = os ? (old ? old : seq_base + (uint32_t)t) : 0u;
+    write_cell<T>(dst, dst_status, dst_seq, dst_nan, cell, x, !is_default_f64(x, dst_nan), true, seq_base + (uint32_t)t);
+  }
+}
+
+// ---- set_values: n setValue calls as one scatter.  The entries are sorted by cell (stably: list order within a cell)
+// into slots; a slot's entry "unsets" when setValue would leave its cell unset (null, the default, or a value whose
+// conversion is the default).  run[j] = the first slot of j's cell after the last unsetting slot before j (or the
+// cell's first slot): a max-scan of these markers.  The last slot of a cell decides its value; a cell that ends set
+// and has no unsetting slot keeps its place, any other one is appended at the list position of slot run[last].
+
+template <typename T>
+__device__ __forceinline__ bool entry_unsets(double x, bool null, bool def_nan) {
+  T ov;
+  int32_t os;
+  emit_cell<T>(x, !null && !is_default_f64(x, def_nan), def_nan, ov, os);
+  return os == 0;
+}
+
+__global__ __launch_bounds__(kBlock) void iota_u32_kernel(uint32_t *out, uint64_t n) {
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) out[j] = (uint32_t)j;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void set_values_mark_kernel(const uint64_t *__restrict__ cell, const uint32_t *__restrict__ pos,
+                                                                 const double *__restrict__ values, const uint8_t *__restrict__ is_null, int def_nan_i,
+                                                                 uint64_t n, uint32_t *__restrict__ marker) {
+  const bool def_nan = def_nan_i != 0;
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
+    bool starts = j == 0 || cell[j - 1] != cell[j];
+    if (!starts) {
+      const uint32_t q = pos[j - 1];
+      starts = entry_unsets<T>(values[q], is_null && is_null[q], def_nan);
     }
+    marker[j] = starts ? (uint32_t)j : 0u;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void set_values_write_kernel(const uint64_t *__restrict__ cell, const uint32_t *__restrict__ pos,
+                                                                  const double *__restrict__ values, const uint8_t *__restrict__ is_null,
+                                                                  const uint32_t *__restrict__ run, uint64_t n, T *dst, int32_t *dst_status,
+                                                                  uint32_t *dst_seq, uint32_t seq_base, int dst_nan_i) {
+  const bool dst_nan = dst_nan_i != 0;
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
+    if (j + 1 < n && cell[j + 1] == cell[j]) continue;  // not the cell's last slot
+    const uint32_t q = pos[j], r = run[j];
+    const double x = values[q];
+    const bool has = !(is_null && is_null[q]) && !is_default_f64(x, dst_nan);
+    const bool keeps_place = r == 0 || cell[r - 1] != cell[r];
+    write_cell<T>(dst, dst_status, dst_seq, dst_nan, cell[j], x, has, keeps_place, seq_base + pos[r]);
   }
 }
 
@@ -590,4 +652,109 @@ extern "C" int olap_store_copy_select(olap_store *target, const olap_store *sour
   if (rc) return rc;
   if ((rc = select_validate(source, ndim, lens, nlev, axis, n_sel, sel, true))) return rc;
   return select_copy(target, source, ndim, lens, nlev, axis, n_sel, sel);
+}
+
+// ---- set_values ------------------------------------------------------------------------------------------------
+
+int set_values_validate(const olap_store *s, uint64_t n, const uint64_t *indexes, const double *values) {
+  if (!s) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (n && (!indexes || !values)) return fail(OLAP_ERR_INVALID_ARGUMENT, "indexes/values is NULL");
+  for (uint64_t i = 0; i < n; ++i)
+    if (indexes[i] >= s->size)
+      return fail(OLAP_ERR_INDEX_RANGE, "entry %llu: cell index %llu out of bounds [0, %llu[", (unsigned long long)i, (unsigned long long)indexes[i],
+                  (unsigned long long)s->size);
+  return OLAP_OK;
+}
+
+// one batch of validated entries (n >= 1, n < 2^32): one upload, the sort, the mark + scan, the write, one sync
+static int set_values_batch(olap_store *s, uint64_t n, const uint64_t *indexes, const double *values, const uint8_t *is_null) {
+  // a tracked store keeps its lazy order (ascending flat index) exactly when each setValue would have kept it
+  // (order_before_set_value): every entry lies above all cells that may be set before it
+  uint32_t *seq = nullptr;
+  uint32_t seq_base = 0;
+  int rc;
+  if (s->track_order) {
+    bool lazy = !s->seq && (!s->maybe_nonempty || indexes[0] > s->hi_index);
+    for (uint64_t i = 1; i < n && lazy; ++i) lazy = indexes[i] > indexes[i - 1];
+    if (!lazy && (rc = order_before_select_write(s, n, &seq, &seq_base))) return rc;
+  }
+
+  // entries in one buffer: cells (8n) | values (8n) | nulls (n)
+  const size_t nb = is_null ? n : 0;
+  std::vector<unsigned char> host(16 * n + nb);
+  memcpy(host.data(), indexes, 8 * n);
+  memcpy(host.data() + 8 * n, values, 8 * n);
+  if (nb) memcpy(host.data() + 16 * n, is_null, nb);
+  int cell_bits = 1;
+  while (cell_bits < 64 && ((s->size - 1) >> cell_bits)) ++cell_bits;
+  unsigned char *entries = nullptr;
+  uint64_t *cell_sorted = nullptr;
+  uint32_t *pos_in = nullptr, *pos_sorted = nullptr;
+  void *tmp = nullptr;
+  size_t sort_bytes = 0, scan_bytes = 0;
+  hipError_t e = dev_alloc((void **)&entries, host.size());
+  if (e == hipSuccess) e = dev_alloc((void **)&cell_sorted, 8 * n);
+  if (e == hipSuccess) e = dev_alloc((void **)&pos_in, 4 * n);
+  if (e == hipSuccess) e = dev_alloc((void **)&pos_sorted, 4 * n);
+  uint64_t *cell_in = (uint64_t *)entries;
+  const double *dv = (const double *)(entries + 8 * n);
+  const uint8_t *dn = nb ? entries + 16 * n : nullptr;
+  uint32_t *marker = pos_in, *run = (uint32_t *)cell_in;  // (both free once the sort has read them)
+  if (e == hipSuccess)
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t *)cell_in, cell_sorted, (const uint32_t *)pos_in, pos_sorted,
+                                           (unsigned int)n, 0, cell_bits, (hipStream_t) nullptr);
+  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(nullptr, scan_bytes, (const uint32_t *)marker, run, hipcub::Max(), (unsigned int)n,
+                                                             (hipStream_t) nullptr);
+  if (e == hipSuccess) e = dev_alloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16));
+  if (e == hipSuccess) e = hipMemcpy(entries, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(iota_u32_kernel, grid_for(n), kBlock, 0, nullptr, pos_in, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint64_t *)cell_in, cell_sorted, (const uint32_t *)pos_in, pos_sorted,
+                                           (unsigned int)n, 0, cell_bits, (hipStream_t) nullptr);
+  const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
+  if (e == hipSuccess) {
+    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_mark_kernel<T>), grid_for(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+                                                 (const uint32_t *)pos_sorted, dv, dn, def_nan, n, marker));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(tmp, scan_bytes, (const uint32_t *)marker, run, hipcub::Max(), (unsigned int)n,
+                                                             (hipStream_t) nullptr);
+  if (e == hipSuccess) {
+    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_write_kernel<T>), grid_for(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+                                                 (const uint32_t *)pos_sorted, dv, dn, (const uint32_t *)run, n, (T *)s->values, s->status, seq,
+                                                 seq_base, def_nan));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  for (void *q : {(void *)entries, (void *)cell_sorted, (void *)pos_in, (void *)pos_sorted, tmp})
+    if (q) dev_free(q);
+  if (e != hipSuccess) return hip_fail(e, "set_values");
+  if (seq) {
+    order_after_select_write(s);
+  } else {  // what order_after_set_value leaves without seq
+    s->maybe_nonempty = true;
+    s->hi_index = std::max(s->hi_index, *std::max_element(indexes, indexes + n));
+  }
+  return OLAP_OK;
+}
+
+int set_values(olap_store *s, uint64_t n, const uint64_t *indexes, const double *values, const uint8_t *is_null) {
+  OnStoreDevice on_device__(s);
+  int rc = set_values_validate(s, n, indexes, values);
+  if (rc || n == 0) return rc;
+  if ((rc = require_device())) return rc;
+  // sequential setValue calls compose: a long list is written as consecutive batches (positions stay 32-bit)
+  constexpr uint64_t kBatch = 1ull << 26;
+  for (uint64_t first = 0; first < n; first += kBatch) {
+    const uint64_t k = std::min(kBatch, n - first);
+    if ((rc = set_values_batch(s, k, indexes + first, values + first, is_null ? is_null + first : nullptr))) return rc;
+  }
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_set_values(olap_store *store, uint64_t n, const uint64_t *indexes, const double *values, const uint8_t *is_null) {
+  return set_values(store, n, indexes, values, is_null);
 }

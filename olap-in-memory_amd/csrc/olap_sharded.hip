@@ -1644,6 +1644,32 @@ extern "C" int olap_sharded_store_set_value(olap_sharded_store *s, uint64_t inde
   HIP_TRY(hipSetDevice(s->comm->local[i].device));
   return olap_store_set_value(s->shard[i], li, value, is_null);
 }
+extern "C" int olap_sharded_store_set_values(olap_sharded_store *s, uint64_t n, const uint64_t *indexes, const double *values,
+                                             const uint8_t *is_null) {
+  if (!s) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (n && (!indexes || !values)) return fail(OLAP_ERR_INVALID_ARGUMENT, "indexes/values is NULL");
+  if (n == 0) return OLAP_OK;
+  const size_t k = s->shard.size();
+  std::vector<std::vector<uint64_t>> li(k);
+  std::vector<std::vector<double>> lv(k);
+  std::vector<std::vector<uint8_t>> ln(k);
+  for (uint64_t j = 0; j < n; ++j) {
+    if (indexes[j] >= s->size)
+      return fail(OLAP_ERR_INDEX_RANGE, "entry %llu: cell index %llu out of bounds [0, %llu[", (unsigned long long)j, (unsigned long long)indexes[j],
+                  (unsigned long long)s->size);
+    uint64_t at = 0;
+    const int i = owner_of(s, indexes[j], &at);
+    if (i < 0)
+      return fail(OLAP_ERR_INDEX_RANGE, "sharded: entry %llu: cell %llu belongs to a rank this process does not drive", (unsigned long long)j,
+                  (unsigned long long)indexes[j]);
+    li[i].push_back(at);
+    lv[i].push_back(values[j]);
+    if (is_null) ln[i].push_back(is_null[j]);
+  }
+  return for_each_shard(s, [&](int i, olap_store *sh) -> int {
+    return set_values(sh, li[i].size(), li[i].data(), lv[i].data(), is_null ? ln[i].data() : nullptr);
+  });
+}
 extern "C" int olap_sharded_store_fill(olap_sharded_store *s, double value) {
   return for_each_shard(s, [&](int, olap_store *sh) { return olap_store_fill(sh, value); });
 }

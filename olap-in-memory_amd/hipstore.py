@@ -41,6 +41,24 @@ def _levels(lens, levels):
     return lv, ax, n, keep, arr
 
 
+def _entries(indexes, values):
+    """(n, indexes, values, is_null or None) pointers of a set_values list (each keeps its array alive); None in `values`
+    means unset"""
+    idx = np.ascontiguousarray(indexes, dtype=np.uint64).reshape(-1)
+    vals = list(values) if not isinstance(values, np.ndarray) else values
+    if len(vals) != len(idx):
+        raise ValueError("set_values: %d indexes, %d values" % (len(idx), len(vals)))
+    if isinstance(vals, np.ndarray) and vals.dtype != object:
+        v, nulls = np.ascontiguousarray(vals, dtype=np.float64).reshape(-1), None
+    else:
+        nulls = np.fromiter((x is None for x in vals), dtype=np.uint8, count=len(vals))
+        v = np.fromiter((0.0 if x is None else float(x) for x in vals), dtype=np.float64, count=len(vals))
+        if not nulls.any():
+            nulls = None
+    return (len(idx), idx.ctypes.data_as(capi._pu64), v.ctypes.data_as(capi._pdbl),
+            nulls.ctypes.data_as(C.POINTER(C.c_uint8)) if nulls is not None else None)
+
+
 def _default_kind(default):
     if isinstance(default, str):
         return capi.DEFAULT_NAN if default == "NaN" else capi.DEFAULT_ZERO
@@ -333,6 +351,10 @@ class HipStore:
             check(self._lib.olap_store_set_value(self._h, int(index), 0.0, 1))
         else:
             check(self._lib.olap_store_set_value(self._h, int(index), float(value), 0))
+
+    def set_values(self, indexes, values):
+        """olap_store_set_values: set_value(indexes[i], values[i]) for every i, in list order, in one call (None unsets)."""
+        check(self._lib.olap_store_set_values(self._h, *_entries(indexes, values)))
 
     def fill(self, value):
         check(self._lib.olap_store_fill(self._h, float(value)))

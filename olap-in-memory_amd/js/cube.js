@@ -355,7 +355,45 @@ class Cube {
     this.setData(measureId, fromNestedObject(value, this.dimensions));
   }
 
+  /**
+   * src/cube.js hydrateFromSparseNestedObject.  The walk is the per-cell one (same `for...in` order, same item lookups),
+   * but it records each leaf and the store writes them all in one setValues call, which leaves the store exactly as the
+   * per-cell setValue calls would.  A leaf that is not a number, null or undefined (setValue's coercion could throw or
+   * differ), or an offset outside the store, sends the whole call down the per-cell path.  When the walk itself throws,
+   * the leaves recorded so far are written first, as the per-cell path would have written them.
+   */
   hydrateFromSparseNestedObject(measureId, obj, offset = 0, depth = 0) {
+    const store = this.storedMeasures[measureId];
+    if (store === undefined) return this._hydrateFromSparseNestedObjectPerCell(measureId, obj, offset, depth);
+    const size = store.size;
+    const indexes = [];
+    const values = [];
+    const perCell = {};
+    const walk = (node, at, d) => {
+      if (d === this.dimensions.length) {
+        if ((typeof node !== 'number' && node !== null && node !== undefined) || !Number.isInteger(at) || at < 0 || at >= size) throw perCell;
+        indexes.push(at);
+        values.push(node);
+        return;
+      }
+      const dimension = this.dimensions[d];
+      for (const key in node) {
+        const item = dimension.getRootIndexFromRootItem(key);
+        if (item !== -1) walk(node[key], at * dimension.numItems + item, d + 1);
+      }
+    };
+    try {
+      walk(obj, offset, depth);
+    } catch (e) {
+      if (e === perCell) return this._hydrateFromSparseNestedObjectPerCell(measureId, obj, offset, depth);
+      if (indexes.length) store.setValues(indexes, values);
+      throw e;
+    }
+    if (indexes.length) store.setValues(indexes, values);
+    return undefined;
+  }
+
+  _hydrateFromSparseNestedObjectPerCell(measureId, obj, offset = 0, depth = 0) {
     if (depth === this.dimensions.length) {
       this.storedMeasures[measureId].setValue(offset, obj);
       return;
@@ -363,7 +401,7 @@ class Cube {
     const dimension = this.dimensions[depth];
     for (const key in obj) {
       const at = dimension.getRootIndexFromRootItem(key);
-      if (at !== -1) this.hydrateFromSparseNestedObject(measureId, obj[key], offset * dimension.numItems + at, depth + 1);
+      if (at !== -1) this._hydrateFromSparseNestedObjectPerCell(measureId, obj[key], offset * dimension.numItems + at, depth + 1);
     }
   }
 

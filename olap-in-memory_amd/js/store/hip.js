@@ -283,6 +283,28 @@ class HipStore {
     this._writable.setValue(index, value);
   }
 
+  /**
+   * setValue(indexes[i], values[i]) for every i, in list order, as one device call: the same values, mask and key
+   * order.  A null or undefined value unsets its cell; other values are coerced to numbers as setValue does.
+   */
+  setValues(indexes, values) {
+    const n = indexes.length;
+    if (values.length !== n) throw new Error(`setValues: ${n} indexes, ${values.length} values`);
+    const idx = Float64Array.from(indexes);
+    const vals = new Float64Array(n);
+    let nulls;
+    for (let i = 0; i < n; ++i) {
+      const v = values[i];
+      if (v === null || v === undefined) {
+        if (nulls === undefined) nulls = new Uint8Array(n);
+        nulls[i] = 1;
+      } else {
+        vals[i] = +v;
+      }
+    }
+    this._writable.setValues(idx, vals, nulls);
+  }
+
   fill(value) {
     if (value === undefined || value === null) this._writable.fill(this._defaultValue);
     else this._writable.fill(value);

@@ -338,6 +338,62 @@ static napi_value StoreSetValue(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+static napi_value bad_args(napi_env env, const char *what);
+
+// setValues(indexes: Float64Array, values: Float64Array, nulls?: Uint8Array): setValue(indexes[i], values[i]) in list
+// order (nulls[i] != 0: unset); every index must be an integer >= 0 (RangeError), checked before the store sees any
+struct SetValuesArgs {
+  std::vector<uint64_t> idx;
+  const double *values = nullptr;
+  const uint8_t *nulls = nullptr;
+
+  bool decode(napi_env env, size_t argc, napi_value *argv) {
+    napi_typedarray_type ti, tv, tn;
+    size_t ni = 0, nv = 0, nn = 0;
+    void *pi = nullptr, *pv = nullptr, *pn = nullptr;
+    bool is_ta = false;
+    if (argc < 2 || napi_is_typedarray(env, argv[0], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[0], &ti, &ni, &pi, nullptr, nullptr) != napi_ok || ti != napi_float64_array ||
+        napi_is_typedarray(env, argv[1], &is_ta) != napi_ok || !is_ta ||
+        napi_get_typedarray_info(env, argv[1], &tv, &nv, &pv, nullptr, nullptr) != napi_ok || tv != napi_float64_array || ni != nv) {
+      bad_args(env, "setValues(indexes: Float64Array, values: Float64Array, nulls?: Uint8Array) of one length");
+      return false;
+    }
+    napi_valuetype t = napi_undefined;
+    if (argc > 2 && napi_typeof(env, argv[2], &t) != napi_ok) t = napi_null;
+    if (t != napi_undefined) {
+      if (napi_is_typedarray(env, argv[2], &is_ta) != napi_ok || !is_ta ||
+          napi_get_typedarray_info(env, argv[2], &tn, &nn, &pn, nullptr, nullptr) != napi_ok || tn != napi_uint8_array || nn != ni) {
+        bad_args(env, "setValues: nulls must be undefined or a Uint8Array of the indexes' length");
+        return false;
+      }
+      nulls = (const uint8_t *)pn;
+    }
+    values = (const double *)pv;
+    idx.resize(ni);
+    const double *d = (const double *)pi;
+    for (size_t i = 0; i < ni; ++i) {
+      if (!(d[i] >= 0) || d[i] != std::floor(d[i]) || d[i] >= 18446744073709551616.0) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "setValues: index %zu is not an integer >= 0 (%g)", i, d[i]);
+        napi_throw_range_error(env, nullptr, msg);
+        return false;
+      }
+      idx[i] = (uint64_t)d[i];
+    }
+    return true;
+  }
+};
+
+static napi_value StoreSetValues(napi_env env, napi_callback_info info) {
+  STORE_METHOD_PROLOGUE(3)
+  SetValuesArgs a;
+  if (!a.decode(env, argc, argv)) return nullptr;
+  int rc = olap_store_set_values(s, a.idx.size(), a.idx.data(), a.values, a.nulls);
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
+}
+
 static napi_value StoreFill(napi_env env, napi_callback_info info) {
   STORE_METHOD_PROLOGUE(1)
   double v = 0;
@@ -959,6 +1015,14 @@ static napi_value ShardedGetValue(napi_env env, napi_callback_info info) {
   if (rc) return throw_olap(env, rc);
   return is_set ? num(env, v) : undef;
 }
+static napi_value ShardedSetValues(napi_env env, napi_callback_info info) {
+  SHARDED_PROLOGUE(3)
+  SetValuesArgs a;
+  if (!a.decode(env, argc, argv)) return nullptr;
+  int rc = olap_sharded_store_set_values(s, a.idx.size(), a.idx.data(), a.values, a.nulls);
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
+}
 static napi_value ShardedSetValue(napi_env env, napi_callback_info info) {
   SHARDED_PROLOGUE(2)
   double idx = 0, v = 0;
@@ -1252,6 +1316,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"countSet", nullptr, StoreCountSet, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getValue", nullptr, StoreGetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setValue", nullptr, StoreSetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"setValues", nullptr, StoreSetValues, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fill", nullptr, StoreFill, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"total", nullptr, StoreTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"toSparse", nullptr, StoreToSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -1284,6 +1349,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"getStatus", nullptr, ShardedGetStatus, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"getValue", nullptr, ShardedGetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setValue", nullptr, ShardedSetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"setValues", nullptr, ShardedSetValues, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fill", nullptr, ShardedFill, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"total", nullptr, ShardedTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"clone", nullptr, ShardedClone, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import capi
 from .capi import check
-from .hipstore import HipStore, Plan, _default_kind, _levels, _method_code, _tables, _u32
+from .hipstore import HipStore, Plan, _default_kind, _entries, _levels, _method_code, _tables, _u32
 
 NP_OF_DTYPE = {0: np.int32, 1: np.uint32, 2: np.float32, 3: np.float64}
 NAME_OF_DTYPE = {0: "int32", 1: "uint32", 2: "float32", 3: "float64"}
@@ -351,6 +351,10 @@ class ShardedStore:
             check(self._lib.olap_sharded_store_set_value(self._h, int(index), 0.0, 1))
         else:
             check(self._lib.olap_sharded_store_set_value(self._h, int(index), float(value), 0))
+
+    def set_values(self, indexes, values):
+        """HipStore.set_values over the shards: the entries are split by owner, list order kept within a shard."""
+        check(self._lib.olap_sharded_store_set_values(self._h, *_entries(indexes, values)))
 
     def fill(self, value):
         check(self._lib.olap_sharded_store_fill(self._h, float(value)))
