@@ -15,6 +15,7 @@ import pytest
 from conftest import load_package
 from golden_util import GOLDEN, config_cube, mulberry32_at, dec_num, dec_store, default_of, expected_typed, is_default_typed, load_cases, same_typed
 from oracle.oracle import OracleStore, to_typed
+from select_reference import mulberry_cell_values as _mulberry_cell_values
 
 pytestmark = pytest.mark.gpu
 
@@ -1367,17 +1368,6 @@ def test_sparse_form_round_trip(type_name, default):
         assert np.array_equal(v.astype(np.float64), vals[keep])
         back = pkg.HipStore.from_sparse(n, type_name, default, idx, v)
         assert same_typed(back.get_data(), s.get_data()) and np.array_equal(back.get_status(), s.get_status())
-
-
-def _mulberry_cell_values(cells, seed=20240807):
-    """fround(0.5 + u(2*cell + 1)) for arbitrary (64-bit) cell indices — the device generator in closed form."""
-    cells = np.asarray(cells, dtype=np.uint64)
-    a = ((np.uint64(seed) + (np.uint64(2) * cells + np.uint64(1)) * np.uint64(0x6D2B79F5)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    with np.errstate(over="ignore"):
-        t = (a ^ (a >> np.uint32(15))) * (np.uint32(1) | a)
-        t = (t + ((t ^ (t >> np.uint32(7))) * (np.uint32(61) | t))) ^ t
-        r = t ^ (t >> np.uint32(14))
-    return (0.5 + r.astype(np.float64) / 4294967296.0).astype(np.float32)
 
 
 @pytest.mark.parametrize("axis", [0, 1, 2])

@@ -153,3 +153,73 @@ def test_two_shards_on_one_device(dtype):
         with pytest.raises(pkg.OlapError, match=r"entry 1: cell index 105 out of bounds"):
             got.set_values([0, size], [1.0, 2.0])
         assert got.gather().get_data().tobytes() == before
+
+
+def last_writes(idx, vals, size):
+    """the numpy last-write-wins model: (value of each cell's last entry, or NaN where none; whether it has one)"""
+    last_pos = np.full(size, -1, dtype=np.int64)
+    np.maximum.at(last_pos, np.asarray(idx, dtype=np.int64), np.arange(len(idx), dtype=np.int64))
+    has = last_pos >= 0
+    return np.where(has, np.asarray(vals)[np.maximum(last_pos, 0)], np.nan), has
+
+
+def test_batches_compose_across_the_2_26_split():
+    """2^26 + 2^12 entries are written as two batches: the second must see the first one's result, as the sequential
+    setValue calls would (numpy entries, a plain Float32 store with a 0 default: a cell ends set exactly when its last
+    value is non-zero)"""
+    size = 1 << 20
+    split = 1 << 26
+    k = 1 << 12
+    n = split + k
+    rng = np.random.default_rng(26)
+    idx = rng.integers(0, size, size=n).astype(np.uint64)
+    vals = rng.integers(-3, 4, size=n).astype(np.float64)
+    # the tail revisits cells the first batch leaves set and cells it leaves unset: it unsets, overwrites and sets them
+    before, _ = last_writes(idx[:split], vals[:split], size)
+    picks = np.concatenate([rng.choice(np.nonzero(before != 0)[0], size=k // 2), rng.choice(np.nonzero(before == 0)[0], size=k // 2)])
+    idx[split:] = picks.astype(np.uint64)
+    vals[split:] = np.where(rng.random(k) < 0.3, 0.0, rng.integers(5, 9, size=k).astype(np.float64))
+    last, has = last_writes(idx, vals, size)
+    assert has.all()
+    assert np.any((before[picks] != 0) & (last[picks] == 0)) and np.any((before[picks] == 0) & (last[picks] != 0))
+    assert np.any((before[picks] != 0) & (last[picks] != 0) & (last[picks] != before[picks]))
+    s = pkg.HipStore(size, "float32", 0.0)
+    s.set_values(idx, vals)
+    assert np.array_equal((s.get_status() & 2) != 0, last != 0)
+    assert np.array_equal(s.get_data(), last.astype(np.float32))
+
+
+def test_set_values_beyond_2_32_cells():
+    """a 5x10^9-cell Float32 store (20 GB): the sort runs on 33 key bits; the written cells are read back one by one, and
+    a filtered total over rows that straddle cell 2^32 is the exact sum of the generator's values"""
+    from fractions import Fraction
+
+    from select_reference import mulberry_cell_values
+
+    shape = [5000, 1000, 1000]
+    n = int(np.prod(shape))
+    s = pkg.HipStore(n, "float32", 0.0)
+    pkg.capi.check(pkg.lib().olap_fill_seeded(s.values_ptr, None, n, 0, 2, 20240807, 1.0, None))
+    two32 = 1 << 32
+    idx = [two32 + 1, two32 - 1, two32, n - 1, two32, two32 + 1, 7, two32 - 1, two32 + 1]
+    vals = [3.0, 5.0, 0.0, 11.0, 6.0, None, 2.5, 9.0, 4.0]
+    s.set_values(idx, vals)
+    want = {two32 - 1: 9.0, two32: 6.0, two32 + 1: 4.0, n - 1: 11.0, 7: 2.5}
+    for cell, v in want.items():
+        assert s.get_value(cell) == (v, True), cell
+    assert s.get_value(two32 + 2) == (float(mulberry_cell_values([two32 + 2])[0]), True)
+    # rows 4 294 and 4 293 (cell 2^32 is row 4 294, column 967 296), ROW mode; then three cells around 2^32, FLAT mode
+    r0 = two32 // 1_000_000
+    cells = np.concatenate([np.arange(r0 * 10 ** 6, (r0 + 1) * 10 ** 6), np.arange((r0 - 1) * 10 ** 6, r0 * 10 ** 6)]).astype(np.uint64)
+    terms = mulberry_cell_values(cells).astype(np.float64)
+    for cell, v in want.items():
+        terms[cells == cell] = v
+    scaled = terms * 2 ** 24  # Float32 values in [0.5, 1.5) and small integers: multiples of 2^-24
+    assert np.array_equal(scaled, np.floor(scaled))
+    exact = Fraction(int(scaled.astype(np.int64).sum()), 2 ** 24)
+    got, path = s.select_total(shape, [(0, [r0, r0 - 1]), (1, list(range(1000))), (2, list(range(1000)))])
+    assert path == "device" and got == float(exact)
+    i1, i2 = (two32 % 10 ** 6) // 1000, two32 % 1000
+    got, path = s.select_total(shape, [(2, [i2 + 1, i2, i2 - 1]), (0, [r0]), (1, [i1])])
+    assert path == "device" and got == 4.0 + 6.0 + 9.0
+    del s
