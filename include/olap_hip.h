@@ -347,6 +347,19 @@ int olap_store_select_total(const olap_store *store, int ndim, const uint32_t *l
  * stores may differ, both live on one device.  Entries must be >= 0.  A tracked target gets the reference's key order. */
 int olap_store_copy_select(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev,
                            const int *axis, const uint32_t *n_sel, const int32_t *const *sel);
+/* olap_store_select_total of a computed measure: the value of a combination is the formula program (olap_eval_formula's
+ * code and constants, no SCALAR operand) evaluated at its cell over n_inputs (1..OLAP_FORMULA_MAX_INPUTS) stores of
+ * any cell types and defaults, each of the product of lens cells, on one device.  A -1 entry evaluates the program on
+ * every input's own default.  Same certificate and sequential fallback; the values are those of olap_eval_formula. */
+int olap_formula_select_total(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                              const olap_store *const *inputs, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                              const uint32_t *n_sel, const int32_t *const *sel, double *total, int *exact_path);
+/* olap_store_copy_select with the formula as the source: target.setValue(pos, formula(pos)) over the distinct
+ * combinations.  The target may be one of the inputs (each cell is read before it is written; a selection with
+ * repeats or free keys revisits cells, which the caller then copies cell by cell).  Entries must be >= 0. */
+int olap_store_copy_select_formula(olap_store *target, const int32_t *code, int n_code, const double *consts, int n_consts,
+                                   int n_inputs, const olap_store *const *inputs, int ndim, const uint32_t *lens, int nlev,
+                                   const int *axis, const uint32_t *n_sel, const int32_t *const *sel);
 
 /* olap_eval_formula over stores (all of the same size) into a host float64 array */
 int olap_store_eval_formula(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,

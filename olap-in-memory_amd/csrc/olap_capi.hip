@@ -2120,8 +2120,7 @@ extern "C" int olap_diag_read_ceiling(const void *device, uint64_t bytes, void *
 }
 
 // ---- computed measures --------------------------------------------------------------------------
-// the kernel is not templated: it lives in this translation unit
-static int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars) {
+int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars) {
   if (!code || n_code <= 0 || n_code > OLAP_FORMULA_MAX_CODE) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula program has %d words (1..%d allowed)", n_code, OLAP_FORMULA_MAX_CODE);
   if (n_consts < 0 || n_consts > OLAP_FORMULA_MAX_CONSTS || n_inputs < 0 || n_inputs > OLAP_FORMULA_MAX_INPUTS || n_scalars < 0 ||
       n_scalars > OLAP_FORMULA_MAX_INPUTS)

@@ -130,6 +130,8 @@ OLAP_INTERNAL int select_cert(const olap_store *s, int ndim, const uint32_t *len
                               double *sum, double *abs_sum, int *min_exp, unsigned *flags);
 // 1 and *total when the certificate proves the order-free sum (times m) equal to the sequential one
 OLAP_INTERNAL int select_certified_total(double sum, double abs_sum, int min_exp, unsigned flags, double m, double *total);
+// the program checks of olap_eval_formula (olap_capi.hip): length, operands, stack
+OLAP_INTERNAL int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars);
 OLAP_INTERNAL int select_copy(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
                               const uint32_t *n_sel, const int32_t *const *sel);
 

@@ -3464,86 +3464,106 @@ struct FormulaProgram {
 __device__ __forceinline__ bool js_truthy(double v) { return v == v && v != 0.0; }
 __device__ __forceinline__ double js_round(double v) { return floor(v + 0.5); }  // Math.round: halves go up
 
+// getValue(i) of input k (in-memory.js:118-120): the stored value, or the default where unset
+__device__ __forceinline__ double formula_input(const FormulaProgram &p, int k, uint64_t i) {
+  double v;
+  switch (p.in_dtype[k]) {
+    case OLAP_INT32: v = (double)((const int32_t *)p.in_values[k])[i]; break;
+    case OLAP_UINT32: v = (double)((const uint32_t *)p.in_values[k])[i]; break;
+    case OLAP_FLOAT32: v = (double)((const float *)p.in_values[k])[i]; break;
+    default: v = ((const double *)p.in_values[k])[i]; break;
+  }
+  if (p.in_status[k] && !(p.in_status[k][i] & OLAP_STATUS_SET)) v = p.in_def_nan[k] ? __builtin_nan("") : 0.0;
+  return v;
+}
+
+// The program at one cell; input(k) gives the value of input k there.
+template <int STACK, typename Input>
+__device__ __forceinline__ double formula_run(const FormulaProgram &p, Input input) {
+  double st[STACK];
+  int sp = 0;
+  for (int pc = 0; pc < p.n_code; ++pc) {
+    const int op = p.code[pc];
+    if (op == F_CONST) {
+      st[sp++] = p.consts[p.code[++pc]];
+    } else if (op == F_INPUT) {
+      st[sp++] = input(p.code[++pc]);
+    } else if (op == F_SCALAR) {
+      st[sp++] = p.scalars[p.code[++pc]];
+    } else if (op == F_SELECT) {
+      const double c = st[sp - 3], a = st[sp - 2], b = st[sp - 1];
+      sp -= 2;
+      st[sp - 1] = js_truthy(c) ? a : b;
+    } else if (op == F_NEG || op == F_ISNAN || op >= F_ABS) {
+      const double a = st[sp - 1];
+      double r;
+      switch (op) {
+        case F_NEG: r = -a; break;
+        case F_ISNAN: r = (a != a) ? 1.0 : 0.0; break;
+        case F_ABS: r = fabs(a); break;
+        case F_CEIL: r = ceil(a); break;
+        case F_FLOOR: r = floor(a); break;
+        case F_ROUND: r = js_round(a); break;
+        case F_TRUNC: r = trunc(a); break;
+        case F_SQRT: r = sqrt(a); break;
+        case F_CBRT: r = cbrt(a); break;
+        case F_EXP: r = exp(a); break;
+        case F_LN: r = log(a); break;
+        case F_LOG10: r = log10(a); break;
+        case F_LOG2: r = log2(a); break;
+        case F_SIGN: r = (a != a) ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : a)); break;
+        case F_SIN: r = sin(a); break;
+        case F_COS: r = cos(a); break;
+        case F_TAN: r = tan(a); break;
+        case F_ASIN: r = asin(a); break;
+        case F_ACOS: r = acos(a); break;
+        case F_ATAN: r = atan(a); break;
+        default: r = js_truthy(a) ? 0.0 : 1.0; break;  // F_NOT
+      }
+      st[sp - 1] = r;
+    } else {
+      const double a = st[sp - 2], b = st[sp - 1];
+      --sp;
+      double r;
+      switch (op) {
+        case F_ADD: r = a + b; break;
+        case F_SUB: r = a - b; break;
+        case F_MUL: r = a * b; break;
+        case F_DIV: r = a / b; break;
+        case F_MOD: r = fmod(a, b); break;
+        case F_POW: r = pow(a, b); break;
+        case F_NANADD: r = (a != a && b == b) ? b : ((a == a && b != b) ? a : a + b); break;  // src/parser.js:18-23
+        case F_MIN: r = js_min(a, b); break;
+        case F_MAX: r = js_max(a, b); break;
+        case F_ATAN2: r = atan2(a, b); break;
+        case F_HYPOT: r = hypot(a, b); break;
+        default: {  // F_ROUNDTO
+          const double f = pow(10.0, trunc(b));
+          r = js_round(a * f) / f;
+          break;
+        }
+      }
+      st[sp - 1] = r;
+    }
+  }
+  return sp > 0 ? st[sp - 1] : __builtin_nan("");
+}
+
+// the program at cell i (src/cube.js:326-363)
+template <int STACK>
+__device__ __forceinline__ double formula_at(const FormulaProgram &p, uint64_t i) {
+  return formula_run<STACK>(p, [&](int k) { return formula_input(p, k, i); });
+}
+
+// the program at a cell that does not exist (a -1 selection entry): every input reads its own default
+template <int STACK>
+__device__ __forceinline__ double formula_at_missing(const FormulaProgram &p) {
+  return formula_run<STACK>(p, [&](int k) { return p.in_def_nan[k] ? __builtin_nan("") : 0.0; });
+}
+
 template <int STACK>  // a template only so that the header may be included by several translation units
 __global__ __launch_bounds__(kBlock) void eval_formula_kernel(const FormulaProgram p, double *__restrict__ out, uint64_t n) {
-  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-    double st[STACK];
-    int sp = 0;
-    for (int pc = 0; pc < p.n_code; ++pc) {
-      const int op = p.code[pc];
-      if (op == F_CONST) {
-        st[sp++] = p.consts[p.code[++pc]];
-      } else if (op == F_INPUT) {
-        const int k = p.code[++pc];
-        double v;
-        switch (p.in_dtype[k]) {  // getValue(i): the stored value, or the default where unset
-          case OLAP_INT32: v = (double)((const int32_t *)p.in_values[k])[i]; break;
-          case OLAP_UINT32: v = (double)((const uint32_t *)p.in_values[k])[i]; break;
-          case OLAP_FLOAT32: v = (double)((const float *)p.in_values[k])[i]; break;
-          default: v = ((const double *)p.in_values[k])[i]; break;
-        }
-        if (p.in_status[k] && !(p.in_status[k][i] & OLAP_STATUS_SET)) v = p.in_def_nan[k] ? __builtin_nan("") : 0.0;
-        st[sp++] = v;
-      } else if (op == F_SCALAR) {
-        st[sp++] = p.scalars[p.code[++pc]];
-      } else if (op == F_SELECT) {
-        const double c = st[sp - 3], a = st[sp - 2], b = st[sp - 1];
-        sp -= 2;
-        st[sp - 1] = js_truthy(c) ? a : b;
-      } else if (op == F_NEG || op == F_ISNAN || op >= F_ABS) {
-        const double a = st[sp - 1];
-        double r;
-        switch (op) {
-          case F_NEG: r = -a; break;
-          case F_ISNAN: r = (a != a) ? 1.0 : 0.0; break;
-          case F_ABS: r = fabs(a); break;
-          case F_CEIL: r = ceil(a); break;
-          case F_FLOOR: r = floor(a); break;
-          case F_ROUND: r = js_round(a); break;
-          case F_TRUNC: r = trunc(a); break;
-          case F_SQRT: r = sqrt(a); break;
-          case F_CBRT: r = cbrt(a); break;
-          case F_EXP: r = exp(a); break;
-          case F_LN: r = log(a); break;
-          case F_LOG10: r = log10(a); break;
-          case F_LOG2: r = log2(a); break;
-          case F_SIGN: r = (a != a) ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : a)); break;
-          case F_SIN: r = sin(a); break;
-          case F_COS: r = cos(a); break;
-          case F_TAN: r = tan(a); break;
-          case F_ASIN: r = asin(a); break;
-          case F_ACOS: r = acos(a); break;
-          case F_ATAN: r = atan(a); break;
-          default: r = js_truthy(a) ? 0.0 : 1.0; break;  // F_NOT
-        }
-        st[sp - 1] = r;
-      } else {
-        const double a = st[sp - 2], b = st[sp - 1];
-        --sp;
-        double r;
-        switch (op) {
-          case F_ADD: r = a + b; break;
-          case F_SUB: r = a - b; break;
-          case F_MUL: r = a * b; break;
-          case F_DIV: r = a / b; break;
-          case F_MOD: r = fmod(a, b); break;
-          case F_POW: r = pow(a, b); break;
-          case F_NANADD: r = (a != a && b == b) ? b : ((a == a && b != b) ? a : a + b); break;  // src/parser.js:18-23
-          case F_MIN: r = js_min(a, b); break;
-          case F_MAX: r = js_max(a, b); break;
-          case F_ATAN2: r = atan2(a, b); break;
-          case F_HYPOT: r = hypot(a, b); break;
-          default: {  // F_ROUNDTO
-            const double f = pow(10.0, trunc(b));
-            r = js_round(a * f) / f;
-            break;
-          }
-        }
-        st[sp - 1] = r;
-      }
-    }
-    out[i] = sp > 0 ? st[sp - 1] : __builtin_nan("");
-  }
+  for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = formula_at<STACK>(p, i);
 }
 
 // ======================================================================= sparse <-> dense

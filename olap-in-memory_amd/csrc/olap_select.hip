@@ -26,6 +26,7 @@
 
 #include "olap_device.hpp"
 #include "olap_internal.hpp"
+#include "olap_kernels.hpp"
 
 using namespace olap;
 
@@ -87,6 +88,35 @@ __device__ __forceinline__ double read_cell(const T *values, const int32_t *stat
                                                                                                : (def_nan ? __builtin_nan("") : 0.0);
 }
 
+// Where a selection's values come from.  at(i): getValue of cell i as a JS number; missing(): the value of a cell that
+// does not exist (a -1 entry); missing_row(c, n): cert_add of n such values by the workgroup (one lane or all).
+template <typename T>
+struct StoreSource {  // one stored measure
+  const T *__restrict__ values;
+  const int32_t *__restrict__ status;
+  int def_nan_i;
+  __device__ __forceinline__ double at(uint64_t i) const { return read_cell<T>(values, status, i, def_nan_i != 0); }
+  __device__ __forceinline__ double missing() const { return def_nan_i != 0 ? __builtin_nan("") : 0.0; }
+  __device__ __forceinline__ void missing_row(Cert &c, uint64_t) const {
+    if (def_nan_i != 0 && threadIdx.x == 0) c.flags |= kFlagNaN;  // (the default 0 adds nothing)
+  }
+};
+
+template <typename T>
+StoreSource<T> store_source(const olap_store *s) {
+  return StoreSource<T>{(const T *)s->values, mask_needed(s), s->default_kind == OLAP_DEFAULT_NAN};
+}
+
+struct FormulaSource {  // a computed measure: the program (in device memory) evaluated in registers at each cell
+  const FormulaProgram *__restrict__ prog;
+  __device__ __forceinline__ double at(uint64_t i) const { return formula_at<OLAP_FORMULA_MAX_STACK>(*prog, i); }
+  __device__ __forceinline__ double missing() const { return formula_at_missing<OLAP_FORMULA_MAX_STACK>(*prog); }
+  __device__ __forceinline__ void missing_row(Cert &c, uint64_t n) const {
+    const double x = missing();
+    for (uint64_t i = threadIdx.x; i < n; i += kBlock) cert_add(c, x);
+  }
+};
+
 // The gathered part of a selection: `ngl` levels (cube order, outermost first) in front of a contiguous run of `run`
 // cells that the trailing identity levels fold into.  Row g of the rows x run view starts at the cell
 // sum_l idx[off[l] + digit_l(g)] * stride[l], or does not exist when one of those entries is -1.
@@ -128,18 +158,17 @@ __device__ __forceinline__ int64_t row_base(const GatherPlan &p, uint64_t g) {
 // both have been added nothing finite can bring the sum back); a single-signed inf gives that inf, because under the
 // condition the finite partial sums never overflow.  Otherwise (the condition fails) the host re-adds the values in
 // nesting order (select_gather_kernel).
-template <typename T, bool VEC>
-__global__ __launch_bounds__(kBlock) void select_total_kernel(const T *__restrict__ values, const int32_t *__restrict__ status, int def_nan_i,
-                                                              GatherPlan p, Cert *__restrict__ partial) {
-  constexpr int V = 16 / sizeof(T);
-  const bool def_nan = def_nan_i != 0;
+//
+// VEC (a StoreSource<T> only): whole 16-byte groups of a row are read with one load each.
+template <typename Src, typename T, bool VEC>
+__global__ __launch_bounds__(kBlock) void select_total_kernel(const Src src, GatherPlan p, Cert *__restrict__ partial) {
   Cert c{0.0, 0.0, INT_MAX, 0u};
   if (p.flat) {
     const uint64_t cells = p.rows * p.run;
     for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < cells; t += (uint64_t)gridDim.x * kBlock) {
       const uint64_t g = t / p.run, r = t - g * p.run;
       const int64_t base = row_base(p, g);
-      cert_add(c, base < 0 ? (def_nan ? __builtin_nan("") : 0.0) : read_cell<T>(values, status, (uint64_t)base + r, def_nan));
+      cert_add(c, base < 0 ? src.missing() : src.at((uint64_t)base + r));
     }
   } else {
     const uint64_t units = p.rows * p.chunks;
@@ -148,26 +177,32 @@ __global__ __launch_bounds__(kBlock) void select_total_kernel(const T *__restric
       const int64_t base = row_base(p, g);
       const uint64_t lo = k * p.chunk, hi = lo + p.chunk < p.run ? lo + p.chunk : p.run;
       if (base < 0) {  // a row that does not exist: every cell reads the default
-        if (def_nan && threadIdx.x == 0) c.flags |= kFlagNaN;
+        src.missing_row(c, hi - lo);
         continue;
       }
       const uint64_t first = (uint64_t)base + lo, n = hi - lo;
       uint64_t done = 0;
-      if (VEC && (first % V) == 0) {
-        const uint64_t groups = n / V;
-        for (uint64_t q = threadIdx.x; q < groups; q += kBlock) {
-          const Vec<T, V> x = load_stream<T, V>(values + first + q * V);
-          Vec<int32_t, V> sx;
-          if (status) sx = load_stream<int32_t, V>(status + first + q * V);
+      if constexpr (VEC) {
+        constexpr int V = 16 / sizeof(T);
+        const T *values = src.values;
+        const int32_t *status = src.status;
+        const bool def_nan = src.def_nan_i != 0;
+        if ((first % V) == 0) {
+          const uint64_t groups = n / V;
+          for (uint64_t q = threadIdx.x; q < groups; q += kBlock) {
+            const Vec<T, V> x = load_stream<T, V>(values + first + q * V);
+            Vec<int32_t, V> sx;
+            if (status) sx = load_stream<int32_t, V>(status + first + q * V);
 #pragma unroll
-          for (int e = 0; e < V; ++e) {
-            const bool set = cell_is_set<T>(x.v[e], status ? sx.v[e] : OLAP_STATUS_SET, status != nullptr, def_nan);
-            cert_add(c, set ? Cell<T>::to_f64(x.v[e]) : (def_nan ? __builtin_nan("") : 0.0));
+            for (int e = 0; e < V; ++e) {
+              const bool set = cell_is_set<T>(x.v[e], status ? sx.v[e] : OLAP_STATUS_SET, status != nullptr, def_nan);
+              cert_add(c, set ? Cell<T>::to_f64(x.v[e]) : (def_nan ? __builtin_nan("") : 0.0));
+            }
           }
+          done = groups * V;
         }
-        done = groups * V;
       }
-      for (uint64_t i = done + threadIdx.x; i < n; i += kBlock) cert_add(c, read_cell<T>(values, status, first + i, def_nan));
+      for (uint64_t i = done + threadIdx.x; i < n; i += kBlock) cert_add(c, src.at(first + i));
     }
   }
 #pragma unroll
@@ -238,13 +273,11 @@ __device__ __forceinline__ int64_t nest_cell(const NestPlan &p, uint64_t rank) {
 }
 
 // the value of every combination of ranks [first, first + n) in nesting order, as a JS number
-template <typename T>
-__global__ __launch_bounds__(kBlock) void select_gather_kernel(const T *__restrict__ values, const int32_t *__restrict__ status, int def_nan_i,
-                                                               NestPlan p, uint64_t first, uint64_t n, double *__restrict__ out) {
-  const bool def_nan = def_nan_i != 0;
+template <typename Src>
+__global__ __launch_bounds__(kBlock) void select_gather_kernel(const Src src, NestPlan p, uint64_t first, uint64_t n, double *__restrict__ out) {
   for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
     const int64_t cell = nest_cell(p, first + t);
-    out[t] = cell < 0 ? (def_nan ? __builtin_nan("") : 0.0) : read_cell<T>(values, status, (uint64_t)cell, def_nan);
+    out[t] = cell < 0 ? src.missing() : src.at((uint64_t)cell);
   }
 }
 
@@ -268,15 +301,14 @@ __device__ __forceinline__ void write_cell(T *dst, int32_t *dst_status, uint32_t
 
 // target.setValue(pos, source.getValue(pos)) (src/cube.js:859-888) for every combination; the levels are free of
 // repeats, so every lane owns a distinct cell.  A tracked target appends a newly set cell at seq_base + its rank in
-// nesting order.
-template <typename S, typename T>
-__global__ __launch_bounds__(kBlock) void copy_select_kernel(const S *__restrict__ src, const int32_t *__restrict__ src_status, int src_nan_i,
-                                                             T *dst, int32_t *dst_status, uint32_t *dst_seq, uint32_t seq_base, int dst_nan_i,
-                                                             NestPlan p, uint64_t n) {
-  const bool src_nan = src_nan_i != 0, dst_nan = dst_nan_i != 0;
+// nesting order.  The target may be one of a formula's inputs: each lane reads its own cell before it writes it.
+template <typename Src, typename T>
+__global__ __launch_bounds__(kBlock) void copy_select_kernel(const Src src, T *dst, int32_t *dst_status, uint32_t *dst_seq, uint32_t seq_base,
+                                                             int dst_nan_i, NestPlan p, uint64_t n) {
+  const bool dst_nan = dst_nan_i != 0;
   for (uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x; t < n; t += (uint64_t)gridDim.x * kBlock) {
     const uint64_t cell = (uint64_t)nest_cell(p, t);
-    const double x = read_cell<S>(src, src_status, cell, src_nan);
+    const double x = src.at(cell);
     write_cell<T>(dst, dst_status, dst_seq, dst_nan, cell, x, !is_default_f64(x, dst_nan), true, seq_base + (uint32_t)t);
   }
 }
@@ -330,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void set_values_write_kernel(const uint64_t
   }
 }
 
-unsigned grid_for(uint64_t n) {
+unsigned select_grid(uint64_t n) {
   const uint64_t want = (n + kBlock - 1) / kBlock;
   return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, kSelBlocks));
 }
@@ -393,11 +425,12 @@ int select_validate(const olap_store *store, int ndim, const uint32_t *lens, int
   return OLAP_OK;
 }
 
-// The order-free part of select_total over ONE store: lists per cube dimension (cube order, repeats and -1 allowed).
-// Free levels are not seen here.  *cert receives the certificate of one copy of the terms.
-int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint32_t *n_by_dim, const int32_t *const *sel_by_dim, double *sum,
-                double *abs_sum, int *min_exp, unsigned *flags) {
-  OnStoreDevice on_device__(s);
+// The order-free part of select_total: lists per cube dimension (cube order, repeats and -1 allowed).  Free levels are
+// not seen here.  `launch(p, blocks, partial)` starts select_total_kernel for the value source; the certificate of one
+// copy of the terms comes back.  Runs on the current device.
+template <typename Launch>
+static int cert_of(int ndim, const uint32_t *lens, const uint32_t *n_by_dim, const int32_t *const *sel_by_dim, Launch launch, double *sum,
+                   double *abs_sum, int *min_exp, unsigned *flags) {
   *sum = 0.0;
   *abs_sum = 0.0;
   *min_exp = INT_MAX;
@@ -438,7 +471,7 @@ int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint3
   unsigned blocks;
   if (run < 1024) {
     p.flat = 1;
-    blocks = grid_for(cells);
+    blocks = select_grid(cells);
   } else {
     p.flat = 0;
     // about kSelBlocks units, each a contiguous piece of one row of at least 1024 cells (a multiple of 16 cells)
@@ -460,12 +493,7 @@ int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint3
   Cert *partial = nullptr;
   hipError_t e = dev_alloc((void **)&partial, (blocks + 1) * sizeof(Cert));
   if (e == hipSuccess) {
-    const bool vec = (((uintptr_t)s->values | (uintptr_t)mask_needed(s)) & 15u) == 0;
-    const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
-    SEL_DISPATCH(s->dtype, T, {
-      if (vec) hipLaunchKernelGGL((select_total_kernel<T, true>), blocks, kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), def_nan, p, partial);
-      else hipLaunchKernelGGL((select_total_kernel<T, false>), blocks, kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), def_nan, p, partial);
-    });
+    launch(p, blocks, partial);
     e = hipGetLastError();
     if (e == hipSuccess) {
       hipLaunchKernelGGL(select_finish_kernel, 1, kBlock, 0, nullptr, partial, blocks, pinned ? pinned : partial + blocks);
@@ -489,6 +517,20 @@ int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint3
   if (dev_lists) dev_free(dev_lists);
   if (e != hipSuccess) return hip_fail(e, "select_total");
   return OLAP_OK;
+}
+
+// select_total's order-free part over ONE store
+int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint32_t *n_by_dim, const int32_t *const *sel_by_dim, double *sum,
+                double *abs_sum, int *min_exp, unsigned *flags) {
+  OnStoreDevice on_device__(s);
+  const bool vec = (((uintptr_t)s->values | (uintptr_t)mask_needed(s)) & 15u) == 0;
+  auto launch = [&](const GatherPlan &p, unsigned blocks, Cert *partial) {
+    SEL_DISPATCH(s->dtype, T, {
+      if (vec) hipLaunchKernelGGL((select_total_kernel<StoreSource<T>, T, true>), blocks, kBlock, 0, nullptr, store_source<T>(s), p, partial);
+      else hipLaunchKernelGGL((select_total_kernel<StoreSource<T>, T, false>), blocks, kBlock, 0, nullptr, store_source<T>(s), p, partial);
+    });
+  };
+  return cert_of(ndim, lens, n_by_dim, sel_by_dim, launch, sum, abs_sum, min_exp, flags);
 }
 
 // Applies the certificate.  Returns 1 and sets *total when the order-free result is the sequential one; 0 otherwise.
@@ -527,9 +569,10 @@ static void by_dimension(int ndim, int nlev, const int *axis, const uint32_t *n_
 }
 
 // The reference's order, always: every combination's value in nesting order, added left to right from +0.
-static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim, int nlev, const int *axis, const uint32_t *n_sel,
-                             const int32_t *const *sel, double *total) {
-  OnStoreDevice on_device__(s);
+// `launch(p, first, k, out)` starts select_gather_kernel for the value source.  Runs on the current device.
+template <typename Launch>
+static int sequential_of(const uint32_t *lens, int ndim, int nlev, const int *axis, const uint32_t *n_sel, const int32_t *const *sel, Launch launch,
+                         double *total) {
   static thread_local NestPlan p;
   memset(&p, 0, offsetof(NestPlan, inl));
   std::vector<uint64_t> stride(ndim);
@@ -559,8 +602,7 @@ static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim
   double acc = 0.0;
   for (uint64_t first = 0; e == hipSuccess && first < n; first += chunk) {
     const uint64_t k = std::min(chunk, n - first);
-    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((select_gather_kernel<T>), grid_for(k), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
-                                                 s->default_kind == OLAP_DEFAULT_NAN, p, first, k, dev));
+    launch(p, first, k, dev);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(host.data(), dev, k * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess)
@@ -571,6 +613,16 @@ static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim
   if (e != hipSuccess) return hip_fail(e, "select_total (sequential)");
   *total = acc;
   return OLAP_OK;
+}
+
+static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim, int nlev, const int *axis, const uint32_t *n_sel,
+                             const int32_t *const *sel, double *total) {
+  OnStoreDevice on_device__(s);
+  auto launch = [&](const NestPlan &p, uint64_t first, uint64_t k, double *out) {
+    SEL_DISPATCH(s->dtype, T,
+                 hipLaunchKernelGGL((select_gather_kernel<StoreSource<T>>), select_grid(k), kBlock, 0, nullptr, store_source<T>(s), p, first, k, out));
+  };
+  return sequential_of(lens, ndim, nlev, axis, n_sel, sel, launch, total);
 }
 
 extern "C" int olap_store_select_total(const olap_store *s, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
@@ -597,25 +649,24 @@ extern "C" int olap_store_select_total(const olap_store *s, int ndim, const uint
   return select_sequential(s, lens, ndim, nlev, axis, n_sel, sel, total);
 }
 
-// copy over ONE pair of stores on one device; levels already validated (entries >= 0)
-int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
-                const int32_t *const *sel) {
-  OnStoreDevice on_device__(t);
-  if (t->device != src->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "copy_select: source and target live on different devices");
-  // every level without repeats (first occurrence kept), free levels dropped: each combination is a distinct cell
-  // and its rank among the distinct combinations is its place among the keys the copy creates
+// The levels of a copy: every level without repeats (first occurrence kept), free levels dropped, so that each
+// combination is a distinct cell and its rank among the distinct combinations is its place among the keys the copy
+// creates.  *n = 0: no combination.
+static void copy_plan(int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel, const int32_t *const *sel, NestPlan &p,
+                      std::vector<int32_t> &all, uint64_t *n) {
   std::vector<uint64_t> stride(ndim);
   uint64_t st = 1;
   for (int d = ndim - 1; d >= 0; --d) {
     stride[d] = st;
     st *= lens[d];
   }
-  static thread_local NestPlan p;
   memset(&p, 0, offsetof(NestPlan, inl));
-  std::vector<int32_t> all;
-  uint64_t n = 1;
+  *n = 1;
   for (int l = 0; l < nlev; ++l) {
-    if (!n_sel[l]) return OLAP_OK;  // no combination: nothing is written
+    if (!n_sel[l]) {  // no combination: nothing is written
+      *n = 0;
+      return;
+    }
     if (axis[l] < 0) continue;
     const uint32_t at = (uint32_t)all.size();
     std::vector<char> seen(lens[axis[l]], 0);
@@ -625,8 +676,13 @@ int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *
     p.len[k] = (uint32_t)all.size() - at;
     p.off[k] = at;
     p.stride[k] = stride[axis[l]];
-    n *= p.len[k];
+    *n *= p.len[k];
   }
+}
+
+// Writes the copy into `t` on the current device: `launch(p, n, seq, seq_base)` starts copy_select_kernel.
+template <typename Launch>
+static int copy_into(olap_store *t, NestPlan &p, const std::vector<int32_t> &all, uint64_t n, Launch launch) {
   int rc = require_device();
   if (rc) return rc;
   uint32_t *seq = nullptr;
@@ -634,10 +690,7 @@ int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *
   if ((rc = order_before_select_write(t, n, &seq, &seq_base))) return rc;
   int32_t *dev_lists = nullptr;
   if ((rc = place_lists(p, kSelInline / 2, all, &dev_lists))) return rc;
-  const int sn = src->default_kind == OLAP_DEFAULT_NAN, tn = t->default_kind == OLAP_DEFAULT_NAN;
-  SEL_DISPATCH(src->dtype, S, SEL_DISPATCH(t->dtype, T, hipLaunchKernelGGL((copy_select_kernel<S, T>), grid_for(n), kBlock, 0, nullptr,
-                                                                          (const S *)src->values, mask_needed(src), sn, (T *)t->values, t->status,
-                                                                          seq, seq_base, tn, p, n)));
+  launch(p, n, seq, seq_base);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (dev_lists) dev_free(dev_lists);
@@ -646,12 +699,150 @@ int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *
   return OLAP_OK;
 }
 
+// copy over ONE pair of stores on one device; levels already validated (entries >= 0)
+int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                const int32_t *const *sel) {
+  OnStoreDevice on_device__(t);
+  if (t->device != src->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "copy_select: source and target live on different devices");
+  static thread_local NestPlan p;
+  std::vector<int32_t> all;
+  uint64_t n;
+  copy_plan(ndim, lens, nlev, axis, n_sel, sel, p, all, &n);
+  if (n == 0) return OLAP_OK;
+  const int tn = t->default_kind == OLAP_DEFAULT_NAN;
+  return copy_into(t, p, all, n, [&](const NestPlan &q, uint64_t k, uint32_t *seq, uint32_t seq_base) {
+    SEL_DISPATCH(src->dtype, S, SEL_DISPATCH(t->dtype, T, hipLaunchKernelGGL((copy_select_kernel<StoreSource<S>, T>), select_grid(k), kBlock, 0, nullptr,
+                                                                            store_source<S>(src), (T *)t->values, t->status, seq, seq_base, tn, q, k)));
+  });
+}
+
 extern "C" int olap_store_copy_select(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
                                       const uint32_t *n_sel, const int32_t *const *sel) {
   int rc = select_validate(target, ndim, lens, nlev, axis, n_sel, sel, true);
   if (rc) return rc;
   if ((rc = select_validate(source, ndim, lens, nlev, axis, n_sel, sel, true))) return rc;
   return select_copy(target, source, ndim, lens, nlev, axis, n_sel, sel);
+}
+
+// ---- computed measures: the same reduction, gather and scatter with a formula as the value source ----------------
+
+// the host checks of olap_formula_select_total / olap_store_copy_select_formula, before any device work
+static int formula_select_validate(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                                   const olap_store *const *inputs, int ndim, const uint32_t *lens, int nlev, const int *axis, const uint32_t *n_sel,
+                                   const int32_t *const *sel, bool for_copy) {
+  if (n_inputs < 1 || n_inputs > OLAP_FORMULA_MAX_INPUTS)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula over a selection needs 1..%d stored measures, got %d", OLAP_FORMULA_MAX_INPUTS, n_inputs);
+  if (code && n_code > 0 && n_code <= OLAP_FORMULA_MAX_CODE)
+    for (int pc = 0; pc < n_code; ++pc) {
+      if (code[pc] == F_SCALAR) return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula over a selection cannot read a measure total (SCALAR)");
+      if (code[pc] == F_CONST || code[pc] == F_INPUT) ++pc;
+    }
+  int rc = check_formula(code, n_code, n_consts, n_inputs, 0);
+  if (rc) return rc;
+  if (n_consts && !consts) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula constants are NULL");
+  if (!inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs are NULL");
+  for (int k = 0; k < n_inputs; ++k) {
+    if (!inputs[k]) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is NULL", k);
+    if ((rc = select_validate(inputs[k], ndim, lens, nlev, axis, n_sel, sel, for_copy))) return rc;
+    if (inputs[k]->device != inputs[0]->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs live on different devices");
+  }
+  return OLAP_OK;
+}
+
+// the program and its inputs in device memory of the current device (*dev is freed by the caller)
+static int upload_formula(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs, const olap_store *const *inputs,
+                          FormulaProgram **dev) {
+  *dev = nullptr;
+  int rc = require_device();
+  if (rc) return rc;
+  static thread_local FormulaProgram h;
+  memset(&h, 0, sizeof h);
+  h.n_code = n_code;
+  memcpy(h.code, code, n_code * sizeof(int32_t));
+  if (n_consts) memcpy(h.consts, consts, n_consts * sizeof(double));
+  h.n_inputs = n_inputs;
+  for (int k = 0; k < n_inputs; ++k) {  // what olap_store_eval_formula hands its kernel
+    h.in_values[k] = inputs[k]->values;
+    h.in_status[k] = mask_needed(inputs[k]);
+    h.in_dtype[k] = inputs[k]->dtype;
+    h.in_def_nan[k] = inputs[k]->default_kind == OLAP_DEFAULT_NAN;
+  }
+  HIP_TRY(dev_alloc((void **)dev, sizeof h));
+  const hipError_t e = hipMemcpy(*dev, &h, sizeof h, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    dev_free(*dev);
+    *dev = nullptr;
+    return hip_fail(e, "formula program");
+  }
+  return OLAP_OK;
+}
+
+extern "C" int olap_formula_select_total(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                                         const olap_store *const *inputs, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                                         const uint32_t *n_sel, const int32_t *const *sel, double *total, int *exact_path) {
+  int rc = formula_select_validate(code, n_code, consts, n_consts, n_inputs, inputs, ndim, lens, nlev, axis, n_sel, sel, false);
+  if (rc) return rc;
+  if (!total) return fail(OLAP_ERR_INVALID_ARGUMENT, "total is NULL");
+  std::vector<uint32_t> nd;
+  std::vector<const int32_t *> sd;
+  double m;
+  bool empty;
+  by_dimension(ndim, nlev, axis, n_sel, sel, nd, sd, &m, &empty);
+  if (exact_path) *exact_path = 1;
+  if (empty) {  // no combination: the reduce starts and ends at 0 (src/cube.js:704)
+    *total = 0.0;
+    return OLAP_OK;
+  }
+  OnStoreDevice on_device__(inputs[0]);
+  FormulaProgram *prog = nullptr;
+  if ((rc = upload_formula(code, n_code, consts, n_consts, n_inputs, inputs, &prog))) return rc;
+  const FormulaSource src{prog};
+  double sum, abs_sum;
+  int min_exp;
+  unsigned flags;
+  rc = cert_of(
+      ndim, lens, nd.data(), sd.data(),
+      [&](const GatherPlan &p, unsigned blocks, Cert *partial) {
+        hipLaunchKernelGGL((select_total_kernel<FormulaSource, double, false>), blocks, kBlock, 0, nullptr, src, p, partial);
+      },
+      &sum, &abs_sum, &min_exp, &flags);
+  if (!rc && !select_certified_total(sum, abs_sum, min_exp, flags, m, total)) {
+    if (exact_path) *exact_path = 0;
+    rc = sequential_of(
+        lens, ndim, nlev, axis, n_sel, sel,
+        [&](const NestPlan &p, uint64_t first, uint64_t k, double *out) {
+          hipLaunchKernelGGL((select_gather_kernel<FormulaSource>), select_grid(k), kBlock, 0, nullptr, src, p, first, k, out);
+        },
+        total);
+  }
+  dev_free(prog);
+  return rc;
+}
+
+extern "C" int olap_store_copy_select_formula(olap_store *target, const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                                              const olap_store *const *inputs, int ndim, const uint32_t *lens, int nlev, const int *axis,
+                                              const uint32_t *n_sel, const int32_t *const *sel) {
+  int rc = select_validate(target, ndim, lens, nlev, axis, n_sel, sel, true);
+  if (rc) return rc;
+  if ((rc = formula_select_validate(code, n_code, consts, n_consts, n_inputs, inputs, ndim, lens, nlev, axis, n_sel, sel, true))) return rc;
+  if (target->device != inputs[0]->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "copy_select: the formula's inputs and the target live on different devices");
+  OnStoreDevice on_device__(target);
+  static thread_local NestPlan p;
+  std::vector<int32_t> all;
+  uint64_t n;
+  copy_plan(ndim, lens, nlev, axis, n_sel, sel, p, all, &n);
+  if (n == 0) return OLAP_OK;
+  FormulaProgram *prog = nullptr;
+  if ((rc = upload_formula(code, n_code, consts, n_consts, n_inputs, inputs, &prog))) return rc;
+  const FormulaSource src{prog};
+  const int tn = target->default_kind == OLAP_DEFAULT_NAN;
+  rc = copy_into(target, p, all, n, [&](const NestPlan &q, uint64_t k, uint32_t *seq, uint32_t seq_base) {
+    SEL_DISPATCH(target->dtype, T,
+                 hipLaunchKernelGGL((copy_select_kernel<FormulaSource, T>), select_grid(k), kBlock, 0, nullptr, src, (T *)target->values,
+                                    target->status, seq, seq_base, tn, q, k));
+  });
+  dev_free(prog);
+  return rc;
 }
 
 // ---- set_values ------------------------------------------------------------------------------------------------
@@ -708,7 +899,7 @@ static int set_values_batch(olap_store *s, uint64_t n, const uint64_t *indexes, 
   if (e == hipSuccess) e = dev_alloc(&tmp, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16));
   if (e == hipSuccess) e = hipMemcpy(entries, host.data(), host.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(iota_u32_kernel, grid_for(n), kBlock, 0, nullptr, pos_in, n);
+    hipLaunchKernelGGL(iota_u32_kernel, select_grid(n), kBlock, 0, nullptr, pos_in, n);
     e = hipGetLastError();
   }
   if (e == hipSuccess)
@@ -716,14 +907,14 @@ static int set_values_batch(olap_store *s, uint64_t n, const uint64_t *indexes, 
                                            (unsigned int)n, 0, cell_bits, (hipStream_t) nullptr);
   const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
   if (e == hipSuccess) {
-    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_mark_kernel<T>), grid_for(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_mark_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
                                                  (const uint32_t *)pos_sorted, dv, dn, def_nan, n, marker));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(tmp, scan_bytes, (const uint32_t *)marker, run, hipcub::Max(), (unsigned int)n,
                                                              (hipStream_t) nullptr);
   if (e == hipSuccess) {
-    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_write_kernel<T>), grid_for(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_write_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
                                                  (const uint32_t *)pos_sorted, dv, dn, (const uint32_t *)run, n, (T *)s->values, s->status, seq,
                                                  seq_base, def_nan));
     e = hipGetLastError();

@@ -41,6 +41,25 @@ def _levels(lens, levels):
     return lv, ax, n, keep, arr
 
 
+def _formula(code, consts, inputs):
+    """(code, n_code, consts, n_consts, n_inputs, input table, keepalive) of a formula over stores"""
+    c = np.ascontiguousarray(code, dtype=np.int32).reshape(-1)
+    k = np.ascontiguousarray(consts if len(consts) else [0.0], dtype=np.float64).reshape(-1)
+    table = (C.c_void_p * max(len(inputs), 1))(*[s._h.value if s is not None else None for s in inputs])
+    return (c.ctypes.data_as(capi._pi32), len(c), k.ctypes.data_as(capi._pdbl), len(consts), len(inputs), table, (c, k))
+
+
+def select_total_formula(code, consts, inputs, lens, levels):
+    """getTotalForDimensionItems of a computed measure (olap_formula_select_total): the program evaluated over the stores
+    `inputs` at every combination of the levels (see HipStore.select_total).  Returns (total, "device" | "sequential")."""
+    prog = _formula(code, consts, inputs)
+    lv, ax, n, keep, arr = _levels(lens, levels)
+    total, path = C.c_double(), C.c_int()
+    check(capi.lib().olap_formula_select_total(*prog[:-1], len(lv), lv.ctypes.data_as(capi._pu32), len(levels), ax, n.ctypes.data_as(capi._pu32),
+                                                arr, C.byref(total), C.byref(path)))
+    return total.value, ("device" if path.value else "sequential")
+
+
 def _entries(indexes, values):
     """(n, indexes, values, is_null or None) pointers of a set_values list (each keeps its array alive); None in `values`
     means unset"""
@@ -473,6 +492,15 @@ class HipStore:
         lv, ax, n, keep, arr = _levels(lens, levels)
         check(self._lib.olap_store_copy_select(self._h, source._h, len(lv), lv.ctypes.data_as(capi._pu32), len(levels), ax,
                                                n.ctypes.data_as(capi._pu32), arr))
+        return self
+
+    def copy_select_formula(self, code, consts, inputs, lens, levels):
+        """copyMeasureData from a computed measure (olap_store_copy_select_formula): self.set_value(pos, formula(pos))
+        over the selection; `code` / `consts` as olap_eval_formula takes them, `inputs` the stores it reads."""
+        prog = _formula(code, consts, inputs)
+        lv, ax, n, keep, arr = _levels(lens, levels)
+        check(self._lib.olap_store_copy_select_formula(self._h, *prog[:-1], len(lv), lv.ctypes.data_as(capi._pu32), len(levels), ax,
+                                                       n.ctypes.data_as(capi._pu32), arr))
         return self
 
     def load(self, other, my_len, his_len, his_to_mine):

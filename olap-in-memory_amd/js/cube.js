@@ -21,7 +21,7 @@ const CatchAllDimension = require('./dimension/catch-all');
 const TimeSlot = require('./calendar');
 const { toNestedArray, fromNestedArray, toNestedObject, fromNestedObject } = require('./formatter');
 const { toBuffer, fromBuffer, toArrayBuffer } = require('./wire');
-const { getParser } = require('./formula');
+const { getParser, isDeviceExact } = require('./formula');
 const backend = require('./backend');
 const { selectionLevels, copyLevels } = require('./selection');
 
@@ -453,9 +453,12 @@ class Cube {
    */
   getTotalForDimensionItems(measureId, dimensionsFilter = {}) {
     const store = this.storedMeasures[measureId];
-    if (store !== undefined) {
+    const formula = store === undefined ? this._deviceFormula(measureId) : null;
+    if (store !== undefined || formula !== null) {
       const levels = selectionLevels(this.dimensions, dimensionsFilter);
-      if (levels.valid) return store.selectTotal(Uint32Array.from(this.dimensions, (d) => d.numItems), levels);
+      const lengths = Uint32Array.from(this.dimensions, (d) => d.numItems);
+      if (levels.valid && store !== undefined) return store.selectTotal(lengths, levels);
+      if (levels.valid) return HipStore.selectTotalFormula(formula.program, formula.stores, lengths, levels);
     }
     return this._getTotalForDimensionItemsPerCell(measureId, dimensionsFilter);
   }
@@ -478,12 +481,19 @@ class Cube {
   copyMeasureData(sourceMeasureId, targetMeasureId, dimensionsFilter = {}) {
     const source = this.storedMeasures[sourceMeasureId];
     const target = this.storedMeasures[targetMeasureId];
-    if (source !== undefined && target !== undefined) {
+    const formula = source === undefined && target !== undefined ? this._deviceFormula(sourceMeasureId) : null;
+    if ((source !== undefined || formula !== null) && target !== undefined) {
       const levels = selectionLevels(this.dimensions, dimensionsFilter);
       if (levels.valid) {
         const copy = copyLevels(levels);
         if (copy.count === 0) return;
-        if (target.copySelect(source, Uint32Array.from(this.dimensions, (d) => d.numItems), copy)) return;
+        const lengths = Uint32Array.from(this.dimensions, (d) => d.numItems);
+        if (source !== undefined) {
+          if (target.copySelect(source, lengths, copy)) return;
+        } else if (copy.count === levels.count || !formula.stores.includes(target)) {
+          // (a selection that revisits cells reads a target input after it was written: cell by cell)
+          if (target.copySelectFormula(formula.program, formula.stores, lengths, copy)) return;
+        }
       }
     }
     this._copyMeasureDataPerCell(sourceMeasureId, targetMeasureId, dimensionsFilter);
@@ -491,6 +501,27 @@ class Cube {
 
   _copyMeasureDataPerCell(sourceMeasureId, targetMeasureId, dimensionsFilter = {}) {
     for (const coords of this._combinations(dimensionsFilter)) this.setSingleData(targetMeasureId, coords, this.getSingleData(sourceMeasureId, coords));
+  }
+
+  /**
+   * A computed measure that may run on the device over a selection (DESIGN.md §3 K8): { program, stores } when it is
+   * not also stored, reads 1..8 stored measures and nothing else, and compiles to opcodes that give the same bits on
+   * the device as getSingleData here (formula.js isDeviceExact).  null: the per-cell path, with its messages.
+   */
+  _deviceFormula(measureId) {
+    const expression = this.computedMeasures[measureId];
+    if (expression === undefined || this.storedMeasures[measureId] !== undefined) return null;
+    const inputs = {};
+    const stores = [];
+    for (const name of expression.variables({ withMembers: true })) {
+      const store = this.storedMeasures[name];
+      if (store === undefined) return null; // `<id>__total` and unknown names: getSingleData throws
+      inputs[name] = stores.push(store) - 1;
+    }
+    if (stores.length === 0 || stores.length > 8) return null;
+    const program = expression.compile(inputs);
+    if (!isDeviceExact(program) || program.code.length > 96 || program.consts.length > 24 || program.depth > 16) return null;
+    return { program, stores };
   }
 
   // ------------------------------------------------------------------ the derivation helper

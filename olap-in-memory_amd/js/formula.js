@@ -38,6 +38,22 @@ const OP = {
   ABS: 20, CEIL: 21, FLOOR: 22, ROUND: 23, TRUNC: 24, SQRT: 25, CBRT: 26, EXP: 27, LN: 28, LOG10: 29, LOG2: 30, SIGN: 31,
   SIN: 32, COS: 33, TAN: 34, ASIN: 35, ACOS: 36, ATAN: 37, NOT: 38,
 };
+// Opcodes whose device result is bit-equal to evaluate() here (DESIGN.md §3 K8).  ROUND (js_round is floor(v + 0.5)),
+// POW, ROUNDTO, HYPOT, ATAN2, CBRT and the transcendental ops differ from V8's Math in the last bits; SCALAR reads a
+// measure total, which getSingleData cannot.
+const DEVICE_EXACT_OPS = new Set([OP.CONST, OP.INPUT, OP.ADD, OP.SUB, OP.MUL, OP.DIV, OP.MOD, OP.NEG, OP.NANADD, OP.SELECT, OP.MIN, OP.MAX, OP.ISNAN,
+  OP.ABS, OP.CEIL, OP.FLOOR, OP.TRUNC, OP.SQRT, OP.SIGN, OP.NOT]);
+
+/** True when every opcode of a compiled program ({ code }) is in DEVICE_EXACT_OPS. */
+function isDeviceExact(program) {
+  const code = program.code;
+  for (let i = 0; i < code.length; ++i) {
+    if (!DEVICE_EXACT_OPS.has(code[i])) return false;
+    if (code[i] <= OP.SCALAR) ++i; // operand word
+  }
+  return true;
+}
+
 const UNARY_OP = { abs: OP.ABS, ceil: OP.CEIL, floor: OP.FLOOR, round: OP.ROUND, trunc: OP.TRUNC, sqrt: OP.SQRT, cbrt: OP.CBRT, exp: OP.EXP, ln: OP.LN, log: OP.LN, log10: OP.LOG10, log2: OP.LOG2, sign: OP.SIGN, sin: OP.SIN, cos: OP.COS, tan: OP.TAN, asin: OP.ASIN, acos: OP.ACOS, atan: OP.ATAN, not: OP.NOT };
 
 const truthy = (v) => v !== 0 && !Number.isNaN(v) && v !== false && v !== undefined && v !== null;
@@ -366,4 +382,4 @@ function getParser() {
   return new Parser();
 }
 
-module.exports = { getParser, Parser, Expression, OP };
+module.exports = { getParser, Parser, Expression, OP, DEVICE_EXACT_OPS, isDeviceExact };

@@ -454,6 +454,7 @@ class HipStore {
     const from = source._native;
     if (!target.isSharded) {
       target.copySelect(from.isSharded ? from.gather() : from, lengths, levels.axis, levels.lists);
+      HipStore.lastCopyPath = 'device';
       return true;
     }
     const spread = from.isSharded ? from : backend.load().shardStore(from, lengths);
@@ -463,6 +464,34 @@ class HipStore {
       if (!/^sharded:/.test(e.message)) throw e;
       return false;
     }
+    HipStore.lastCopyPath = 'device';
+    return true;
+  }
+
+  /**
+   * getTotalForDimensionItems of a computed measure: `program` (formula.js compile(), no SCALAR) over the stores
+   * `inputs`, evaluated at every combination of the levels on the device, added as selectTotal adds (same certificate,
+   * same sequential fallback, same lastSelectPath).  Pending inputs are materialised and sharded ones gathered.
+   */
+  static selectTotalFormula(program, inputs, lengths, levels) {
+    const pathOut = new Int32Array(1);
+    const natives = inputs.map((store) => store._whole);
+    const total = backend.load().selectTotalFormula(program.code, program.consts, natives, lengths, levels.axis, levels.lists, pathOut);
+    HipStore.lastSelectPath = pathOut[0] ? 'device' : 'sequential';
+    return total;
+  }
+
+  /**
+   * copyMeasureData from a computed measure: this.setValue(pos, formula(pos)) over a selection of distinct cells
+   * (./selection.js copyLevels) in one launch.  This store may be one of `inputs`.  Returns false for a sharded
+   * target: the caller copies cell by cell.
+   */
+  copySelectFormula(program, inputs, lengths, levels) {
+    if (this._native.isSharded) return false;
+    const target = this._writable; // (before the inputs: a target that is one of them is read where it is written)
+    const natives = inputs.map((store) => store._whole);
+    target.copySelectFormula(program.code, program.consts, natives, lengths, levels.axis, levels.lists);
+    HipStore.lastCopyPath = 'device';
     return true;
   }
 
@@ -516,6 +545,8 @@ class HipStore {
 }
 
 HipStore.lastSelectPath = null;
+// 'device' after a copyMeasureData that ran as one device scatter (copySelect / copySelectFormula); never reset here
+HipStore.lastCopyPath = null;
 
 module.exports = HipStore;
 module.exports.toPlainArray = toPlainArray;

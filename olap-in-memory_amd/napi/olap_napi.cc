@@ -774,6 +774,77 @@ static napi_value EvalFormula(napi_env env, napi_callback_info info) {
   return ta;
 }
 
+// A formula over a selection: code (Int32Array), consts (Float64Array) and stores (Store[], the inputs)
+struct FormulaArgs {
+  size_t n_code = 0, n_consts = 0;
+  void *code = nullptr, *consts = nullptr;
+  std::vector<const olap_store *> stores;
+  // false with an exception pending when a store is not one
+  bool decode(napi_env env, napi_value c, napi_value k, napi_value st, bool *bad) {
+    napi_typedarray_type t;
+    *bad = true;
+    if (napi_get_typedarray_info(env, c, &t, &n_code, &code, nullptr, nullptr) != napi_ok || t != napi_int32_array ||
+        napi_get_typedarray_info(env, k, &t, &n_consts, &consts, nullptr, nullptr) != napi_ok || t != napi_float64_array)
+      return false;
+    bool is_arr = false;
+    napi_is_array(env, st, &is_arr);
+    if (!is_arr) return false;
+    *bad = false;
+    uint32_t n = 0;
+    napi_get_array_length(env, st, &n);
+    stores.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      napi_value e;
+      if (napi_get_element(env, st, i, &e) != napi_ok) return false;
+      stores[i] = unwrap(env, e);
+      if (!stores[i]) return false;
+    }
+    return true;
+  }
+  const double *consts_ptr() const {
+    static const double zero = 0;
+    return consts ? (const double *)consts : &zero;
+  }
+};
+
+// selectTotalFormula(code, consts, stores: Store[], lens, axis, lists, pathOut?: Int32Array) -> number (olap_formula_select_total)
+static napi_value SelectTotalFormula(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const char *usage = "selectTotalFormula(code: Int32Array, consts: Float64Array, stores: Store[], lens: Uint32Array, axis: Int32Array, lists: Int32Array[])";
+  if (argc < 6) return bad_args(env, usage);
+  FormulaArgs f;
+  bool bad;
+  if (!f.decode(env, argv[0], argv[1], argv[2], &bad)) return bad ? bad_args(env, usage) : nullptr;
+  SelectArgs a;
+  if (!a.decode(env, argv[3], argv[4], argv[5])) return bad_args(env, usage);
+  double total = 0;
+  int path = 1;
+  int rc = olap_formula_select_total((const int32_t *)f.code, (int)f.n_code, f.consts_ptr(), (int)f.n_consts, (int)f.stores.size(), f.stores.data(),
+                                     (int)a.lens.size(), a.lens.data(), (int)a.axis.size(), a.axis.data(), a.n_sel.data(), a.ptrs.data(), &total, &path);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 6) set_path(env, argv[6], path);
+  return num(env, total);
+}
+
+// copySelectFormula(code, consts, stores: Store[], lens, axis, lists): this.setValue(pos, formula(pos)) over the selection
+static napi_value StoreCopySelectFormula(napi_env env, napi_callback_info info) {
+  STORE_METHOD_PROLOGUE(6)
+  const char *usage = "copySelectFormula(code: Int32Array, consts: Float64Array, stores: Store[], lens: Uint32Array, axis: Int32Array, lists: Int32Array[])";
+  if (argc < 6) return bad_args(env, usage);
+  FormulaArgs f;
+  bool bad;
+  if (!f.decode(env, argv[0], argv[1], argv[2], &bad)) return bad ? bad_args(env, usage) : nullptr;
+  SelectArgs a;
+  if (!a.decode(env, argv[3], argv[4], argv[5])) return bad_args(env, usage);
+  int rc = olap_store_copy_select_formula(s, (const int32_t *)f.code, (int)f.n_code, f.consts_ptr(), (int)f.n_consts, (int)f.stores.size(),
+                                          f.stores.data(), (int)a.lens.size(), a.lens.data(), (int)a.axis.size(), a.axis.data(), a.n_sel.data(),
+                                          a.ptrs.data());
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
+}
+
 // drillUpMulti(stores: Store[], methods: Int32Array, oldLen, newLen, maps) -> Store[]
 // Every stored measure of a cube with its own rule for the rolled-up dimension (olap_store_drillup_multi): one
 // mixed-rule launch where the roll-up allows it, one launch per rule otherwise.
@@ -1332,6 +1403,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"load", nullptr, StoreLoad, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"selectTotal", nullptr, StoreSelectTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"copySelect", nullptr, StoreCopySelect, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"copySelectFormula", nullptr, StoreCopySelectFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_value ctor;
   if (napi_define_class(env, "Store", NAPI_AUTO_LENGTH, StoreNew, nullptr, sizeof(props) / sizeof(props[0]), props, &ctor) != napi_ok) return nullptr;
@@ -1372,6 +1444,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"shardStore", nullptr, ShardStore, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"evalFormulaSharded", nullptr, EvalFormulaSharded, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"evalFormula", nullptr, EvalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"selectTotalFormula", nullptr, SelectTotalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillUpMulti", nullptr, DrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
