@@ -329,6 +329,22 @@ int olap_store_from_sparse(olap_store **store, uint64_t size, int dtype, int def
  * once; otherwise D + 2 launches instead of 2^D - 1.  *launches / *bytes_read (optional) report what ran. */
 int olap_store_totals(const olap_store *store, int ndim, const uint32_t *lens, const int *methods, double *host_values,
                       int32_t *host_status, int *launches, uint64_t *bytes_read);
+/* getNestedObject(computed measure, withTotals = true): the extended cube of a formula over stored measures in one
+ * call.  Marginal s of a stored measure is the sub-lattice s of its extended cube E (olap_store_totals), and a computed
+ * measure on marginal s is the formula applied cell by cell to its inputs there — so the result is the program
+ * (olap_eval_formula's code and constants, no SCALAR operand) evaluated at every cell e of the extended cube on
+ * (E_0[e], ..., E_{n-1}[e]), E_i being what olap_store_totals(inputs[i], ..., methods + i * ndim) exports: the default
+ * where unset, NaN for an integer cell unset under a NaN default.  Same values as evaluating the formula on each of
+ * the 2^D marginal cubes.  inputs: 1..OLAP_FORMULA_MAX_INPUTS stores of any cell types and defaults, each of the
+ * product of lens cells, on one device, none tracked ("ordered: ..."); methods[i * ndim + d] is input i's own rule for
+ * dimension d.  host_values receives prod(lens[d] + 1) float64.  The E_i never leave the device: when the extended cube
+ * fits in LDS one launch per distinct cell type builds them (a workgroup per input) and one more evaluates the
+ * program; otherwise each input runs olap_store_totals' passes and one launch evaluates.  One copy to the host, one
+ * synchronisation.  *launches / *bytes_read (optional) report what ran (bytes: every pass's reads plus the n_inputs
+ * extended cubes the evaluation reads).  Arguments are checked on the host before any device work.  DESIGN.md §3 K6. */
+int olap_formula_totals(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                        const olap_store *const *inputs, int ndim, const uint32_t *lens, const int *methods,
+                        double *host_values, int *launches, uint64_t *bytes_read);
 
 /* Filtered totals and copies over a cartesian selection given as nlev LEVELS in nesting order, the first outermost
  * (getCombinations, src/cube.js:19-32: the filter's keys in their own order, then the unfiltered dimensions in cube

@@ -25,11 +25,13 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include <vector>
 
 #include "olap_device.hpp"
 #include "olap_internal.hpp"
+#include "olap_kernels.hpp"
 
 using namespace olap;
 
@@ -114,13 +116,12 @@ __device__ __forceinline__ void export_cell(T v, bool set, bool def_nan, double 
 }
 
 // ---- E in LDS: one launch, the cube is read once -------------------------------------------------
+// one workgroup builds one measure's E: `method` / `def_nan` are that measure's (s.method / s.def_nan are not read)
 template <typename T>
-__global__ __launch_bounds__(1024) void totals_lds_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, double *__restrict__ out,
-                                                          int32_t *__restrict__ st_out, const TotalsShape s) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+__device__ __forceinline__ void totals_lds_body(unsigned char *lds_raw, const T *__restrict__ in, const int32_t *__restrict__ st_in, double *__restrict__ out,
+                                                int32_t *__restrict__ st_out, const TotalsShape &s, const int *method, const bool def_nan) {
   T *val = reinterpret_cast<T *>(lds_raw);
   unsigned char *flag = lds_raw + (size_t)((s.ext * sizeof(T) + 15) & ~(uint64_t)15);
-  const bool def_nan = s.def_nan != 0;
   for (uint64_t i = threadIdx.x; i < s.cells; i += blockDim.x) {
     const T x = in[i];
     const bool set = cell_is_set<T>(x, st_in ? st_in[i] : OLAP_STATUS_SET, st_in != nullptr, def_nan);
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(1024) void totals_lds_kernel(const T *__restrict__ 
       const uint64_t base = stage_base(s, d, o);
       T ov;
       int32_t os;
-      stage_cell_any<T>(s.method[d], val, flag, base, s.len[d], s.pitch[d], def_nan, ov, os);
+      stage_cell_any<T>(method[d], val, flag, base, s.len[d], s.pitch[d], def_nan, ov, os);
       const uint64_t at = base + (uint64_t)s.len[d] * s.pitch[d];
       val[at] = ov;
       flag[at] = os ? 1 : 0;
@@ -149,6 +150,46 @@ __global__ __launch_bounds__(1024) void totals_lds_kernel(const T *__restrict__ 
     out[e] = ov;
     if (st_out) st_out[e] = os;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void totals_lds_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, double *__restrict__ out,
+                                                          int32_t *__restrict__ st_out, const TotalsShape s) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  totals_lds_body<T>(lds_raw, in, st_in, out, st_out, s, s.method, s.def_nan != 0);
+}
+
+// The same for several measures of one cell type and one shape (the inputs of a formula, olap_formula_totals): one
+// workgroup per measure, blockIdx.x picks its buffers, default kind and rule list (as Batch<T> does for the roll-ups).
+// The workgroups share nothing.
+constexpr int kTotalsBatch = OLAP_FORMULA_MAX_INPUTS;
+template <typename T>
+struct TotalsBatch {
+  const T *in[kTotalsBatch];
+  const int32_t *st_in[kTotalsBatch];
+  double *out[kTotalsBatch];
+  int def_nan[kTotalsBatch];
+  int method[kTotalsBatch][kTotalsMaxDims];
+};
+
+template <typename T>
+__global__ __launch_bounds__(1024) void totals_lds_batch_kernel(const TotalsBatch<T> b, const TotalsShape s) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const unsigned k = blockIdx.x;
+  totals_lds_body<T>(lds_raw, b.in[k], b.st_in[k], b.out[k], (int32_t *)nullptr, s, b.method[k], b.def_nan[k] != 0);
+}
+
+// The formula over the extended cubes of its inputs (float64, p.in_status all NULL): a lane owns whole cells, two at a
+// time, and writes them with one 16-byte store.
+__global__ __launch_bounds__(kBlock) void formula_totals_eval_kernel(const FormulaProgram p, double *__restrict__ out, uint64_t n) {
+  const uint64_t pairs = n / 2;
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < pairs; j += (uint64_t)gridDim.x * kBlock) {
+    Vec<double, 2> r;
+    r.v[0] = formula_at<OLAP_FORMULA_MAX_STACK>(p, 2 * j);
+    r.v[1] = formula_at<OLAP_FORMULA_MAX_STACK>(p, 2 * j + 1);
+    store_vec<double, 2>(out + 2 * j, r);
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = formula_at<OLAP_FORMULA_MAX_STACK>(p, n - 1);
 }
 
 // ---- E in HBM: scatter, one launch per dimension, export -----------------------------------------
@@ -445,8 +486,11 @@ unsigned stride_grid(uint64_t n) {
   return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
 }
 
+// `defer` (olap_formula_totals): the launches are only queued — the caller synchronises once, after its last launch, and
+// then frees the intermediate buffers collected here
 template <typename T>
-int totals_typed(const olap_store *st, const TotalsShape &s, double *dev_out, int32_t *dev_status, int *launches, uint64_t *bytes_read) {
+int totals_typed(const olap_store *st, const TotalsShape &s, double *dev_out, int32_t *dev_status, int *launches, uint64_t *bytes_read,
+                 std::vector<void *> *defer = nullptr) {
   const T *in = (const T *)st->values;
   const int32_t *st_in = mask_needed(st);
   const uint64_t mask_bytes = st_in ? 4 : 0;
@@ -562,11 +606,12 @@ int totals_typed(const olap_store *st, const TotalsShape &s, double *dev_out, in
       cur_fl = dfl;
     }
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // the intermediate tensors go back to the pool
-    for (int k = 0; k < 2; ++k) {
-      if (buf[k]) dev_free(buf[k]);
-      if (fbuf[k]) dev_free(fbuf[k]);
-    }
+    if (e == hipSuccess && !defer) e = hipStreamSynchronize(nullptr);  // the intermediate tensors go back to the pool
+    for (int k = 0; k < 2; ++k)
+      for (void *q : {(void *)buf[k], (void *)fbuf[k]}) {
+        if (q && defer) defer->push_back(q);
+        else if (q) dev_free(q);
+      }
     if (e != hipSuccess) return hip_fail(e, "totals");
     if (launches) *launches = n_launch;
     if (bytes_read) *bytes_read = bytes;
@@ -594,9 +639,11 @@ int totals_typed(const olap_store *st, const TotalsShape &s, double *dev_out, in
   ++n_launch;
   bytes += s.ext * (sizeof(T) + 4);
   e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // val / flag go back to the pool
-  dev_free(val);
-  dev_free(flag);
+  if (e == hipSuccess && !defer) e = hipStreamSynchronize(nullptr);  // val / flag go back to the pool
+  for (void *q : {(void *)val, (void *)flag}) {
+    if (defer) defer->push_back(q);
+    else dev_free(q);
+  }
   if (e != hipSuccess) return hip_fail(e, "totals");
   if (launches) *launches = n_launch;
   if (bytes_read) *bytes_read = bytes;
@@ -662,5 +709,161 @@ extern "C" int olap_store_totals(const olap_store *st, int ndim, const uint32_t 
   if (dev_status) dev_free(dev_status);
   if (rc) return rc;
   if (e != hipSuccess) return hip_fail(e, "totals");
+  return OLAP_OK;
+}
+
+// ---- getNestedObject(computed measure, withTotals): the formula over its inputs' extended cubes ---------------------
+// Marginal s of a stored measure IS the sub-lattice s of its extended cube, and the reference evaluates a computed
+// measure on marginal s cell by cell from its inputs' getValue there — so the computed measure's extended cube is the
+// program applied cell-wise to E_0 .. E_{n-1}: the same operands, the same interpreter (formula_input widens every
+// cell to float64 before the first opcode), the same bits as evaluating on each of the 2^D marginal cubes.
+namespace {
+
+// every input of one cell type in ONE launch, a workgroup each (E <= kLdsCells)
+template <typename T>
+hipError_t totals_lds_batch(int n_inputs, const olap_store *const *inputs, const int *methods, const TotalsShape &s, double *const *dev_e, int *launches,
+                            uint64_t *bytes) {
+  TotalsBatch<T> b{};
+  unsigned nb = 0;
+  for (int i = 0; i < n_inputs; ++i) {
+    if (inputs[i]->dtype != Cell<T>::dtype) continue;
+    b.in[nb] = (const T *)inputs[i]->values;
+    b.st_in[nb] = mask_needed(inputs[i]);
+    b.out[nb] = dev_e[i];
+    b.def_nan[nb] = inputs[i]->default_kind == OLAP_DEFAULT_NAN;
+    for (int d = 0; d < s.nd; ++d) b.method[nb][d] = methods[(size_t)i * s.nd + d];
+    *bytes += s.cells * (sizeof(T) + (b.st_in[nb] ? 4 : 0));  // each cube, once
+    ++nb;
+  }
+  if (!nb) return hipSuccess;
+  const size_t lds = (size_t)((s.ext * sizeof(T) + 15) & ~(uint64_t)15) + (size_t)s.ext;
+  static PerDeviceFlag raised;  // (per cell type, per device)
+  if (lds > 48 * 1024 && !raised.test_and_set()) {
+    const hipError_t e = hipFuncSetAttribute((const void *)totals_lds_batch_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(kLdsCells * (sizeof(T) + 1) + 16));
+    if (e != hipSuccess) return e;
+  }
+  const unsigned threads = s.ext >= 4096 ? 1024 : 256;
+  hipLaunchKernelGGL((totals_lds_batch_kernel<T>), nb, threads, lds, nullptr, b, s);
+  ++*launches;
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int olap_formula_totals(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs, const olap_store *const *inputs,
+                                   int ndim, const uint32_t *lens, const int *methods, double *host_values, int *launches, uint64_t *bytes_read) {
+  // ---- the host checks, before any HIP call
+  if (n_inputs < 1 || n_inputs > OLAP_FORMULA_MAX_INPUTS)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula with totals needs 1..%d stored measures, got %d", OLAP_FORMULA_MAX_INPUTS, n_inputs);
+  if (code && n_code > 0 && n_code <= OLAP_FORMULA_MAX_CODE)
+    for (int pc = 0; pc < n_code; ++pc) {
+      if (code[pc] == F_SCALAR) return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula with totals cannot read a measure total (SCALAR)");
+      if (code[pc] == F_CONST || code[pc] == F_INPUT) ++pc;
+    }
+  int rc = check_formula(code, n_code, n_consts, n_inputs, 0);
+  if (rc) return rc;
+  if (n_consts && !consts) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula constants are NULL");
+  if (!inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs are NULL");
+  for (int i = 0; i < n_inputs; ++i)
+    if (!inputs[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is NULL", i);
+  if (ndim < 0 || ndim > kTotalsMaxDims) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: at most %d dimensions", kTotalsMaxDims);
+  if (ndim > 0 && (!lens || !methods)) return fail(OLAP_ERR_INVALID_ARGUMENT, "lens/methods is NULL");
+  if (!host_values) return fail(OLAP_ERR_INVALID_ARGUMENT, "values is NULL");
+  for (int i = 0; i < n_inputs; ++i)
+    if (inputs[i]->track_order)  // (as olap_store_totals: every marginal has an insertion order of its own)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: formula input %d tracks its insertion order; run the chain of drillUps instead", i);
+  TotalsShape s{};
+  s.nd = ndim;
+  long double cells = 1, ext = 1;
+  for (int d = 0; d < ndim; ++d) {
+    for (int i = 0; i < n_inputs; ++i) {
+      const int m = methods[(size_t)i * ndim + d];
+      if (m < OLAP_SUM || m > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", m);
+    }
+    s.len[d] = lens[d];
+    cells *= lens[d];
+    ext *= (long double)lens[d] + 1;
+  }
+  if (ext > 4.0e9L) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: the extended cube would hold %.3Lg cells", ext);
+  s.cells = (uint64_t)cells;
+  s.ext = (uint64_t)ext;
+  for (int i = 0; i < n_inputs; ++i) {
+    if (inputs[i]->size != s.cells)
+      return fail(OLAP_ERR_LENGTH_MISMATCH, "formula input %d holds %llu cells but the dimensions describe %llu", i, (unsigned long long)inputs[i]->size,
+                  (unsigned long long)s.cells);
+    if (inputs[i]->device != inputs[0]->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs live on different devices");
+  }
+  uint64_t pitch = 1;
+  for (int d = ndim - 1; d >= 0; --d) {
+    s.pitch[d] = pitch;
+    pitch *= (uint64_t)lens[d] + 1;
+  }
+  if ((rc = require_device())) return rc;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(inputs[0]->device));
+
+  // ---- E_0 .. E_{n-1} and the result, float64, all on the device
+  std::vector<void *> held;  // freed after the one synchronisation (the copy to the host)
+  double *dev_e[OLAP_FORMULA_MAX_INPUTS] = {};
+  double *dev_out = nullptr;
+  hipError_t e = dev_alloc((void **)&dev_out, s.ext * sizeof(double));
+  if (e == hipSuccess) held.push_back(dev_out);
+  for (int i = 0; i < n_inputs && e == hipSuccess; ++i) {
+    e = dev_alloc((void **)&dev_e[i], s.ext * sizeof(double));
+    if (e == hipSuccess) held.push_back(dev_e[i]);
+  }
+  int n_launch = 0;
+  uint64_t bytes = 0;
+  rc = OLAP_OK;
+  if (e == hipSuccess && s.ext <= kLdsCells) {
+    e = totals_lds_batch<int32_t>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
+    if (e == hipSuccess) e = totals_lds_batch<uint32_t>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
+    if (e == hipSuccess) e = totals_lds_batch<float>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
+    if (e == hipSuccess) e = totals_lds_batch<double>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
+  } else if (e == hipSuccess) {
+    for (int i = 0; i < n_inputs && !rc; ++i) {  // each input's own pass plan, queued on the one stream
+      const olap_store *st = inputs[i];
+      TotalsShape si = s;
+      si.def_nan = st->default_kind == OLAP_DEFAULT_NAN;
+      for (int d = 0; d < ndim; ++d) si.method[d] = methods[(size_t)i * ndim + d];
+      int l = 0;
+      uint64_t b = 0;
+      switch (st->dtype) {
+        case OLAP_INT32: rc = totals_typed<int32_t>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
+        case OLAP_UINT32: rc = totals_typed<uint32_t>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
+        case OLAP_FLOAT32: rc = totals_typed<float>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
+        default: rc = totals_typed<double>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
+      }
+      n_launch += l;
+      bytes += b;
+    }
+  }
+  if (e == hipSuccess && !rc) {
+    static thread_local FormulaProgram p;
+    memset(&p, 0, sizeof p);
+    p.n_code = n_code;
+    memcpy(p.code, code, n_code * sizeof(int32_t));
+    if (n_consts) memcpy(p.consts, consts, n_consts * sizeof(double));
+    p.n_inputs = n_inputs;
+    for (int i = 0; i < n_inputs; ++i) {  // E_i holds getValue: the default where unset, no mask to consult
+      p.in_values[i] = dev_e[i];
+      p.in_status[i] = nullptr;
+      p.in_dtype[i] = OLAP_FLOAT64;
+      p.in_def_nan[i] = inputs[i]->default_kind == OLAP_DEFAULT_NAN;
+    }
+    hipLaunchKernelGGL(formula_totals_eval_kernel, stride_grid((s.ext + 1) / 2), kBlock, 0, nullptr, p, dev_out, s.ext);
+    ++n_launch;
+    bytes += (uint64_t)n_inputs * s.ext * sizeof(double);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(host_values, dev_out, s.ext * sizeof(double), hipMemcpyDeviceToHost);  // the one synchronisation
+  } else {
+    (void)hipStreamSynchronize(nullptr);  // whatever was queued has finished before its buffers go back to the pool
+  }
+  for (void *q : held) dev_free(q);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(e, "formula_totals");
+  if (launches) *launches = n_launch;
+  if (bytes_read) *bytes_read = bytes;
   return OLAP_OK;
 }

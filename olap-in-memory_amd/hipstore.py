@@ -60,6 +60,24 @@ def select_total_formula(code, consts, inputs, lens, levels):
     return total.value, ("device" if path.value else "sequential")
 
 
+def formula_totals(code, consts, inputs, lens, methods):
+    """getNestedObject(computed measure, withTotals) (olap_formula_totals): the program over the extended cubes of the
+    stores `inputs`; `methods[i]` lists input i's rule per dimension.  Returns (float64 values of the extended cube,
+    launches, bytes read)."""
+    prog = _formula(code, consts, inputs)
+    lv = _u32(lens)
+    flat = [_method_code(m) for per_input in methods for m in per_input]
+    if len(flat) != len(inputs) * len(lv):
+        raise ValueError("formula_totals: one rule per input and dimension")
+    m = (C.c_int * max(len(flat), 1))(*flat)
+    n = int(np.prod([int(l) + 1 for l in lv])) if len(lv) else 1
+    vals = np.zeros(n, np.float64)
+    launches, nbytes = C.c_int(), C.c_uint64()
+    check(capi.lib().olap_formula_totals(*prog[:-1], len(lv), lv.ctypes.data_as(capi._pu32), m, vals.ctypes.data_as(capi._pdbl), C.byref(launches),
+                                          C.byref(nbytes)))
+    return vals, launches.value, nbytes.value
+
+
 def _entries(indexes, values):
     """(n, indexes, values, is_null or None) pointers of a set_values list (each keeps its array alive); None in `values`
     means unset"""

@@ -327,28 +327,81 @@ class Cube {
     // when the extended cube fits in LDS, D + 2 launches otherwise) — same chain order, same rounding.
     // (a measure that tracks its insertion order takes the chain too: every marginal has an order of its own)
     const direct = (id) => this.storedMeasures[id] !== undefined && !this.storedMeasures[id].orderTracked;
-    const stored = measureIds.filter(direct);
-    const others = measureIds.filter((id) => !direct(id));
     const extended = this.dimensions.map((d) => ({ getItems: () => d.getItems().concat(['all']) }));
-    let result = {};
-    for (const id of stored) {
-      const rules = this.storedMeasuresRules[id] || {};
-      result[id] = toNestedObject(this.storedMeasures[id].totals(this.dimensions, this.dimensions.map((d) => rules[d.id])), extended);
-    }
-    if (others.length) {
-      // computed measures are evaluated on each marginal cube (their `__total` parameters are that cube's
-      // totals).  The chain of subset s is the chain of (s without its highest dimension) plus one
-      // drillUp, so marginals are memoised: same order of operations, same values.
-      const marginals = [this];
-      for (let subset = 0; subset < 2 ** this.dimensions.length; ++subset) {
-        if (subset > 0) {
-          const top = 31 - Math.clz32(subset);
-          marginals[subset] = marginals[subset & ~(1 << top)].drillUp(this.dimensions[top].id, 'all');
-        }
-        result = deepMerge(result, plain(marginals[subset], others));
+    const found = {};
+    const others = [];
+    for (const id of measureIds) {
+      if (direct(id)) {
+        const rules = this.storedMeasuresRules[id] || {};
+        found[id] = toNestedObject(this.storedMeasures[id].totals(this.dimensions, this.dimensions.map((d) => rules[d.id])), extended);
+        continue;
       }
+      // A computed measure over stored measures: marginal s of input X is the sub-lattice s of X's extended cube, and
+      // the measure on marginal s is the formula applied cell by cell to its inputs there — so its extended cube is the
+      // formula over the inputs' extended cubes, built and evaluated on the device in one call (olap_formula_totals).
+      const formula = this._totalsFormula(id);
+      if (formula === null) {
+        others.push(id);
+        continue;
+      }
+      const rulesPerInput = formula.ids.map((input) => {
+        const rules = this.storedMeasuresRules[input] || {};
+        return this.dimensions.map((d) => rules[d.id]);
+      });
+      found[id] = toNestedObject(HipStore.totalsFormula(formula.program, formula.stores, this.dimensions, rulesPerInput), extended);
+    }
+    // tracked stored measures, formulas that read `<id>__total`, constants only or more than 8 measures: the chain
+    const chained = others.length ? this._getNestedObjectsChain(others) : {};
+    const result = {};
+    for (const id of measureIds) result[id] = found[id] !== undefined ? found[id] : chained[id];
+    return result;
+  }
+
+  /**
+   * src/cube.js:442-465 lightly memoised: the measures are read on each of the 2^D marginal cubes (a computed measure's
+   * `__total` parameters are that cube's totals) and the objects merged.  The chain of subset s is the chain of (s
+   * without its highest dimension) plus one drillUp, so marginals are memoised: same order of operations, same values.
+   */
+  _getNestedObjectsChain(measureIds) {
+    const plain = (cube, ids) => {
+      const out = {};
+      for (const id of ids) out[id] = toNestedObject(cube.getData(id), cube.dimensions);
+      return out;
+    };
+    let result = {};
+    const marginals = [this];
+    for (let subset = 0; subset < 2 ** this.dimensions.length; ++subset) {
+      if (subset > 0) {
+        const top = 31 - Math.clz32(subset);
+        marginals[subset] = marginals[subset & ~(1 << top)].drillUp(this.dimensions[top].id, 'all');
+      }
+      result = deepMerge(result, plain(marginals[subset], measureIds));
     }
     return result;
+  }
+
+  /**
+   * A computed measure whose totals run on the device (DESIGN.md §3 K6): { program, stores, ids } when it is not also
+   * stored, reads 1..8 stored measures of this cube and nothing else (no `<id>__total`), none of them tracking its
+   * insertion order, and its program fits the device interpreter.  No isDeviceExact filter: the chain evaluates on the
+   * device too, with the same interpreter.  null: the chain.
+   */
+  _totalsFormula(measureId) {
+    const expression = this.computedMeasures[measureId];
+    if (expression === undefined || this.storedMeasures[measureId] !== undefined) return null;
+    const inputs = {};
+    const stores = [];
+    const ids = [];
+    for (const name of expression.variables({ withMembers: true })) {
+      const store = this.storedMeasures[name];
+      if (store === undefined || store.orderTracked) return null;
+      inputs[name] = stores.push(store) - 1;
+      ids.push(name);
+    }
+    if (stores.length === 0 || stores.length > 8) return null;
+    const program = expression.compile(inputs);
+    if (program.code.length > 96 || program.consts.length > 24 || program.depth > 16) return null;
+    return { program, stores, ids };
   }
 
   setNestedObject(measureId, value) {

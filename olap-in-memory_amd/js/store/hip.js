@@ -482,6 +482,25 @@ class HipStore {
   }
 
   /**
+   * getNestedObject(computed measure, withTotals): `program` (formula.js compile(), no SCALAR) over the extended cubes
+   * of the stores `inputs`, each built with its own rules (`rulesPerInput[i][d]`, names; an unknown one throws
+   * 'Unsupported aggregation method: <m>' as the chain of drillUps does).  Returns the Float64Array of the formula's
+   * extended cube.  Pending inputs are materialised and sharded ones gathered, as totals() does.
+   */
+  static totalsFormula(program, inputs, dimensions, rulesPerInput) {
+    const addon = backend.load();
+    const nd = dimensions.length;
+    const codes = new Int32Array(inputs.length * nd);
+    for (let i = 0; i < inputs.length; ++i) for (let d = 0; d < nd; ++d) codes[i * nd + d] = addon.methodFromName(rulesPerInput[i][d]);
+    const launchesOut = new Int32Array(1);
+    const natives = inputs.map((store) => store._whole);
+    const values = addon.totalsFormula(program.code, program.consts, natives, lengthsOf(dimensions), codes, launchesOut);
+    HipStore.lastTotalsPath = 'device';
+    HipStore.lastTotalsLaunches = launchesOut[0];
+    return values;
+  }
+
+  /**
    * copyMeasureData from a computed measure: this.setValue(pos, formula(pos)) over a selection of distinct cells
    * (./selection.js copyLevels) in one launch.  This store may be one of `inputs`.  Returns false for a sharded
    * target: the caller copies cell by cell.
@@ -545,6 +564,10 @@ class HipStore {
 }
 
 HipStore.lastSelectPath = null;
+// 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the
+// launches it reported; never reset here
+HipStore.lastTotalsPath = null;
+HipStore.lastTotalsLaunches = null;
 // 'device' after a copyMeasureData that ran as one device scatter (copySelect / copySelectFormula); never reset here
 HipStore.lastCopyPath = null;
 

@@ -828,6 +828,38 @@ static napi_value SelectTotalFormula(napi_env env, napi_callback_info info) {
   return num(env, total);
 }
 
+// totalsFormula(code, consts, stores: Store[], lens: Uint32Array, methods: Int32Array /* stores.length * lens.length */,
+//               launchesOut?: Int32Array) -> Float64Array of the formula's extended cube (olap_formula_totals)
+static napi_value TotalsFormula(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const char *usage = "totalsFormula(code: Int32Array, consts: Float64Array, stores: Store[], lens: Uint32Array, methods: Int32Array)";
+  if (argc < 5) return bad_args(env, usage);
+  FormulaArgs f;
+  bool bad;
+  if (!f.decode(env, argv[0], argv[1], argv[2], &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<uint32_t> lens, methods;
+  if (!get_u32_vec(env, argv[3], lens) || !get_u32_vec(env, argv[4], methods) || methods.size() != f.stores.size() * lens.size()) return bad_args(env, usage);
+  double n = 1;
+  for (uint32_t l : lens) n *= (double)l + 1;
+  if (n > 4.0e9) {
+    napi_throw_range_error(env, nullptr, "totals: extended cube too large");
+    return nullptr;
+  }
+  void *data;
+  napi_value ta = make_ta(env, napi_float64_array, 8, (size_t)n, &data);
+  if (!ta) return nullptr;
+  static const uint32_t none = 0;
+  int launches = 0;
+  int rc = olap_formula_totals((const int32_t *)f.code, (int)f.n_code, f.consts_ptr(), (int)f.n_consts, (int)f.stores.size(), f.stores.data(),
+                               (int)lens.size(), lens.empty() ? &none : lens.data(), methods.empty() ? (const int *)&none : (const int *)methods.data(),
+                               (double *)data, &launches, nullptr);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 5) set_path(env, argv[5], launches);
+  return ta;
+}
+
 // copySelectFormula(code, consts, stores: Store[], lens, axis, lists): this.setValue(pos, formula(pos)) over the selection
 static napi_value StoreCopySelectFormula(napi_env env, napi_callback_info info) {
   STORE_METHOD_PROLOGUE(6)
@@ -1445,6 +1477,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"evalFormulaSharded", nullptr, EvalFormulaSharded, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"evalFormula", nullptr, EvalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"selectTotalFormula", nullptr, SelectTotalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"totalsFormula", nullptr, TotalsFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillUpMulti", nullptr, DrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
