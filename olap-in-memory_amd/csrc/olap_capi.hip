@@ -1640,7 +1640,32 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
 }
 
 // ---- run ------------------------------------------------------------------------------------
-static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+// every buffer of a launch starts on a 16-byte boundary (a buffer the launch does not have is passed as nullptr)
+static bool all_aligned16(const void *in, const void *in_s, const void *out, const void *out_s) {
+  return (((uintptr_t)in | (uintptr_t)in_s | (uintptr_t)out | (uintptr_t)out_s) & 15u) == 0;
+}
+
+// What a launch over p->axis runs with: buffers off the 16-byte grid take one cell per lane.  The drillDown row
+// kernels read neither `total` nor `xcd_order`, and the mixed-rule launcher declines unaligned buffers before it
+// looks at the lane width, so one preparation serves all four launches.
+static DrillUpAxis axis_for_launch(const olap_plan *p, bool aligned, int *vec) {
+  DrillUpAxis a = p->axis;
+  a.aligned16 = aligned;
+  *vec = aligned ? p->vec : 1;
+  a.n_vec = a.inner / (uint64_t)*vec;
+  a.total = a.outer * a.G * a.n_vec;
+  a.blocks_per_row = (a.n_vec + kBlock - 1) / kBlock;
+  const char *x = getenv("OLAP_XCD_ORDER");  // 0: A/B against the dispatch order
+  a.xcd_order = x ? atoi(x) : 1;
+  return a;
+}
+
+// the lane width a Remap runs with: one cell per lane (r.total counts lanes) when a buffer is off the 16-byte grid
+static int remap_for_launch(Remap &r, int vec, bool aligned) {
+  if (vec == 1 || aligned) return vec;
+  r.total *= (uint64_t)vec;
+  return 1;
+}
 
 // `rule` >= 0: the drillUp rule to run with instead of the one the plan was built for (a drillUp plan's tables do not
 // depend on it; nothing in the plan is written, so a cached plan stays shareable)
@@ -1653,20 +1678,14 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
   const bool hs = in_s != nullptr;
   hipError_t e = hipSuccess;
   if (p->xy_ok && !hs) {  // reorder without a mask to honour: pure permutation of the cells
-    e = launch_transpose_xy(p->xy, (int)sizeof(T), in_v, out_v, out_s, aligned16(in_v) && aligned16(out_v) && (!out_s || aligned16(out_s)), stream);
+    e = launch_transpose_xy(p->xy, (int)sizeof(T), in_v, out_v, out_s, all_aligned16(in_v, nullptr, out_v, out_s), stream);
     if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
     return OLAP_OK;
   }
   switch (p->kind) {
     case PLAN_DRILLUP_AXIS: {
-      DrillUpAxis a = p->axis;
-      int vec = p->vec;
-      a.aligned16 = aligned16(in) && aligned16(out) && (!in_s || aligned16(in_s)) && (!out_s || aligned16(out_s));
-      if (!a.aligned16) vec = 1;
-      a.n_vec = a.inner / (uint64_t)vec;
-      a.total = a.outer * a.G * a.n_vec;
-      a.blocks_per_row = (a.n_vec + kBlock - 1) / kBlock;
-      { const char *x = getenv("OLAP_XCD_ORDER"); a.xcd_order = x ? atoi(x) : 1; }  // 0: A/B against the dispatch order
+      int vec;
+      const DrillUpAxis a = axis_for_launch(p, all_aligned16(in, in_s, out, out_s), &vec);
       if (p->seg.S_tot > 0 && drillup_method != OLAP_PRODUCT && drillup_method != OLAP_PARTIAL_AVERAGE) {
         e = Launch<T>::drillup_segmented(drillup_method, hs, vec, in, in_s, out, out_s, a, p->seg, stream);
         break;
@@ -1682,16 +1701,12 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
       e = Launch<T>::drillup_generic(drillup_method, hs, in, in_s, out, out_s, p->gen, stream);
       break;
     case PLAN_GATHER: {
-      if (p->dice_direct && aligned16(out) && (!out_s || aligned16(out_s))) {
+      if (p->dice_direct && all_aligned16(nullptr, nullptr, out, out_s)) {
         e = Launch<T>::dice_direct(hs, in, in_s, out, out_s, p->dice_rows, stream);
         break;
       }
       Remap r = p->remap;
-      int vec = p->vec;
-      if (vec > 1 && !(aligned16(in) && aligned16(out) && (!in_s || aligned16(in_s)) && (!out_s || aligned16(out_s)))) {
-        r.total *= (uint64_t)vec;
-        vec = 1;
-      }
+      const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
       e = Launch<T>::gather(hs, vec, in, in_s, out, out_s, r, stream);
       break;
     }
@@ -1701,11 +1716,7 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
         break;
       }
       Remap r = p->remap;
-      int vec = p->vec;
-      if (vec > 1 && !(aligned16(in) && aligned16(out) && (!in_s || aligned16(in_s)) && (!out_s || aligned16(out_s)))) {
-        r.total *= (uint64_t)vec;
-        vec = 1;
-      }
+      const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
       e = Launch<T>::load_scatter(hs, vec, in, in_s, out, out_s, r, stream);
       break;
     }
@@ -1714,22 +1725,14 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
       break;
     case PLAN_GATHER_REDUCE: {
       GatherReduce g = p->gr;
-      int vec = p->vec;
-      if (vec > 1 && !(aligned16(in) && aligned16(out) && (!in_s || aligned16(in_s)) && (!out_s || aligned16(out_s)))) {
-        g.r.total *= (uint64_t)vec;
-        vec = 1;
-      }
+      const int vec = remap_for_launch(g.r, p->vec, all_aligned16(in, in_s, out, out_s));
       e = Launch<T>::gather_reduce(p->method, hs, vec, in, in_s, out, out_s, g, stream);
       break;
     }
     case PLAN_DRILLDOWN: {
       if (p->dd_rows) {
-        DrillUpAxis a = p->axis;
-        int vec = p->vec;
-        a.aligned16 = aligned16(in) && aligned16(out) && (!in_s || aligned16(in_s)) && (!out_s || aligned16(out_s));
-        if (!a.aligned16) vec = 1;
-        a.n_vec = a.inner / (uint64_t)vec;
-        a.blocks_per_row = (a.n_vec + kBlock - 1) / kBlock;
+        int vec;
+        const DrillUpAxis a = axis_for_launch(p, all_aligned16(in, in_s, out, out_s), &vec);
         const bool divide = p->method == OLAP_SUM;
         const bool spread = divide && p->dd.use_rounding;
         // rows off the 128-byte grid: store line-aligned windows from LDS (drilldown_rows_lines_kernel)
@@ -1746,11 +1749,7 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
         e = Launch<T>::drilldown_scale(hs, in, in_s, q, p->dds, stream);
         if (e != hipSuccess) break;
         Remap r = p->remap;
-        int vec = p->vec;
-        if (vec > 1 && !(aligned16(out) && (!out_s || aligned16(out_s)))) {
-          r.total *= (uint64_t)vec;
-          vec = 1;
-        }
+        const int vec = remap_for_launch(r, p->vec, all_aligned16(nullptr, nullptr, out, out_s));
         e = Launch<T>::gather(false, vec, q, nullptr, out, out_s, r, stream);
         break;
       }
@@ -1764,26 +1763,29 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
   return OLAP_OK;
 }
 
+// The check and the bookkeeping the run entry points share.  false, with *cur the current device, when the plan's
+// tables live on another one.  (last_stream / ran of a cached plan are written without the cache's lock.)
+static bool begin_run(olap_plan *p, hipStream_t s, int *cur) {
+  *cur = -1;
+  if (hipGetDevice(cur) == hipSuccess && *cur != p->device) return false;
+  p->last_stream = s;
+  p->ran = true;
+  return true;
+}
+static int foreign_device(const olap_plan *p, int cur) {
+  return fail(OLAP_ERR_INVALID_ARGUMENT, "plan was built on device %d but the current device is %d", p->device, cur);
+}
+
 static int plan_run_rule(olap_plan *p, const void *in_values, const int32_t *in_status, void *out_values, int32_t *out_status, void *stream,
                          int rule) {
   if (!p) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan is NULL");
   if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
   if ((p->in_cells && !in_values) || (p->out_cells && !out_values))
     return fail(OLAP_ERR_INVALID_ARGUMENT, "values pointers must not be NULL");
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != p->device)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "plan was built on device %d but the current device is %d", p->device, cur);
-  }
   hipStream_t s = (hipStream_t)stream;
-  p->last_stream = s;
-  p->ran = true;
-  switch (p->dtype) {
-    case OLAP_INT32: return run_typed<int32_t>(p, in_values, in_status, out_values, out_status, s, rule);
-    case OLAP_UINT32: return run_typed<uint32_t>(p, in_values, in_status, out_values, out_status, s, rule);
-    case OLAP_FLOAT32: return run_typed<float>(p, in_values, in_status, out_values, out_status, s, rule);
-    default: return run_typed<double>(p, in_values, in_status, out_values, out_status, s, rule);
-  }
+  int cur;
+  if (!begin_run(p, s, &cur)) return foreign_device(p, cur);
+  DISPATCH_DTYPE(p->dtype, T, return run_typed<T>(p, in_values, in_status, out_values, out_status, s, rule));
 }
 
 extern "C" int olap_plan_run(olap_plan *p, const void *in_values, const int32_t *in_status,
@@ -1791,87 +1793,89 @@ extern "C" int olap_plan_run(olap_plan *p, const void *in_values, const int32_t 
   return plan_run_rule(p, in_values, in_status, out_values, out_status, stream, -1);
 }
 
-// One launch for several measures (Batch<T>): drillUp plans of one axis outside the cooperative reduce regime (whose
-// workspace belongs to the plan); everything else runs pair by pair — still one call for the host.
+namespace {
+// The pairs of a batch.
+struct Pairs {
+  int n;
+  const void *const *in_v;
+  const int32_t *const *in_s;  // may be NULL, like out_s
+  void *const *out_v;
+  int32_t *const *out_s;
+  bool masks() const { return in_s && in_s[0]; }
+};
+}  // namespace
+
+// nb pairs from `first` on (with their rules, if any) as the kernels take them; *aligned: every buffer is on the 16-byte grid
 template <typename T>
-static int run_batch_typed(olap_plan *p, int n, const void *const *in_v, const int32_t *const *in_s, void *const *out_v,
-                           int32_t *const *out_s, hipStream_t stream) {
-  const bool hs = in_s && in_s[0];
-  for (int first = 0; first < n; first += kMaxBatch) {
-    const int nb = std::min(n - first, (int)kMaxBatch);
-    Batch<T> b{};
-    bool al = true;
-    for (int i = 0; i < nb; ++i) {
-      b.in[i] = (const T *)in_v[first + i];
-      b.st_in[i] = hs ? in_s[first + i] : nullptr;
-      b.out[i] = (T *)out_v[first + i];
-      b.st_out[i] = out_s ? out_s[first + i] : nullptr;
-      al = al && aligned16(b.in[i]) && aligned16(b.out[i]) && (!b.st_in[i] || aligned16(b.st_in[i])) && (!b.st_out[i] || aligned16(b.st_out[i]));
-    }
-    DrillUpAxis a = p->axis;
-    int vec = p->vec;
-    a.aligned16 = al;
-    if (!al) vec = 1;
-    a.n_vec = a.inner / (uint64_t)vec;
-    a.total = a.outer * a.G * a.n_vec;
-    a.blocks_per_row = (a.n_vec + kBlock - 1) / kBlock;
-    { const char *x = getenv("OLAP_XCD_ORDER"); a.xcd_order = x ? atoi(x) : 1; }
-    hipError_t e = Launch<T>::drillup_axis_batch(p->method, hs, vec, b, (unsigned)nb, a, stream);
-    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+static Batch<T> fill_batch(const Pairs &q, int first, int nb, const int *methods, bool *aligned) {
+  Batch<T> b{};
+  *aligned = true;
+  for (int i = 0; i < nb; ++i) {
+    b.in[i] = (const T *)q.in_v[first + i];
+    b.st_in[i] = q.masks() ? q.in_s[first + i] : nullptr;
+    b.out[i] = (T *)q.out_v[first + i];
+    b.st_out[i] = q.out_s ? q.out_s[first + i] : nullptr;
+    if (methods) b.method[i] = methods[first + i];
+    *aligned = *aligned && all_aligned16(b.in[i], b.st_in[i], b.out[i], b.st_out[i]);
   }
-  return OLAP_OK;
+  return b;
 }
 
-// n pairs whose rules differ (methods[i]), same plan otherwise.  OLAP_OK when they went out as mixed-rule launches;
-// OLAP_ERR_UNSUPPORTED (nothing launched) when this plan / these buffers need rule-by-rule launches.
+// One launch for several measures (Batch<T>): drillUp plans of one axis outside the cooperative reduce regime (whose
+// workspace belongs to the plan); everything else runs pair by pair — still one call for the host.
+// `methods`: the pairs' rules differ (same plan otherwise) and go out as mixed-rule launches; OLAP_MIXED_NOT_APPLICABLE
+// (nothing launched) when this plan / these buffers need rule-by-rule launches.
 constexpr int OLAP_MIXED_NOT_APPLICABLE = -1000;
 template <typename T>
-static int run_mixed_typed(olap_plan *p, int n, const int *methods, const void *const *in_v, const int32_t *const *in_s, void *const *out_v,
-                           int32_t *const *out_s, hipStream_t stream) {
-  const bool hs = in_s && in_s[0];
+static int run_batch_typed(olap_plan *p, const Pairs &q, const int *methods, hipStream_t stream) {
   bool deep = false;
-  for (int i = 0; i < n; ++i) deep = deep || methods[i] == OLAP_PRODUCT;
-  for (int first = 0; first < n; first += kMaxBatch) {
-    const int nb = std::min(n - first, (int)kMaxBatch);
-    Batch<T> b{};
-    bool al = true;
-    for (int i = 0; i < nb; ++i) {
-      b.in[i] = (const T *)in_v[first + i];
-      b.st_in[i] = hs ? in_s[first + i] : nullptr;
-      b.out[i] = (T *)out_v[first + i];
-      b.st_out[i] = out_s ? out_s[first + i] : nullptr;
-      b.method[i] = methods[first + i];
-      al = al && aligned16(b.in[i]) && aligned16(b.out[i]) && (!b.st_in[i] || aligned16(b.st_in[i])) && (!b.st_out[i] || aligned16(b.st_out[i]));
-    }
-    DrillUpAxis a = p->axis;
-    a.aligned16 = al;
-    a.n_vec = a.inner / (uint64_t)p->vec;
-    a.total = a.outer * a.G * a.n_vec;
-    a.blocks_per_row = (a.n_vec + kBlock - 1) / kBlock;
-    { const char *x = getenv("OLAP_XCD_ORDER"); a.xcd_order = x ? atoi(x) : 1; }
-    hipError_t e = Launch<T>::drillup_rows_mixed(hs, p->vec, b, (unsigned)nb, a, deep, stream);
-    if (e == hipErrorNotSupported && first == 0) return OLAP_MIXED_NOT_APPLICABLE;
-    if (e != hipSuccess) return hip_fail(e, "drillup_rows_mixed_kernel");
+  for (int i = 0; methods && i < q.n; ++i) deep = deep || methods[i] == OLAP_PRODUCT;
+  for (int first = 0; first < q.n; first += kMaxBatch) {
+    const int nb = std::min(q.n - first, (int)kMaxBatch);
+    bool aligned;
+    int vec;
+    const Batch<T> b = fill_batch<T>(q, first, nb, methods, &aligned);
+    const DrillUpAxis a = axis_for_launch(p, aligned, &vec);
+    const hipError_t e = methods ? Launch<T>::drillup_rows_mixed(q.masks(), vec, b, (unsigned)nb, a, deep, stream)
+                                 : Launch<T>::drillup_axis_batch(p->method, q.masks(), vec, b, (unsigned)nb, a, stream);
+    if (methods && e == hipErrorNotSupported && first == 0) return OLAP_MIXED_NOT_APPLICABLE;
+    if (e != hipSuccess) return hip_fail(e, methods ? "drillup_rows_mixed_kernel" : p->kernel_name.c_str());
   }
   return OLAP_OK;
 }
 
 // (internal) the pairs of one plan with a rule each; masks on all pairs or on none
-static int plan_run_mixed(olap_plan *p, int n, const int *methods, const void *const *in_values, const int32_t *const *in_status,
-                          void *const *out_values, int32_t *const *out_status, hipStream_t s) {
+static int plan_run_mixed(olap_plan *p, const Pairs &q, const int *methods, hipStream_t s) {
   if (p->kind != PLAN_DRILLUP_AXIS || p->reduce.S != 0 || plan_dry() || getenv("OLAP_NO_MIXED_RULES")) return OLAP_MIXED_NOT_APPLICABLE;
-  for (int i = 0; i < n; ++i)
+  for (int i = 0; i < q.n; ++i)
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return OLAP_MIXED_NOT_APPLICABLE;
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != p->device) return OLAP_MIXED_NOT_APPLICABLE;
-  p->last_stream = s;
-  p->ran = true;
-  switch (p->dtype) {
-    case OLAP_INT32: return run_mixed_typed<int32_t>(p, n, methods, in_values, in_status, out_values, out_status, s);
-    case OLAP_UINT32: return run_mixed_typed<uint32_t>(p, n, methods, in_values, in_status, out_values, out_status, s);
-    case OLAP_FLOAT32: return run_mixed_typed<float>(p, n, methods, in_values, in_status, out_values, out_status, s);
-    default: return run_mixed_typed<double>(p, n, methods, in_values, in_status, out_values, out_status, s);
+  int cur;
+  if (!begin_run(p, s, &cur)) return OLAP_MIXED_NOT_APPLICABLE;
+  DISPATCH_DTYPE(p->dtype, T, return run_batch_typed<T>(p, q, methods, s));
+}
+
+// The per-pair checks of the batch entry points, in the order they report: pair i's rule (if there are rules), then
+// its values pointers.  *mixed_masks: some pairs carry a mask where others carry none (they cannot share a launch).
+static int check_pairs(const olap_plan *p, const Pairs &q, const int *methods, bool *mixed_masks) {
+  bool masks_in = false, masks_out = false;
+  *mixed_masks = false;
+  for (int i = 0; i < q.n; ++i) {
+    if (methods && (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT)) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
+    if ((p->in_cells && !q.in_v[i]) || (p->out_cells && !q.out_v[i]))
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "values pointers must not be NULL (pair %d of the batch)", i);
+    const bool mi = q.in_s && q.in_s[i], mo = q.out_s && q.out_s[i];
+    if (i == 0) masks_in = mi, masks_out = mo;
+    else if (mi != masks_in || mo != masks_out) *mixed_masks = true;
   }
+  return OLAP_OK;
+}
+
+// pair by pair (`methods`: each with its rule; a drillUp plan's tables do not depend on the rule)
+static int run_pair_by_pair(olap_plan *p, const Pairs &q, const int *methods, void *stream) {
+  int rc = OLAP_OK;
+  for (int i = 0; i < q.n && !rc; ++i)
+    rc = plan_run_rule(p, q.in_v[i], q.in_s ? q.in_s[i] : nullptr, q.out_v[i], q.out_s ? q.out_s[i] : nullptr, stream, methods ? methods[i] : -1);
+  return rc;
 }
 
 extern "C" int olap_plan_run_batch_rules(olap_plan *p, int n, const int *methods, const void *const *in_values,
@@ -1880,24 +1884,15 @@ extern "C" int olap_plan_run_batch_rules(olap_plan *p, int n, const int *methods
   if (n < 0 || (n > 0 && (!methods || !in_values || !out_values))) return fail(OLAP_ERR_INVALID_ARGUMENT, "batch of %d: method and values lists must not be NULL", n);
   if (p->kind != PLAN_DRILLUP_AXIS && p->kind != PLAN_DRILLUP_GENERIC) return fail(OLAP_ERR_INVALID_ARGUMENT, "rules per pair need a drillUp plan");
   if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-  bool masks_in = false, masks_out = false, mixed_masks = false;
-  for (int i = 0; i < n; ++i) {
-    if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
-    if ((p->in_cells && !in_values[i]) || (p->out_cells && !out_values[i]))
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "values pointers must not be NULL (pair %d of the batch)", i);
-    const bool mi = in_status && in_status[i], mo = out_status && out_status[i];
-    if (i == 0) masks_in = mi, masks_out = mo;
-    else if (mi != masks_in || mo != masks_out) mixed_masks = true;
-  }
+  const Pairs q{n, in_values, in_status, out_values, out_status};
+  bool mixed_masks;
+  int rc = check_pairs(p, q, methods, &mixed_masks);
+  if (rc) return rc;
   if (n > 1 && !mixed_masks) {
-    const int rc = plan_run_mixed(p, n, methods, in_values, in_status, out_values, out_status, (hipStream_t)stream);
+    rc = plan_run_mixed(p, q, methods, (hipStream_t)stream);
     if (rc != OLAP_MIXED_NOT_APPLICABLE) return rc;
   }
-  // pair by pair: a drillUp plan's tables do not depend on the rule
-  int rc = OLAP_OK;
-  for (int i = 0; i < n && !rc; ++i)
-    rc = plan_run_rule(p, in_values[i], in_status ? in_status[i] : nullptr, out_values[i], out_status ? out_status[i] : nullptr, stream, methods[i]);
-  return rc;
+  return run_pair_by_pair(p, q, methods, stream);
 }
 
 extern "C" int olap_plan_run_batch(olap_plan *p, int n, const void *const *in_values, const int32_t *const *in_status,
@@ -1905,36 +1900,16 @@ extern "C" int olap_plan_run_batch(olap_plan *p, int n, const void *const *in_va
   if (!p) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan is NULL");
   if (n < 0 || (n > 0 && (!in_values || !out_values))) return fail(OLAP_ERR_INVALID_ARGUMENT, "batch of %d: values pointer lists must not be NULL", n);
   if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-  bool masks_in = false, masks_out = false, mixed = false;
-  for (int i = 0; i < n; ++i) {
-    if ((p->in_cells && !in_values[i]) || (p->out_cells && !out_values[i]))
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "values pointers must not be NULL (pair %d of the batch)", i);
-    const bool mi = in_status && in_status[i], mo = out_status && out_status[i];
-    if (i == 0) masks_in = mi, masks_out = mo;
-    else if (mi != masks_in || mo != masks_out) mixed = true;
-  }
-  const bool one_launch = p->kind == PLAN_DRILLUP_AXIS && p->reduce.S == 0 && !mixed && n > 1;
-  if (!one_launch) {
-    for (int i = 0; i < n; ++i) {
-      const int rc = olap_plan_run(p, in_values[i], in_status ? in_status[i] : nullptr, out_values[i], out_status ? out_status[i] : nullptr, stream);
-      if (rc) return rc;
-    }
-    return OLAP_OK;
-  }
-  {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != p->device)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "plan was built on device %d but the current device is %d", p->device, cur);
-  }
+  const Pairs q{n, in_values, in_status, out_values, out_status};
+  bool mixed_masks;
+  const int rc = check_pairs(p, q, nullptr, &mixed_masks);
+  if (rc) return rc;
+  const bool one_launch = p->kind == PLAN_DRILLUP_AXIS && p->reduce.S == 0 && !mixed_masks && n > 1;
+  if (!one_launch) return run_pair_by_pair(p, q, nullptr, stream);
   hipStream_t s = (hipStream_t)stream;
-  p->last_stream = s;
-  p->ran = true;
-  switch (p->dtype) {
-    case OLAP_INT32: return run_batch_typed<int32_t>(p, n, in_values, in_status, out_values, out_status, s);
-    case OLAP_UINT32: return run_batch_typed<uint32_t>(p, n, in_values, in_status, out_values, out_status, s);
-    case OLAP_FLOAT32: return run_batch_typed<float>(p, n, in_values, in_status, out_values, out_status, s);
-    default: return run_batch_typed<double>(p, n, in_values, in_status, out_values, out_status, s);
-  }
+  int cur;
+  if (!begin_run(p, s, &cur)) return foreign_device(p, cur);
+  DISPATCH_DTYPE(p->dtype, T, return run_batch_typed<T>(p, q, nullptr, s));
 }
 
 extern "C" int olap_plan_status(olap_plan *p) {
@@ -1951,14 +1926,6 @@ extern "C" int olap_plan_status(olap_plan *p) {
 }
 
 // ------------------------------------------------------------------ element-wise helpers
-#define DISPATCH_DTYPE(dtype, CALL)                      \
-  switch (dtype) {                                       \
-    case OLAP_INT32: { using T = int32_t; CALL; break; } \
-    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
-    case OLAP_FLOAT32: { using T = float; CALL; break; }  \
-    default: { using T = double; CALL; break; }           \
-  }
-
 extern "C" int olap_canonicalize(void *values, int32_t *status, uint64_t n, int dtype, int default_kind,
                                  int use_existing_status, void *stream) {
   int rc;
@@ -1967,7 +1934,7 @@ extern "C" int olap_canonicalize(void *values, int32_t *status, uint64_t n, int 
   if (use_existing_status && !status) return fail(OLAP_ERR_INVALID_ARGUMENT, "use_existing_status needs a status buffer");
   if ((rc = require_device())) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::canonicalize((T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, use_existing_status, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::canonicalize((T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, use_existing_status, (hipStream_t)stream));
   if (e != hipSuccess) return hip_fail(e, "canonicalize");
   return OLAP_OK;
 }
@@ -1979,7 +1946,7 @@ extern "C" int olap_convert_from_f64(const double *src, void *values, int32_t *s
   if (n && (!values || !src)) return fail(OLAP_ERR_INVALID_ARGUMENT, "src/values is NULL");
   if ((rc = require_device())) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::from_f64(src, (T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::from_f64(src, (T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, (hipStream_t)stream));
   if (e != hipSuccess) return hip_fail(e, "convert_from_f64");
   return OLAP_OK;
 }
@@ -1990,7 +1957,7 @@ extern "C" int olap_convert_to_f64(const void *values, double *dst, uint64_t n, 
   if (n && (!values || !dst)) return fail(OLAP_ERR_INVALID_ARGUMENT, "values/dst is NULL");
   if ((rc = require_device())) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::to_f64((const T *)values, dst, n, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::to_f64((const T *)values, dst, n, (hipStream_t)stream));
   if (e != hipSuccess) return hip_fail(e, "convert_to_f64");
   return OLAP_OK;
 }
@@ -2002,7 +1969,7 @@ extern "C" int olap_fill_seeded(void *values, int32_t *status, uint64_t n, uint6
   if (n && !values) return fail(OLAP_ERR_INVALID_ARGUMENT, "values is NULL");
   if ((rc = require_device())) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::fill_seeded((T *)values, status, n, first_cell, seed, frac, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::fill_seeded((T *)values, status, n, first_cell, seed, frac, (hipStream_t)stream));
   if (e != hipSuccess) return hip_fail(e, "fill_seeded");
   return OLAP_OK;
 }
@@ -2014,7 +1981,7 @@ extern "C" int olap_average_finish(void *values, const int32_t *counts, int32_t 
   if (n && (!values || !counts)) return fail(OLAP_ERR_INVALID_ARGUMENT, "values/counts is NULL");
   if ((rc = require_device())) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::average_finish((T *)values, counts, out_status, n, default_kind == OLAP_DEFAULT_NAN, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::average_finish((T *)values, counts, out_status, n, default_kind == OLAP_DEFAULT_NAN, (hipStream_t)stream));
   if (e != hipSuccess) return hip_fail(e, "average_finish");
   return OLAP_OK;
 }
@@ -2214,7 +2181,7 @@ extern "C" int olap_total(const void *values, const int32_t *status, uint64_t n,
     else (void)hipGetLastError();
   }
   Acc *result = pinned ? pinned : dev;
-  DISPATCH_DTYPE(dtype, e = Launch<T>::total((const T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, dev + 1, &result->total, &result->count, (hipStream_t)stream));
+  DISPATCH_DTYPE(dtype, T, e = Launch<T>::total((const T *)values, status, n, default_kind == OLAP_DEFAULT_NAN, dev + 1, &result->total, &result->count, (hipStream_t)stream));
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
   if (e == hipSuccess) {
     if (pinned) host = *pinned;
@@ -2506,7 +2473,7 @@ extern "C" int olap_store_get_value(const olap_store *s, uint64_t index, double 
   }
   if (pinned) {
     hipError_t e = hipSuccess;
-    DISPATCH_DTYPE(s->dtype, e = Launch<T>::get_cell((const T *)s->values, s->status, index, pinned, nullptr));
+    DISPATCH_DTYPE(s->dtype, T, e = Launch<T>::get_cell((const T *)s->values, s->status, index, pinned, nullptr));
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) return hip_fail(e, "getValue");
     v = pinned->value;
@@ -2516,12 +2483,7 @@ extern "C" int olap_store_get_value(const olap_store *s, uint64_t index, double 
     const size_t es = olap_dtype_size(s->dtype);
     unsigned char raw[8];
     HIP_TRY(hipMemcpy(raw, (const char *)s->values + index * es, es, hipMemcpyDeviceToHost));
-    switch (s->dtype) {
-      case OLAP_INT32: { int32_t x; memcpy(&x, raw, 4); v = x; break; }
-      case OLAP_UINT32: { uint32_t x; memcpy(&x, raw, 4); v = x; break; }
-      case OLAP_FLOAT32: { float x; memcpy(&x, raw, 4); v = x; break; }
-      default: memcpy(&v, raw, 8);
-    }
+    DISPATCH_DTYPE(s->dtype, T, { T x; memcpy(&x, raw, sizeof x); v = x; });
   }
   bool set = (st & OLAP_STATUS_SET) != 0;
   if (!mask_is_primary(s)) {  // set <=> value != default
@@ -2540,7 +2502,7 @@ extern "C" int olap_store_set_value(olap_store *s, uint64_t index, double value,
   int rc = order_before_set_value(s, index);
   if (rc) return rc;
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(s->dtype, e = Launch<T>::set_cell((T *)s->values, s->status, index, value, is_null, s->default_kind == OLAP_DEFAULT_NAN, nullptr));
+  DISPATCH_DTYPE(s->dtype, T, e = Launch<T>::set_cell((T *)s->values, s->status, index, value, is_null, s->default_kind == OLAP_DEFAULT_NAN, nullptr));
   if (e == hipSuccess && (rc = order_after_set_value(s, index))) return rc;
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess) return hip_fail(e, "set_value");
@@ -2631,7 +2593,7 @@ extern "C" int olap_store_to_sparse(const olap_store *s, uint32_t *host_indexes,
   HIP_TRY(dev_alloc((void **)&dev_counts, n_chunks * sizeof(unsigned long long)));
   std::vector<unsigned long long> counts(n_chunks), offsets(n_chunks);
   hipError_t e = hipSuccess;
-  DISPATCH_DTYPE(s->dtype, e = Launch<T>::compact_count((const T *)s->values, mask, s->size, chunk, n_chunks, s->default_kind == OLAP_DEFAULT_NAN, dev_counts, nullptr));
+  DISPATCH_DTYPE(s->dtype, T, e = Launch<T>::compact_count((const T *)s->values, mask, s->size, chunk, n_chunks, s->default_kind == OLAP_DEFAULT_NAN, dev_counts, nullptr));
   if (e == hipSuccess) e = hipMemcpy(counts.data(), dev_counts, n_chunks * sizeof(unsigned long long), hipMemcpyDeviceToHost);
   unsigned long long total = 0;
   for (unsigned b = 0; b < n_chunks; ++b) {
@@ -2651,7 +2613,7 @@ extern "C" int olap_store_to_sparse(const olap_store *s, uint32_t *host_indexes,
     if (e == hipSuccess) e = dev_alloc(&dev_val, total * es);
     if (e == hipSuccess) e = hipMemcpy(dev_counts, offsets.data(), n_chunks * sizeof(unsigned long long), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-      DISPATCH_DTYPE(s->dtype, e = Launch<T>::compact_write((const T *)s->values, mask, s->size, chunk, n_chunks, s->default_kind == OLAP_DEFAULT_NAN, dev_counts, dev_idx, (T *)dev_val, nullptr));
+      DISPATCH_DTYPE(s->dtype, T, e = Launch<T>::compact_write((const T *)s->values, mask, s->size, chunk, n_chunks, s->default_kind == OLAP_DEFAULT_NAN, dev_counts, dev_idx, (T *)dev_val, nullptr));
     }
     if (e == hipSuccess) e = hipMemcpy(host_indexes, dev_idx, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(host_values, dev_val, total * es, hipMemcpyDeviceToHost);
@@ -2701,7 +2663,7 @@ extern "C" int olap_store_from_sparse(olap_store **store, uint64_t size, int dty
     if (e == hipSuccess) e = hipMemcpy(dev_idx, host_indexes, n * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dev_val, host_values, n * es, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-      DISPATCH_DTYPE(dtype, e = Launch<T>::scatter_sparse((T *)s->values, dev_idx, (const T *)dev_val, n, size, nullptr));
+      DISPATCH_DTYPE(dtype, T, e = Launch<T>::scatter_sparse((T *)s->values, dev_idx, (const T *)dev_val, n, size, nullptr));
     }
     if (e == hipSuccess && s->status) {
       // integer cells under a NaN default: the listed cells are exactly the set ones
@@ -2842,6 +2804,112 @@ static int check_store_cells(const olap_store *s, const olap_plan *plan) {
 
 static bool bad_dims(int ndim, const void *a, const void *b) { return ndim < 0 || ndim > OLAP_MAX_DIMS || (ndim > 0 && (!a || !b)); }
 
+// every table a key would read is there (two families of tables over the same lengths; one family: pass it twice)
+template <typename A, typename B>
+static bool tables_readable(int ndim, const uint32_t *lens, const A *const *a, const B *const *b) {
+  if (ndim > 0 && (!a || !b)) return false;
+  for (int d = 0; d < ndim; ++d)
+    if (lens[d] && (!a[d] || !b[d])) return false;
+  return true;
+}
+
+// ---- the keys, one writer per operation.  A key stays empty exactly when an argument it would read is unreadable
+// (ndim out of range, a NULL length vector or table); the operation's plan builder rejects exactly those arguments.
+static PlanKey drillup_key(const olap_store *s, int method, int ndim, const uint32_t *old_len, const uint32_t *new_len,
+                           const uint32_t *const *maps) {
+  PlanKey key;
+  if (bad_dims(ndim, old_len, new_len) || !tables_readable(ndim, old_len, maps, maps)) return key;
+  key.i32('U');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
+  key.u32s(old_len, ndim), key.u32s(new_len, ndim);
+  key.tables(maps, old_len, ndim);
+  return key;
+}
+
+static PlanKey drilldown_key(const olap_store *s, int method, int ndim, const uint32_t *old_len, const uint32_t *new_len,
+                             const uint32_t *const *maps) {
+  PlanKey key;
+  if (bad_dims(ndim, old_len, new_len) || !tables_readable(ndim, new_len, maps, maps)) return key;
+  key.i32('W');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
+  key.u32s(old_len, ndim), key.u32s(new_len, ndim);
+  key.tables(maps, new_len, ndim);
+  return key;
+}
+
+static PlanKey dice_key(const olap_store *s, int ndim, const uint32_t *old_len, const uint32_t *new_len, const int32_t *const *sel) {
+  PlanKey key;
+  if (bad_dims(ndim, old_len, new_len) || !tables_readable(ndim, new_len, sel, sel)) return key;
+  key.i32('D');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim);
+  key.u32s(old_len, ndim), key.u32s(new_len, ndim);
+  key.tables((const uint32_t *const *)sel, new_len, ndim);
+  return key;
+}
+
+static PlanKey dice_drillup_key(const olap_store *s, int method, int ndim, const uint32_t *old_len, const uint32_t *mid_len,
+                                const uint32_t *new_len, const int32_t *const *sel, const uint32_t *const *maps) {
+  PlanKey key;
+  if (bad_dims(ndim, old_len, mid_len) || bad_dims(ndim, mid_len, new_len) || !tables_readable(ndim, mid_len, sel, maps)) return key;
+  key.i32('F');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
+  key.u32s(old_len, ndim), key.u32s(mid_len, ndim), key.u32s(new_len, ndim);
+  key.tables((const uint32_t *const *)sel, mid_len, ndim);
+  key.tables(maps, mid_len, ndim);
+  return key;
+}
+
+static PlanKey reorder_key(const olap_store *s, int ndim, const uint32_t *old_len, const int32_t *perm) {
+  PlanKey key;
+  if (bad_dims(ndim, old_len, perm)) return key;
+  key.i32('R');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim);
+  key.u32s(old_len, ndim), key.u32s((const uint32_t *)perm, ndim);
+  return key;
+}
+
+namespace {
+// The plan of one handle operation: pinned in the cache, or private to the call (an empty key, or `keep` said no).
+// Unpinned or destroyed when the holder goes.
+struct PlanRef {
+  olap_plan *plan = nullptr;
+  bool cached = false;
+  PlanRef() = default;
+  PlanRef(const PlanRef &) = delete;
+  PlanRef &operator=(const PlanRef &) = delete;
+  ~PlanRef() {
+    if (cached) plan_cache().release(plan);
+    else olap_plan_destroy(plan);
+  }
+  // build(&plan) calls the operation's plan builder; its error comes back unchanged.  keep(plan) == false: this plan
+  // is not held on to.
+  template <typename Build>
+  int acquire(const PlanKey &key, Build build, bool (*keep)(const olap_plan *) = nullptr) {
+    if (!key.empty() && (plan = plan_cache().find(key.bytes))) {
+      cached = true;
+      return OLAP_OK;
+    }
+    const int rc = build(&plan);
+    if (rc) return rc;
+    if (!key.empty() && (!keep || keep(plan))) {
+      plan_cache().insert(key.bytes, plan);
+      cached = true;
+    }
+    return OLAP_OK;
+  }
+};
+}  // namespace
+
+// how every operation from one store to a new one runs
+template <typename Build>
+static int run_cached(const olap_store *s, olap_store **out, const PlanKey &key, Build build, bool (*keep)(const olap_plan *) = nullptr) {
+  PlanRef ref;
+  int rc = ref.acquire(key, build, keep);
+  if (!rc) rc = check_store_cells(s, ref.plan);
+  if (!rc) rc = run_to_new_store(ref.plan, s, out);
+  return rc;
+}
+
 extern "C" int olap_store_drillup(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len,
                                   const uint32_t *new_len, const uint32_t *const *maps, int method) {
   OnStoreDevice on_device__(s);
@@ -2853,36 +2921,50 @@ extern "C" int olap_store_drillup(const olap_store *s, olap_store **out, int ndi
 int store_drillup_plain(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len, const uint32_t *new_len,
                         const uint32_t *const *maps, int method) {
   *out = nullptr;
-  olap_plan *plan = nullptr;
-  PlanKey key;
-  const bool keyable = !bad_dims(ndim, old_len, new_len) && (ndim == 0 || maps);
-  if (keyable) {
-    bool ok = true;
-    for (int d = 0; d < ndim; ++d) ok = ok && (old_len[d] == 0 || maps[d]);
-    if (ok) {
-      key.i32('U');
-      key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
-      key.u32s(old_len, ndim), key.u32s(new_len, ndim);
-      key.tables(maps, old_len, ndim);
-      plan = plan_cache().find(key.bytes);
-    }
+  return run_cached(s, out, drillup_key(s, method, ndim, old_len, new_len, maps),
+                    [&](olap_plan **p) { return olap_drillup_plan(p, s->dtype, s->default_kind, method, ndim, old_len, new_len, maps); });
+}
+
+// the measures of a batch can share one plan and one launch
+static bool same_shape(int n, const olap_store *const *stores) {
+  bool same = n > 1;
+  for (int i = 0; i < n && same; ++i)
+    same = stores[i]->dtype == stores[0]->dtype && stores[i]->default_kind == stores[0]->default_kind && stores[i]->size == stores[0]->size &&
+           stores[i]->device == stores[0]->device && !stores[i]->track_order;
+  return same;
+}
+
+// a batch failed: none of its results stays
+static int drop_results(int n, olap_store **out, int rc) {
+  for (int i = 0; i < n; ++i) {
+    if (out[i]) olap_store_destroy(out[i]);
+    out[i] = nullptr;
   }
-  if (!plan) {
-    int rc = olap_drillup_plan(&plan, s->dtype, s->default_kind, method, ndim, old_len, new_len, maps);
-    if (rc) return rc;
-    if (!key.empty()) plan_cache().insert(key.bytes, plan);
-    else {
-      rc = check_store_cells(s, plan);
-      if (!rc) rc = run_to_new_store(plan, s, out);
-      olap_plan_destroy(plan);
-      return rc;
-    }
-  }
-  int rc = check_store_cells(s, plan);
-  if (!rc) rc = run_to_new_store(plan, s, out);
-  plan_cache().release(plan);
   return rc;
 }
+
+namespace {
+// The buffers of a batch of n over one plan: allocates the results and lists every pair's pointers.
+struct BatchBuffers {
+  std::vector<const void *> in_v;
+  std::vector<const int32_t *> in_s;
+  std::vector<void *> out_v;
+  std::vector<int32_t *> out_s;
+  explicit BatchBuffers(int n) : in_v(n), in_s(n), out_v(n), out_s(n) {}
+  int alloc(const olap_plan *plan, const olap_store *const *stores, olap_store **out) {
+    for (int i = 0; i < (int)in_v.size(); ++i) {
+      const int rc = store_alloc(&out[i], olap_plan_out_cells(plan), stores[0]->dtype, stores[0]->default_kind);
+      if (rc) return rc;
+      in_v[i] = stores[i]->values;
+      in_s[i] = mask_needed(stores[i]);
+      out_v[i] = out[i]->values;
+      out_s[i] = out[i]->status;
+    }
+    return OLAP_OK;
+  }
+  Pairs pairs() const { return Pairs{(int)in_v.size(), in_v.data(), in_s.data(), out_v.data(), out_s.data()}; }
+};
+}  // namespace
 
 // Cube.drillUp over several stored measures that share cell type, default and rule (src/cube.js:1012-1020 calls the
 // store once per measure): one plan, one launch (olap_plan_run_batch).  Stores that differ in type or default, or that
@@ -2893,63 +2975,43 @@ extern "C" int olap_store_drillup_batch(int n, const olap_store *const *stores, 
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   for (int i = 0; i < n; ++i)
     if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
-  bool same = n > 1;
-  for (int i = 0; i < n && same; ++i)
-    same = stores[i]->dtype == stores[0]->dtype && stores[i]->default_kind == stores[0]->default_kind && stores[i]->size == stores[0]->size &&
-           stores[i]->device == stores[0]->device && !stores[i]->track_order;
-  auto undo = [&](int rc) {
-    for (int i = 0; i < n; ++i) {
-      if (out[i]) olap_store_destroy(out[i]);
-      out[i] = nullptr;
-    }
-    return rc;
-  };
-  if (!same || bad_dims(ndim, old_len, new_len) || (ndim > 0 && !maps)) {
+  if (!same_shape(n, stores) || bad_dims(ndim, old_len, new_len) || (ndim > 0 && !maps)) {
     for (int i = 0; i < n; ++i) {
       const int rc = olap_store_drillup(stores[i], &out[i], ndim, old_len, new_len, maps, method);
-      if (rc) return undo(rc);
+      if (rc) return drop_results(n, out, rc);
     }
     return OLAP_OK;
   }
   const olap_store *s0 = stores[0];
   OnStoreDevice on_device__(s0);
-  olap_plan *plan = nullptr;
-  PlanKey key;
-  bool keyable = true;
-  for (int d = 0; d < ndim; ++d) keyable = keyable && (old_len[d] == 0 || maps[d]);
-  if (keyable) {
-    key.i32('U');
-    key.i32(s0->dtype), key.i32(s0->default_kind), key.i32(method), key.i32(ndim);
-    key.u32s(old_len, ndim), key.u32s(new_len, ndim);
-    key.tables(maps, old_len, ndim);
-    plan = plan_cache().find(key.bytes);
-  }
-  bool cached = plan != nullptr;
-  if (!plan) {
-    int rc = olap_drillup_plan(&plan, s0->dtype, s0->default_kind, method, ndim, old_len, new_len, maps);
-    if (rc) return rc;
-    if (keyable) {
-      plan_cache().insert(key.bytes, plan);
-      cached = true;
-    }
-  }
-  int rc = check_store_cells(s0, plan);
-  std::vector<const void *> in_v(n);
-  std::vector<const int32_t *> in_s(n);
-  std::vector<void *> out_v(n);
-  std::vector<int32_t *> out_s(n);
-  for (int i = 0; i < n && !rc; ++i) {
-    rc = store_alloc(&out[i], olap_plan_out_cells(plan), s0->dtype, s0->default_kind);
-    if (rc) break;
-    in_v[i] = stores[i]->values;
-    in_s[i] = mask_needed(stores[i]);
-    out_v[i] = out[i]->values;
-    out_s[i] = out[i]->status;
-  }
-  if (!rc) rc = olap_plan_run_batch(plan, n, in_v.data(), in_s.data(), out_v.data(), out_s.data(), nullptr);
-  if (cached) plan_cache().release(plan);
-  else olap_plan_destroy(plan);
-  return rc ? undo(rc) : OLAP_OK;
+  PlanRef ref;
+  int rc = ref.acquire(drillup_key(s0, method, ndim, old_len, new_len, maps),
+                       [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, method, ndim, old_len, new_len, maps); });
+  if (rc) return rc;
+  BatchBuffers b(n);
+  rc = check_store_cells(s0, ref.plan);
+  if (!rc) rc = b.alloc(ref.plan, stores, out);
+  if (!rc) rc = olap_plan_run_batch(ref.plan, n, b.in_v.data(), b.in_s.data(), b.out_v.data(), b.out_s.data(), nullptr);
+  return rc ? drop_results(n, out, rc) : OLAP_OK;
+}
+
+// The measures of one shape with a rule each, as mixed-rule launches over the plan of the first rule (a drillUp plan's
+// tables do not depend on the rule).  OLAP_MIXED_NOT_APPLICABLE: the caller goes rule by rule, which also reports
+// arguments that are not there to read.  The caller drops the results on any failure.
+static int drillup_mixed(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim, const uint32_t *old_len,
+                         const uint32_t *new_len, const uint32_t *const *maps) {
+  const olap_store *s0 = stores[0];
+  OnStoreDevice on_device__(s0);
+  const PlanKey key = drillup_key(s0, methods[0], ndim, old_len, new_len, maps);
+  if (key.empty()) return OLAP_MIXED_NOT_APPLICABLE;
+  PlanRef ref;
+  int rc = ref.acquire(key, [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, methods[0], ndim, old_len, new_len, maps); });
+  if (rc) return rc;
+  BatchBuffers b(n);
+  rc = check_store_cells(s0, ref.plan);
+  if (!rc) rc = b.alloc(ref.plan, stores, out);
+  if (!rc) rc = plan_run_mixed(ref.plan, b.pairs(), methods, nullptr);
+  return rc;
 }
 
 // Cube.drillUp over ALL stored measures of a cube, each with its own rule for the rolled-up dimension (methods[i]):
@@ -2963,52 +3025,12 @@ extern "C" int olap_store_drillup_multi(int n, const olap_store *const *stores, 
     if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
   }
-  auto undo = [&](int rc) {
-    for (int i = 0; i < n; ++i) {
-      if (out[i]) olap_store_destroy(out[i]);
-      out[i] = nullptr;
-    }
-    return rc;
-  };
-  bool same = n > 1, one_rule = true;
-  for (int i = 0; i < n; ++i) {
-    same = same && stores[i]->dtype == stores[0]->dtype && stores[i]->default_kind == stores[0]->default_kind && stores[i]->size == stores[0]->size &&
-           stores[i]->device == stores[0]->device && !stores[i]->track_order;
-    one_rule = one_rule && methods[i] == methods[0];
-  }
-  bool keyable = !bad_dims(ndim, old_len, new_len) && (ndim == 0 || maps);
-  for (int d = 0; keyable && d < ndim; ++d) keyable = old_len[d] == 0 || maps[d];
-  if (same && !one_rule && keyable) {
-    const olap_store *s0 = stores[0];
-    OnStoreDevice on_device__(s0);
-    PlanKey key;
-    key.i32('U');
-    key.i32(s0->dtype), key.i32(s0->default_kind), key.i32(methods[0]), key.i32(ndim);
-    key.u32s(old_len, ndim), key.u32s(new_len, ndim);
-    key.tables(maps, old_len, ndim);
-    olap_plan *plan = plan_cache().find(key.bytes);
-    if (!plan) {
-      int rc = olap_drillup_plan(&plan, s0->dtype, s0->default_kind, methods[0], ndim, old_len, new_len, maps);
-      if (rc) return rc;
-      plan_cache().insert(key.bytes, plan);
-    }
-    int rc = check_store_cells(s0, plan);
-    std::vector<const void *> in_v(n);
-    std::vector<const int32_t *> in_s(n);
-    std::vector<void *> out_v(n);
-    std::vector<int32_t *> out_s(n);
-    for (int i = 0; i < n && !rc; ++i) {
-      rc = store_alloc(&out[i], olap_plan_out_cells(plan), s0->dtype, s0->default_kind);
-      if (rc) break;
-      in_v[i] = stores[i]->values;
-      in_s[i] = mask_needed(stores[i]);
-      out_v[i] = out[i]->values;
-      out_s[i] = out[i]->status;
-    }
-    if (!rc) rc = plan_run_mixed(plan, n, methods, in_v.data(), in_s.data(), out_v.data(), out_s.data(), nullptr);
-    plan_cache().release(plan);
+  bool one_rule = true;
+  for (int i = 0; i < n; ++i) one_rule = one_rule && methods[i] == methods[0];
+  if (same_shape(n, stores) && !one_rule) {
+    const int rc = drillup_mixed(n, stores, methods, out, ndim, old_len, new_len, maps);
     if (rc == OLAP_OK) return OLAP_OK;
-    undo(rc);
+    drop_results(n, out, rc);
     if (rc != OLAP_MIXED_NOT_APPLICABLE) return rc;
   }
   // rule by rule: the measures of one rule together (olap_store_drillup_batch groups further by cell type)
@@ -3026,7 +3048,7 @@ extern "C" int olap_store_drillup_multi(int n, const olap_store *const *stores, 
     std::vector<olap_store *> res(members.size(), nullptr);
     for (size_t k = 0; k < members.size(); ++k) in[k] = stores[members[k]];
     const int rc = olap_store_drillup_batch((int)members.size(), in.data(), res.data(), ndim, old_len, new_len, maps, methods[i]);
-    if (rc) return undo(rc);
+    if (rc) return drop_results(n, out, rc);
     for (size_t k = 0; k < members.size(); ++k) out[members[k]] = res[k];
   }
   return OLAP_OK;
@@ -3037,39 +3059,12 @@ static int store_drilldown_plain(const olap_store *s, olap_store **out, int ndim
                                  const double *distributions, uint64_t n_dist) {
   if (!s || !out) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
   *out = nullptr;
-  olap_plan *plan = nullptr;
-  if (!distributions && !bad_dims(ndim, old_len, new_len) && (ndim == 0 || maps)) {
-    // cached like the other operations (a plan costs a table upload and a few allocations: ~100 us against a 70 us kernel);
-    // plans with distributions carry a per-run error word and their weights: built per call
-    bool ok = true;
-    for (int d = 0; d < ndim; ++d) ok = ok && (new_len[d] == 0 || maps[d]);
-    if (ok) {
-      PlanKey key;
-      key.i32('W');
-      key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
-      key.u32s(old_len, ndim), key.u32s(new_len, ndim);
-      key.tables(maps, new_len, ndim);
-      plan = plan_cache().find(key.bytes);
-      bool cached = true;
-      if (!plan) {
-        int rc = olap_drilldown_plan(&plan, s->dtype, s->default_kind, method, ndim, old_len, new_len, maps, nullptr, 0);
-        if (rc) return rc;
-        cached = plan->dev_tmp == nullptr;  // (the two-pass form keeps a buffer of quotients as large as the parents: not held on to)
-        if (cached) plan_cache().insert(key.bytes, plan);
-      }
-      int rc = check_store_cells(s, plan);
-      if (!rc) rc = run_to_new_store(plan, s, out);
-      if (cached) plan_cache().release(plan);
-      else olap_plan_destroy(plan);
-      return rc;
-    }
-  }
-  int rc = olap_drilldown_plan(&plan, s->dtype, s->default_kind, method, ndim, old_len, new_len, maps, distributions, n_dist);
-  if (rc) return rc;
-  rc = check_store_cells(s, plan);
-  if (!rc) rc = run_to_new_store(plan, s, out);
-  olap_plan_destroy(plan);
-  return rc;
+  // cached like the other operations (a plan costs a table upload and a few allocations: ~100 us against a 70 us kernel);
+  // plans with distributions carry a per-run error word and their weights: built per call (no key).  The two-pass form
+  // keeps a buffer of quotients as large as the parents: not held on to either.
+  return run_cached(s, out, distributions ? PlanKey() : drilldown_key(s, method, ndim, old_len, new_len, maps),
+                    [&](olap_plan **p) { return olap_drilldown_plan(p, s->dtype, s->default_kind, method, ndim, old_len, new_len, maps, distributions, n_dist); },
+                    [](const olap_plan *p) { return p->dev_tmp == nullptr; });
 }
 
 extern "C" int olap_store_drilldown(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len,
@@ -3085,34 +3080,8 @@ static int store_dice_plain(const olap_store *s, olap_store **out, int ndim, con
                             const uint32_t *new_len, const int32_t *const *sel) {
   if (!s || !out) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
   *out = nullptr;
-  olap_plan *plan = nullptr;
-  PlanKey key;
-  if (!bad_dims(ndim, old_len, new_len) && (ndim == 0 || sel)) {
-    bool ok = true;
-    for (int d = 0; d < ndim; ++d) ok = ok && (new_len[d] == 0 || sel[d]);
-    if (ok) {
-      key.i32('D');
-      key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim);
-      key.u32s(old_len, ndim), key.u32s(new_len, ndim);
-      key.tables((const uint32_t *const *)sel, new_len, ndim);
-      plan = plan_cache().find(key.bytes);
-    }
-  }
-  if (!plan) {
-    int rc = olap_dice_plan(&plan, s->dtype, s->default_kind, ndim, old_len, new_len, sel);
-    if (rc) return rc;
-    if (!key.empty()) plan_cache().insert(key.bytes, plan);
-    else {
-      rc = check_store_cells(s, plan);
-      if (!rc) rc = run_to_new_store(plan, s, out);
-      olap_plan_destroy(plan);
-      return rc;
-    }
-  }
-  int rc = check_store_cells(s, plan);
-  if (!rc) rc = run_to_new_store(plan, s, out);
-  plan_cache().release(plan);
-  return rc;
+  return run_cached(s, out, dice_key(s, ndim, old_len, new_len, sel),
+                    [&](olap_plan **p) { return olap_dice_plan(p, s->dtype, s->default_kind, ndim, old_len, new_len, sel); });
 }
 
 // an operation on a tracked store failed after its result was allocated
@@ -3146,63 +3115,15 @@ extern "C" int olap_store_dice_drillup(const olap_store *s, olap_store **out, in
     olap_store_destroy(mid);
     return rc;
   }
-  olap_plan *plan = nullptr;
-  PlanKey key;
-  if (!bad_dims(ndim, old_len, mid_len) && !bad_dims(ndim, mid_len, new_len) && (ndim == 0 || (sel && maps))) {
-    bool ok = true;
-    for (int d = 0; d < ndim; ++d) ok = ok && (mid_len[d] == 0 || (sel[d] && maps[d]));
-    if (ok) {
-      key.i32('F');
-      key.i32(s->dtype), key.i32(s->default_kind), key.i32(method), key.i32(ndim);
-      key.u32s(old_len, ndim), key.u32s(mid_len, ndim), key.u32s(new_len, ndim);
-      key.tables((const uint32_t *const *)sel, mid_len, ndim);
-      key.tables(maps, mid_len, ndim);
-      plan = plan_cache().find(key.bytes);
-    }
-  }
-  if (!plan) {
-    int rc = olap_dice_drillup_plan(&plan, s->dtype, s->default_kind, method, ndim, old_len, mid_len, new_len, sel, maps);
-    if (rc) return rc;
-    if (!key.empty()) plan_cache().insert(key.bytes, plan);
-    else {
-      rc = check_store_cells(s, plan);
-      if (!rc) rc = run_to_new_store(plan, s, out);
-      olap_plan_destroy(plan);
-      return rc;
-    }
-  }
-  int rc = check_store_cells(s, plan);
-  if (!rc) rc = run_to_new_store(plan, s, out);
-  plan_cache().release(plan);
-  return rc;
+  return run_cached(s, out, dice_drillup_key(s, method, ndim, old_len, mid_len, new_len, sel, maps),
+                    [&](olap_plan **p) { return olap_dice_drillup_plan(p, s->dtype, s->default_kind, method, ndim, old_len, mid_len, new_len, sel, maps); });
 }
 
 static int store_reorder_plain(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len, const int32_t *perm) {
   if (!s || !out) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
   *out = nullptr;
-  olap_plan *plan = nullptr;
-  PlanKey key;
-  if (!bad_dims(ndim, old_len, perm)) {
-    key.i32('R');
-    key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim);
-    key.u32s(old_len, ndim), key.u32s((const uint32_t *)perm, ndim);
-    plan = plan_cache().find(key.bytes);
-  }
-  if (!plan) {
-    int rc = olap_reorder_plan(&plan, s->dtype, s->default_kind, ndim, old_len, perm);
-    if (rc) return rc;
-    if (!key.empty()) plan_cache().insert(key.bytes, plan);
-    else {
-      rc = check_store_cells(s, plan);
-      if (!rc) rc = run_to_new_store(plan, s, out);
-      olap_plan_destroy(plan);
-      return rc;
-    }
-  }
-  int rc = check_store_cells(s, plan);
-  if (!rc) rc = run_to_new_store(plan, s, out);
-  plan_cache().release(plan);
-  return rc;
+  return run_cached(s, out, reorder_key(s, ndim, old_len, perm),
+                    [&](olap_plan **p) { return olap_reorder_plan(p, s->dtype, s->default_kind, ndim, old_len, perm); });
 }
 
 extern "C" int olap_store_reorder(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len,
@@ -3210,21 +3131,6 @@ extern "C" int olap_store_reorder(const olap_store *s, olap_store **out, int ndi
   OnStoreDevice on_device__(s);
   int rc = store_reorder_plain(s, out, ndim, old_len, perm);
   if (!rc && s->track_order) rc = drop_result(out, order_after_reorder(s, *out, ndim, old_len, perm));
-  return rc;
-}
-
-static int store_load_plain(olap_store *s, const olap_store *other, int ndim, const uint32_t *my_len, const uint32_t *his_len,
-                            const int32_t *const *his_to_mine);
-
-extern "C" int olap_store_load(olap_store *s, const olap_store *other, int ndim, const uint32_t *my_len,
-                               const uint32_t *his_len, const int32_t *const *his_to_mine) {
-  OnStoreDevice on_device__(s);
-  if (!s || !other) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
-  if (s->device != other->device)
-    return fail(OLAP_ERR_INVALID_ARGUMENT, "load: the stores live on different devices (%d and %d)", s->device, other->device);
-  int rc = order_before_load(s);
-  if (!rc) rc = store_load_plain(s, other, ndim, my_len, his_len, his_to_mine);
-  if (!rc) rc = order_after_load(s, other, ndim, my_len, his_len, his_to_mine);
   return rc;
 }
 
@@ -3242,5 +3148,17 @@ static int store_load_plain(olap_store *s, const olap_store *other, int ndim, co
   drop_lazy_status(s);
   rc = olap_plan_run(plan, other->values, mask_needed(other), s->values, s->status, nullptr);
   olap_plan_destroy(plan);  // waits for the launch (its tables go back to the pool)
+  return rc;
+}
+
+extern "C" int olap_store_load(olap_store *s, const olap_store *other, int ndim, const uint32_t *my_len,
+                               const uint32_t *his_len, const int32_t *const *his_to_mine) {
+  OnStoreDevice on_device__(s);
+  if (!s || !other) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (s->device != other->device)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "load: the stores live on different devices (%d and %d)", s->device, other->device);
+  int rc = order_before_load(s);
+  if (!rc) rc = store_load_plain(s, other, ndim, my_len, his_len, his_to_mine);
+  if (!rc) rc = order_after_load(s, other, ndim, my_len, his_len, his_to_mine);
   return rc;
 }

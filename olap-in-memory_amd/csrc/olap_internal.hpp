@@ -21,6 +21,16 @@ OLAP_INTERNAL int hip_fail(hipError_t e, const char *what);
     if (e__ != hipSuccess) return hip_fail(e__, #expr); \
   } while (0)
 
+// Runs CALL with T naming the cell type of `dtype` (an OLAP_* dtype that passed check_dtype).  The one cell-type
+// dispatch of the library; the type's name is a parameter so that two dispatches can nest.
+#define DISPATCH_DTYPE(dtype, T, CALL)                     \
+  switch (dtype) {                                         \
+    case OLAP_INT32: { using T = int32_t; CALL; break; }   \
+    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
+    case OLAP_FLOAT32: { using T = float; CALL; break; }   \
+    default: { using T = double; CALL; break; }            \
+  }
+
 // remembers the calling thread's device and puts it back
 struct DeviceGuard {
   int saved = -1;

@@ -38,14 +38,6 @@ using namespace olap;
 
 namespace {
 
-#define ORDER_DISPATCH(dtype, CALL)                        \
-  switch (dtype) {                                         \
-    case OLAP_INT32: { using T = int32_t; CALL; break; }   \
-    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
-    case OLAP_FLOAT32: { using T = float; CALL; break; }   \
-    default: { using T = double; CALL; break; }            \
-  }
-
 unsigned grid_for_n(uint64_t n) {
   const uint64_t want = (n + kBlock - 1) / kBlock;
   return (unsigned)(want < 1 ? 1 : (want < 4096 ? want : 4096));
@@ -302,7 +294,7 @@ int seq_materialise(const olap_store *s) {
   if (s->size >= 0x7FFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "insertion-order tracking supports stores below 2^31 cells");
   int rc = seq_alloc(s);
   if (rc) return rc;
-  ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((seq_iota_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
+  DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((seq_iota_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
                                               s->seq, s->size, s->default_kind == OLAP_DEFAULT_NAN));
   s->next_seq = s->size + 1;
   return launched("seq_iota_kernel");
@@ -325,7 +317,7 @@ int seq_renumber_if_needed(const olap_store *s, uint64_t wanted) {
 }
 
 int seq_mask(olap_store *s, const uint32_t *fallback) {
-  ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((seq_mask_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq,
+  DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((seq_mask_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq,
                                               fallback, s->size, s->default_kind == OLAP_DEFAULT_NAN));
   return launched("seq_mask_kernel");
 }
@@ -382,7 +374,7 @@ int order_after_bulk_write(olap_store *s) {
   (void)had;
   int rc = seq_renumber_if_needed(s, s->size + 1);
   if (rc) return rc;
-  ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((seq_after_bulk_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
+  DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((seq_after_bulk_kernel<T>), grid_for_n(s->size), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s),
                                               s->seq, s->size, s->default_kind == OLAP_DEFAULT_NAN, (uint32_t)s->next_seq));
   s->next_seq += s->size + 1;
   return launched("seq_after_bulk_kernel");
@@ -406,7 +398,7 @@ int order_after_set_value(olap_store *s, uint64_t index) {
   }
   int rc = seq_renumber_if_needed(s, 2);
   if (rc) return rc;
-  ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((seq_set_cell_kernel<T>), 1, 1, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq, index,
+  DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((seq_set_cell_kernel<T>), 1, 1, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq, index,
                                               (uint32_t)s->next_seq, s->default_kind == OLAP_DEFAULT_NAN));
   s->next_seq += 1;
   return launched("seq_set_cell_kernel");
@@ -486,7 +478,7 @@ static int order_drillup_replay(const olap_store *s, olap_store **out, int ndim,
     return rc;
   }
   const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
-  ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((replay_clear_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (T *)o->values, o->status, o->seq, n_out, def_nan));
+  DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((replay_clear_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (T *)o->values, o->status, o->seq, n_out, def_nan));
   if (n_in == 0 || n_out == 0) {
     rc = launched("replay_clear_kernel");
     if (!rc) {
@@ -538,7 +530,7 @@ static int order_drillup_replay(const olap_store *s, olap_store **out, int ndim,
     e = hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (const uint64_t *)keys_a, (uint64_t *)keys_b, (const uint32_t *)vals_a, (uint32_t *)vals_b,
                                            (unsigned int)n_in, 0, end_bit > 64 ? 64 : end_bit, (hipStream_t) nullptr);
   if (e == hipSuccess) {
-    ORDER_DISPATCH(s->dtype, launch_replay<T>(method, (const T *)s->values, (const uint64_t *)keys_b, (const uint32_t *)vals_b, n_in, (T *)o->values, o->status,
+    DISPATCH_DTYPE(s->dtype, T, launch_replay<T>(method, (const T *)s->values, (const uint64_t *)keys_b, (const uint32_t *)vals_b, n_in, (T *)o->values, o->status,
                                                o->seq, def_nan));
     e = hipGetLastError();
   }
@@ -633,7 +625,7 @@ int order_drillup(const olap_store *s, olap_store **out, int ndim, const uint32_
   if (e == hipSuccess) e = hipMemcpy(dev_tab, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   rc = e == hipSuccess ? seq_alloc(o) : hip_fail(e, "hipMalloc(drillUp by order)");
   if (!rc) {
-    ORDER_DISPATCH(s->dtype, hipLaunchKernelGGL((drillup_byseq_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq,
+    DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((drillup_byseq_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (const T *)s->values, mask_needed(s), s->seq,
                                                 (T *)o->values, o->status, o->seq, outer, K, G, inner, dev_tab, dev_tab + G + 1, method == OLAP_LAST,
                                                 s->default_kind == OLAP_DEFAULT_NAN));
     rc = launched("drillup_byseq_kernel");

@@ -32,14 +32,6 @@ using namespace olap;
 
 namespace {
 
-#define SEL_DISPATCH(dtype, T, CALL)                      \
-  switch (dtype) {                                        \
-    case OLAP_INT32: { using T = int32_t; CALL; break; }  \
-    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
-    case OLAP_FLOAT32: { using T = float; CALL; break; }  \
-    default: { using T = double; CALL; break; }           \
-  }
-
 constexpr int kSelMaxLevels = 64;    // cube dimensions (OLAP_MAX_DIMS) + free filter keys
 constexpr int kSelInline = 512;      // index entries that travel in the kernel arguments (no upload)
 constexpr unsigned kSelBlocks = 2048;
@@ -525,7 +517,7 @@ int select_cert(const olap_store *s, int ndim, const uint32_t *lens, const uint3
   OnStoreDevice on_device__(s);
   const bool vec = (((uintptr_t)s->values | (uintptr_t)mask_needed(s)) & 15u) == 0;
   auto launch = [&](const GatherPlan &p, unsigned blocks, Cert *partial) {
-    SEL_DISPATCH(s->dtype, T, {
+    DISPATCH_DTYPE(s->dtype, T, {
       if (vec) hipLaunchKernelGGL((select_total_kernel<StoreSource<T>, T, true>), blocks, kBlock, 0, nullptr, store_source<T>(s), p, partial);
       else hipLaunchKernelGGL((select_total_kernel<StoreSource<T>, T, false>), blocks, kBlock, 0, nullptr, store_source<T>(s), p, partial);
     });
@@ -619,7 +611,7 @@ static int select_sequential(const olap_store *s, const uint32_t *lens, int ndim
                              const int32_t *const *sel, double *total) {
   OnStoreDevice on_device__(s);
   auto launch = [&](const NestPlan &p, uint64_t first, uint64_t k, double *out) {
-    SEL_DISPATCH(s->dtype, T,
+    DISPATCH_DTYPE(s->dtype, T,
                  hipLaunchKernelGGL((select_gather_kernel<StoreSource<T>>), select_grid(k), kBlock, 0, nullptr, store_source<T>(s), p, first, k, out));
   };
   return sequential_of(lens, ndim, nlev, axis, n_sel, sel, launch, total);
@@ -711,7 +703,7 @@ int select_copy(olap_store *t, const olap_store *src, int ndim, const uint32_t *
   if (n == 0) return OLAP_OK;
   const int tn = t->default_kind == OLAP_DEFAULT_NAN;
   return copy_into(t, p, all, n, [&](const NestPlan &q, uint64_t k, uint32_t *seq, uint32_t seq_base) {
-    SEL_DISPATCH(src->dtype, S, SEL_DISPATCH(t->dtype, T, hipLaunchKernelGGL((copy_select_kernel<StoreSource<S>, T>), select_grid(k), kBlock, 0, nullptr,
+    DISPATCH_DTYPE(src->dtype, S, DISPATCH_DTYPE(t->dtype, T, hipLaunchKernelGGL((copy_select_kernel<StoreSource<S>, T>), select_grid(k), kBlock, 0, nullptr,
                                                                             store_source<S>(src), (T *)t->values, t->status, seq, seq_base, tn, q, k)));
   });
 }
@@ -837,7 +829,7 @@ extern "C" int olap_store_copy_select_formula(olap_store *target, const int32_t 
   const FormulaSource src{prog};
   const int tn = target->default_kind == OLAP_DEFAULT_NAN;
   rc = copy_into(target, p, all, n, [&](const NestPlan &q, uint64_t k, uint32_t *seq, uint32_t seq_base) {
-    SEL_DISPATCH(target->dtype, T,
+    DISPATCH_DTYPE(target->dtype, T,
                  hipLaunchKernelGGL((copy_select_kernel<FormulaSource, T>), select_grid(k), kBlock, 0, nullptr, src, (T *)target->values,
                                     target->status, seq, seq_base, tn, q, k));
   });
@@ -907,14 +899,14 @@ static int set_values_batch(olap_store *s, uint64_t n, const uint64_t *indexes, 
                                            (unsigned int)n, 0, cell_bits, (hipStream_t) nullptr);
   const int def_nan = s->default_kind == OLAP_DEFAULT_NAN;
   if (e == hipSuccess) {
-    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_mark_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+    DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((set_values_mark_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
                                                  (const uint32_t *)pos_sorted, dv, dn, def_nan, n, marker));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipcub::DeviceScan::InclusiveScan(tmp, scan_bytes, (const uint32_t *)marker, run, hipcub::Max(), (unsigned int)n,
                                                              (hipStream_t) nullptr);
   if (e == hipSuccess) {
-    SEL_DISPATCH(s->dtype, T, hipLaunchKernelGGL((set_values_write_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
+    DISPATCH_DTYPE(s->dtype, T, hipLaunchKernelGGL((set_values_write_kernel<T>), select_grid(n), kBlock, 0, nullptr, (const uint64_t *)cell_sorted,
                                                  (const uint32_t *)pos_sorted, dv, dn, (const uint32_t *)run, n, (T *)s->values, s->status, seq,
                                                  seq_base, def_nan));
     e = hipGetLastError();

@@ -479,14 +479,6 @@ unsigned grid_for_n(uint64_t n) {
   return (unsigned)(want < 1 ? 1 : (want < 2048 ? want : 2048));
 }
 
-#define SHARD_DISPATCH(dtype, CALL)                        \
-  switch (dtype) {                                         \
-    case OLAP_INT32: { using T = int32_t; CALL; break; }   \
-    case OLAP_UINT32: { using T = uint32_t; CALL; break; } \
-    case OLAP_FLOAT32: { using T = float; CALL; break; }   \
-    default: { using T = double; CALL; break; }            \
-  }
-
 int launch_check(const char *what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, what);
@@ -828,7 +820,7 @@ extern "C" int olap_shard_drillup_create(olap_shard_drillup **out, olap_comm *co
       }
       if (!rc && rs.local_cells == 0 && def_nan && is_float_dtype(dtype) && recipe.payload_op[0] == OLAP_XCHG_GATHER) {
         // a rank without rows ships "unset everywhere": the canonical default
-        SHARD_DISPATCH(dtype, hipLaunchKernelGGL((fill_default_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (T *)b.send[0], n_out, 1));
+        DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((fill_default_kernel<T>), grid_for_n(n_out), kBlock, 0, nullptr, (T *)b.send[0], n_out, 1));
         rc = launch_check("fill_default_kernel");
       }
       if (!rc && (separate_result(recipe.finish) || op->fused) && !(op->placement == OLAP_PLACE_ROOT && l.rank != 0)) {
@@ -943,19 +935,19 @@ static int shard_finish(olap_shard_drillup *op, int local, int k, hipStream_t st
   switch (op->recipe.finish) {
     case OLAP_FINISH_NONE:
       if (!dest) break;  // the reduced values are the result where they lie
-      SHARD_DISPATCH(op->dtype, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const T *)b.recv[0] + off,
+      DISPATCH_DTYPE(op->dtype, T, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const T *)b.recv[0] + off,
                                                    (const int32_t *)nullptr, (T *)ov, os, cnt, def_nan));
       rc = launch_check("restore_default_kernel");
       break;
     case OLAP_FINISH_RESTORE:
-      SHARD_DISPATCH(op->dtype, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const T *)b.recv[0] + off,
+      DISPATCH_DTYPE(op->dtype, T, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const T *)b.recv[0] + off,
                                                    (const int32_t *)b.recv[1] + off, dest ? (T *)ov : (T *)b.recv[0],
                                                    dest ? os : (int32_t *)b.recv[1], cnt, def_nan));
       rc = launch_check("restore_default_kernel");
       break;
     case OLAP_FINISH_ROUND:
     case OLAP_FINISH_AVERAGE:
-      SHARD_DISPATCH(op->dtype, hipLaunchKernelGGL((partial_round_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const double *)b.recv[0] + off,
+      DISPATCH_DTYPE(op->dtype, T, hipLaunchKernelGGL((partial_round_kernel<T>), grid_for_n(cnt), kBlock, 0, stream, (const double *)b.recv[0] + off,
                                                    op->recipe.n_payloads > 1 ? (const int32_t *)b.recv[1] + off : nullptr,
                                                    dest ? (T *)ov : (T *)b.result, dest ? os : b.result_status, cnt, def_nan, op->recipe.finish));
       rc = launch_check("partial_round_kernel");
@@ -1020,20 +1012,12 @@ static int rank_direct_combine(olap_shard_drillup *op, size_t i, int k, hipStrea
     const uint64_t first = is_scatter(op->placement) ? (uint64_t)l.rank * op->per : 0;
     const uint64_t n = is_scatter(op->placement) ? op->per : op->n_out;
     const bool sum = rp.payload_op[p] == OLAP_XCHG_SUM;
-#define DIRECT_LAUNCH(T)                                                                                                     \
-  do {                                                                                                                       \
-    if (sum) hipLaunchKernelGGL((direct_combine_kernel<T, OLAP_XCHG_SUM>), grid_for_n(n), kBlock, 0, x,                       \
-                                (const T *const *)b.peers[p], c->world, (T *)b.recv[p], first, n);                           \
-    else hipLaunchKernelGGL((direct_combine_kernel<T, OLAP_XCHG_MAX>), grid_for_n(n), kBlock, 0, x,                           \
-                            (const T *const *)b.peers[p], c->world, (T *)b.recv[p], first, n);                               \
-  } while (0)
-    switch (rp.payload_dtype[p]) {
-      case OLAP_INT32: DIRECT_LAUNCH(int32_t); break;
-      case OLAP_UINT32: DIRECT_LAUNCH(uint32_t); break;
-      case OLAP_FLOAT32: DIRECT_LAUNCH(float); break;
-      default: DIRECT_LAUNCH(double); break;
-    }
-#undef DIRECT_LAUNCH
+    DISPATCH_DTYPE(rp.payload_dtype[p], T, {
+      if (sum) hipLaunchKernelGGL((direct_combine_kernel<T, OLAP_XCHG_SUM>), grid_for_n(n), kBlock, 0, x,
+                                  (const T *const *)b.peers[p], c->world, (T *)b.recv[p], first, n);
+      else hipLaunchKernelGGL((direct_combine_kernel<T, OLAP_XCHG_MAX>), grid_for_n(n), kBlock, 0, x,
+                              (const T *const *)b.peers[p], c->world, (T *)b.recv[p], first, n);
+    });
     int rc = launch_check("direct_combine_kernel");
     if (rc) return rc;
   }
@@ -1152,10 +1136,10 @@ static int step_direct_fused(olap_shard_drillup *op, int k, const void *const *i
       const int dn = op->default_kind == OLAP_DEFAULT_NAN;
       const unsigned grid = grid_for_n(op->n_out);
       if (rp.payload_dtype[0] == OLAP_FLOAT64 && op->dtype != OLAP_FLOAT64) {
-        SHARD_DISPATCH(op->dtype, hipLaunchKernelGGL((direct_fused_kernel<T, double>), grid, kBlock, 0, x, (const double *const *)b0.peers[0], src1,
+        DISPATCH_DTYPE(op->dtype, T, hipLaunchKernelGGL((direct_fused_kernel<T, double>), grid, kBlock, 0, x, (const double *const *)b0.peers[0], src1,
                                                      c->world, rp.payload_op[1], op->n_out, rp.finish, dn, d));
       } else {
-        SHARD_DISPATCH(op->dtype, hipLaunchKernelGGL((direct_fused_kernel<T, T>), grid, kBlock, 0, x, (const T *const *)b0.peers[0], src1, c->world,
+        DISPATCH_DTYPE(op->dtype, T, hipLaunchKernelGGL((direct_fused_kernel<T, T>), grid, kBlock, 0, x, (const T *const *)b0.peers[0], src1, c->world,
                                                      rp.payload_op[1], op->n_out, rp.finish, dn, d));
       }
       if ((rc = launch_check("direct_fused_kernel"))) return rc;
@@ -1580,7 +1564,7 @@ extern "C" int olap_sharded_store_fill_seeded(olap_sharded_store *s, uint32_t se
     }
     int rc = olap_fill_seeded(sh->values, st, n, slab_first(s, i), sh->dtype, seed, frac, nullptr);
     if (!rc && fnan) {  // the generator leaves 0 in dropped cells; under a NaN default they hold NaN
-      SHARD_DISPATCH(sh->dtype, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(n), kBlock, 0, nullptr, (const T *)sh->values, (const int32_t *)st,
+      DISPATCH_DTYPE(sh->dtype, T, hipLaunchKernelGGL((restore_default_kernel<T>), grid_for_n(n), kBlock, 0, nullptr, (const T *)sh->values, (const int32_t *)st,
                                                    (T *)sh->values, st, n, 1));
       rc = launch_check("restore_default_kernel");
     }

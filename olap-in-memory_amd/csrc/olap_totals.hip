@@ -696,12 +696,7 @@ extern "C" int olap_store_totals(const olap_store *st, int ndim, const uint32_t 
       return hip_fail(e, "hipMalloc(totals)");
     }
   }
-  switch (st->dtype) {
-    case OLAP_INT32: rc = totals_typed<int32_t>(st, s, dev_out, dev_status, launches, bytes_read); break;
-    case OLAP_UINT32: rc = totals_typed<uint32_t>(st, s, dev_out, dev_status, launches, bytes_read); break;
-    case OLAP_FLOAT32: rc = totals_typed<float>(st, s, dev_out, dev_status, launches, bytes_read); break;
-    default: rc = totals_typed<double>(st, s, dev_out, dev_status, launches, bytes_read); break;
-  }
+  DISPATCH_DTYPE(st->dtype, T, rc = totals_typed<T>(st, s, dev_out, dev_status, launches, bytes_read));
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpy(host_values, dev_out, s.ext * sizeof(double), hipMemcpyDeviceToHost);
   if (!rc && e == hipSuccess && host_status) e = hipMemcpy(host_status, dev_status, s.ext * sizeof(int32_t), hipMemcpyDeviceToHost);
@@ -829,12 +824,7 @@ extern "C" int olap_formula_totals(const int32_t *code, int n_code, const double
       for (int d = 0; d < ndim; ++d) si.method[d] = methods[(size_t)i * ndim + d];
       int l = 0;
       uint64_t b = 0;
-      switch (st->dtype) {
-        case OLAP_INT32: rc = totals_typed<int32_t>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
-        case OLAP_UINT32: rc = totals_typed<uint32_t>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
-        case OLAP_FLOAT32: rc = totals_typed<float>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
-        default: rc = totals_typed<double>(st, si, dev_e[i], nullptr, &l, &b, &held); break;
-      }
+      DISPATCH_DTYPE(st->dtype, T, rc = totals_typed<T>(st, si, dev_e[i], nullptr, &l, &b, &held));
       n_launch += l;
       bytes += b;
     }
