@@ -345,6 +345,36 @@ int olap_store_totals(const olap_store *store, int ndim, const uint32_t *lens, c
 int olap_formula_totals(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
                         const olap_store *const *inputs, int ndim, const uint32_t *lens, const int *methods,
                         double *host_values, int *launches, uint64_t *bytes_read);
+/* getNestedObjects(ids, withTotals = true): the extended cubes of SEVERAL measures of one cube — stored and computed —
+ * in one call.  `inputs` are the n_inputs (1..OLAP_REPORT_MAX_INPUTS) distinct stores the outputs draw on, input i with
+ * its own rules methods[i * ndim + d]; every input's extended cube E_i is built ONCE, whatever number of outputs reads it.
+ * The n_outputs (1..OLAP_REPORT_MAX_OUTPUTS) outputs are described by flat arrays of n_outputs entries:
+ *   out_stored[k] >= 0    output k is E of input out_stored[k]: the bits olap_store_totals(inputs[i], ...) puts in its
+ *                         host_values; out_n_code[k], out_n_consts[k] and out_n_inputs[k] must be 0;
+ *   out_stored[k] == -1   output k is a formula: its program is the next out_n_code[k] words of `code` and the next
+ *                         out_n_consts[k] entries of `consts` (the programs of the formula outputs lie one after the other
+ *                         in output order), exactly what olap_formula_totals accepts, no SCALAR operand; the next
+ *                         out_n_inputs[k] (1..OLAP_FORMULA_MAX_INPUTS) entries of `formula_inputs` name the report input
+ *                         its INPUT operand j reads (each input at most once per formula).  The bits are those of
+ *                         olap_formula_totals over these inputs.
+ * Refused on the host, before any device work, with messages that name the output ("output k: ..."): what
+ * olap_formula_totals refuses in a formula; an input index out of range; an input named twice by one formula; a stored
+ * input named by two outputs (the caller de-duplicates ids); an input no output uses; a tracked input ("ordered: ...");
+ * size, device and rule mismatches as olap_store_totals; more than 4e9 float64 cells on the device (outputs plus the
+ * inputs that only formulas read, times the extended cube: "totals: ..." — ask measure by measure).
+ * host_values receives n_outputs * ext float64, output k at k * ext, ext = prod(lens[d] + 1).  On the device a stored
+ * output's E is built straight into its slot of the one output slab, inputs that only formulas read get scratch cubes,
+ * and ONE launch evaluates every formula; one copy to the host, the call's only wait for device work (the formulas'
+ * programs are uploaded before the first launch, while the stream is idle).
+ * *launches: ext <= 12288 — per distinct cell type ceil(inputs of that type / 8), plus 1 when any output is a formula;
+ * larger — the sum over the inputs of what olap_store_totals reports, plus the same 1.  *bytes_read: every input's passes
+ * once, plus out_n_inputs[k] * ext * 8 per formula.  DESIGN.md §3 K6. */
+#define OLAP_REPORT_MAX_INPUTS 32
+#define OLAP_REPORT_MAX_OUTPUTS 32
+int olap_totals_report(int n_inputs, const olap_store *const *inputs, int ndim, const uint32_t *lens, const int *methods,
+                       int n_outputs, const int *out_stored, const int *out_n_code, const int32_t *code, const int *out_n_consts,
+                       const double *consts, const int *out_n_inputs, const int *formula_inputs, double *host_values,
+                       int *launches, uint64_t *bytes_read);
 
 /* Filtered totals and copies over a cartesian selection given as nlev LEVELS in nesting order, the first outermost
  * (getCombinations, src/cube.js:19-32: the filter's keys in their own order, then the unfiltered dimensions in cube

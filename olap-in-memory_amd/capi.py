@@ -113,6 +113,8 @@ SIGNATURES = {
     "olap_formula_select_total": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl,
                                          C.POINTER(C.c_int)]),
     "olap_formula_totals": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _i32, _pu32, C.POINTER(C.c_int), _pdbl, C.POINTER(C.c_int), _pu64]),
+    "olap_totals_report": (_i32, [_i32, _pvp, _i32, _pu32, C.POINTER(C.c_int), _i32, C.POINTER(C.c_int), C.POINTER(C.c_int), _pi32, C.POINTER(C.c_int), _pdbl,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int), _pdbl, C.POINTER(C.c_int), _pu64]),
     "olap_store_copy_select_formula": (_i32, [_vp, _pi32, _i32, _pdbl, _i32, _i32, _pvp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),
     "olap_memcpy_to_host": (_i32, [_vp, _vp, _u64]),
     "olap_memcpy_to_device": (_i32, [_vp, _vp, _u64]),

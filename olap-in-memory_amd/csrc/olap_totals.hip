@@ -192,6 +192,32 @@ __global__ __launch_bounds__(kBlock) void formula_totals_eval_kernel(const Formu
   if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) out[n - 1] = formula_at<OLAP_FORMULA_MAX_STACK>(p, n - 1);
 }
 
+// Every formula of one report (olap_totals_report) in ONE launch: blockIdx.y picks the formula, whose program and inputs
+// (float64 extended cubes, in_status all NULL) and output slot lie in device memory, as FormulaSource's program does.
+// The slots of a report are packed, so with an odd n a slot may start on an 8-byte boundary only: its first cell is then
+// stored alone and the lane's pairs start at the second cell, which keeps every 16-byte store aligned.
+struct ReportFormula {
+  FormulaProgram prog;
+  double *out;
+};
+__global__ __launch_bounds__(kBlock) void formula_report_eval_kernel(const ReportFormula *__restrict__ formulas, uint64_t n) {
+  const FormulaProgram &p = formulas[blockIdx.y].prog;
+  double *__restrict__ out = formulas[blockIdx.y].out;
+  const uint64_t head = ((uintptr_t)out & 8) ? 1 : 0;
+  const uint64_t pairs = (n - head) / 2;
+  for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < pairs; j += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i = head + 2 * j;
+    Vec<double, 2> r;
+    r.v[0] = formula_at<OLAP_FORMULA_MAX_STACK>(p, i);
+    r.v[1] = formula_at<OLAP_FORMULA_MAX_STACK>(p, i + 1);
+    store_vec<double, 2>(out + i, r);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (head) out[0] = formula_at<OLAP_FORMULA_MAX_STACK>(p, 0);
+    if ((n - head) & 1) out[n - 1] = formula_at<OLAP_FORMULA_MAX_STACK>(p, n - 1);
+  }
+}
+
 // ---- E in HBM: scatter, one launch per dimension, export -----------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kBlock) void totals_fill_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ val,
@@ -714,12 +740,27 @@ extern "C" int olap_store_totals(const olap_store *st, int ndim, const uint32_t 
 // cell to float64 before the first opcode), the same bits as evaluating on each of the 2^D marginal cubes.
 namespace {
 
-// every input of one cell type in ONE launch, a workgroup each (E <= kLdsCells)
+// every input of one cell type, a workgroup each (E <= kLdsCells): ONE launch per kTotalsBatch inputs of that type
 template <typename T>
 hipError_t totals_lds_batch(int n_inputs, const olap_store *const *inputs, const int *methods, const TotalsShape &s, double *const *dev_e, int *launches,
                             uint64_t *bytes) {
+  const size_t lds = (size_t)((s.ext * sizeof(T) + 15) & ~(uint64_t)15) + (size_t)s.ext;
+  const unsigned threads = s.ext >= 4096 ? 1024 : 256;
   TotalsBatch<T> b{};
   unsigned nb = 0;
+  auto flush = [&]() -> hipError_t {
+    if (!nb) return hipSuccess;
+    static PerDeviceFlag raised;  // (per cell type, per device)
+    if (lds > 48 * 1024 && !raised.test_and_set()) {
+      const hipError_t e = hipFuncSetAttribute((const void *)totals_lds_batch_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)(kLdsCells * (sizeof(T) + 1) + 16));
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((totals_lds_batch_kernel<T>), nb, threads, lds, nullptr, b, s);
+    ++*launches;
+    nb = 0;
+    return hipGetLastError();
+  };
   for (int i = 0; i < n_inputs; ++i) {
     if (inputs[i]->dtype != Cell<T>::dtype) continue;
     b.in[nb] = (const T *)inputs[i]->values;
@@ -728,20 +769,83 @@ hipError_t totals_lds_batch(int n_inputs, const olap_store *const *inputs, const
     b.def_nan[nb] = inputs[i]->default_kind == OLAP_DEFAULT_NAN;
     for (int d = 0; d < s.nd; ++d) b.method[nb][d] = methods[(size_t)i * s.nd + d];
     *bytes += s.cells * (sizeof(T) + (b.st_in[nb] ? 4 : 0));  // each cube, once
-    ++nb;
+    if (++nb == (unsigned)kTotalsBatch) {
+      const hipError_t e = flush();
+      if (e != hipSuccess) return e;
+    }
   }
-  if (!nb) return hipSuccess;
-  const size_t lds = (size_t)((s.ext * sizeof(T) + 15) & ~(uint64_t)15) + (size_t)s.ext;
-  static PerDeviceFlag raised;  // (per cell type, per device)
-  if (lds > 48 * 1024 && !raised.test_and_set()) {
-    const hipError_t e = hipFuncSetAttribute((const void *)totals_lds_batch_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(kLdsCells * (sizeof(T) + 1) + 16));
-    if (e != hipSuccess) return e;
+  return flush();
+}
+
+// The host checks olap_formula_totals and olap_totals_report share, after their own: the handles, the dimensions, the result
+// array, tracked inputs, the rules' range, the size limit (one extended cube when `slots` is 0, else `slots` of them), the inputs' sizes
+// and devices.  Fills *s but for method / def_nan, which are each input's own.  `what` names the inputs in the messages.
+int totals_inputs_shape(const char *what, int n_inputs, const olap_store *const *inputs, int ndim, const uint32_t *lens, const int *methods,
+                        const double *host_values, int slots, TotalsShape *s) {
+  for (int i = 0; i < n_inputs; ++i)
+    if (!inputs[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s input %d is NULL", what, i);
+  if (ndim < 0 || ndim > kTotalsMaxDims) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: at most %d dimensions", kTotalsMaxDims);
+  if (ndim > 0 && (!lens || !methods)) return fail(OLAP_ERR_INVALID_ARGUMENT, "lens/methods is NULL");
+  if (!host_values) return fail(OLAP_ERR_INVALID_ARGUMENT, "values is NULL");
+  for (int i = 0; i < n_inputs; ++i)
+    if (inputs[i]->track_order)  // (as olap_store_totals: every marginal has an insertion order of its own)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: %s input %d tracks its insertion order; run the chain of drillUps instead", what, i);
+  *s = TotalsShape{};
+  s->nd = ndim;
+  long double cells = 1, ext = 1;
+  for (int d = 0; d < ndim; ++d) {
+    for (int i = 0; i < n_inputs; ++i) {
+      const int m = methods[(size_t)i * ndim + d];
+      if (m < OLAP_SUM || m > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", m);
+    }
+    s->len[d] = lens[d];
+    cells *= lens[d];
+    ext *= (long double)lens[d] + 1;
   }
-  const unsigned threads = s.ext >= 4096 ? 1024 : 256;
-  hipLaunchKernelGGL((totals_lds_batch_kernel<T>), nb, threads, lds, nullptr, b, s);
-  ++*launches;
-  return hipGetLastError();
+  if (slots == 0 && ext > 4.0e9L) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: the extended cube would hold %.3Lg cells", ext);
+  if (ext * slots > 4.0e9L)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: the report would hold %.3Lg extended cells on the device; ask measure by measure", ext * slots);
+  s->cells = (uint64_t)cells;
+  s->ext = (uint64_t)ext;
+  for (int i = 0; i < n_inputs; ++i) {
+    if (inputs[i]->size != s->cells)
+      return fail(OLAP_ERR_LENGTH_MISMATCH, "%s input %d holds %llu cells but the dimensions describe %llu", what, i, (unsigned long long)inputs[i]->size,
+                  (unsigned long long)s->cells);
+    if (inputs[i]->device != inputs[0]->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s inputs live on different devices", what);
+  }
+  uint64_t pitch = 1;
+  for (int d = ndim - 1; d >= 0; --d) {
+    s->pitch[d] = pitch;
+    pitch *= (uint64_t)lens[d] + 1;
+  }
+  return OLAP_OK;
+}
+
+// Queues, on the one stream, what builds E of every input into dev_e[i] (float64, getValue in every cell): in LDS one launch
+// per cell type per kTotalsBatch inputs, otherwise each input's own pass plan, whose intermediate tensors join `held`.
+// Nothing is waited for.  A HIP error comes back in *e, a refusal of a pass plan as the return value.
+int queue_extended_cubes(int n_inputs, const olap_store *const *inputs, const int *methods, const TotalsShape &s, double *const *dev_e, int *launches,
+                         uint64_t *bytes, std::vector<void *> *held, hipError_t *e) {
+  if (s.ext <= kLdsCells) {
+    *e = totals_lds_batch<int32_t>(n_inputs, inputs, methods, s, dev_e, launches, bytes);
+    if (*e == hipSuccess) *e = totals_lds_batch<uint32_t>(n_inputs, inputs, methods, s, dev_e, launches, bytes);
+    if (*e == hipSuccess) *e = totals_lds_batch<float>(n_inputs, inputs, methods, s, dev_e, launches, bytes);
+    if (*e == hipSuccess) *e = totals_lds_batch<double>(n_inputs, inputs, methods, s, dev_e, launches, bytes);
+    return OLAP_OK;
+  }
+  int rc = OLAP_OK;
+  for (int i = 0; i < n_inputs && !rc; ++i) {
+    const olap_store *st = inputs[i];
+    TotalsShape si = s;
+    si.def_nan = st->default_kind == OLAP_DEFAULT_NAN;
+    for (int d = 0; d < s.nd; ++d) si.method[d] = methods[(size_t)i * s.nd + d];
+    int l = 0;
+    uint64_t b = 0;
+    DISPATCH_DTYPE(st->dtype, T, rc = totals_typed<T>(st, si, dev_e[i], nullptr, &l, &b, held));
+    *launches += l;
+    *bytes += b;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -760,46 +864,14 @@ extern "C" int olap_formula_totals(const int32_t *code, int n_code, const double
   if (rc) return rc;
   if (n_consts && !consts) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula constants are NULL");
   if (!inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs are NULL");
-  for (int i = 0; i < n_inputs; ++i)
-    if (!inputs[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is NULL", i);
-  if (ndim < 0 || ndim > kTotalsMaxDims) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: at most %d dimensions", kTotalsMaxDims);
-  if (ndim > 0 && (!lens || !methods)) return fail(OLAP_ERR_INVALID_ARGUMENT, "lens/methods is NULL");
-  if (!host_values) return fail(OLAP_ERR_INVALID_ARGUMENT, "values is NULL");
-  for (int i = 0; i < n_inputs; ++i)
-    if (inputs[i]->track_order)  // (as olap_store_totals: every marginal has an insertion order of its own)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: formula input %d tracks its insertion order; run the chain of drillUps instead", i);
-  TotalsShape s{};
-  s.nd = ndim;
-  long double cells = 1, ext = 1;
-  for (int d = 0; d < ndim; ++d) {
-    for (int i = 0; i < n_inputs; ++i) {
-      const int m = methods[(size_t)i * ndim + d];
-      if (m < OLAP_SUM || m > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", m);
-    }
-    s.len[d] = lens[d];
-    cells *= lens[d];
-    ext *= (long double)lens[d] + 1;
-  }
-  if (ext > 4.0e9L) return fail(OLAP_ERR_INVALID_ARGUMENT, "totals: the extended cube would hold %.3Lg cells", ext);
-  s.cells = (uint64_t)cells;
-  s.ext = (uint64_t)ext;
-  for (int i = 0; i < n_inputs; ++i) {
-    if (inputs[i]->size != s.cells)
-      return fail(OLAP_ERR_LENGTH_MISMATCH, "formula input %d holds %llu cells but the dimensions describe %llu", i, (unsigned long long)inputs[i]->size,
-                  (unsigned long long)s.cells);
-    if (inputs[i]->device != inputs[0]->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula inputs live on different devices");
-  }
-  uint64_t pitch = 1;
-  for (int d = ndim - 1; d >= 0; --d) {
-    s.pitch[d] = pitch;
-    pitch *= (uint64_t)lens[d] + 1;
-  }
+  TotalsShape s;
+  if ((rc = totals_inputs_shape("formula", n_inputs, inputs, ndim, lens, methods, host_values, 0, &s))) return rc;
   if ((rc = require_device())) return rc;
   DeviceGuard guard;
   HIP_TRY(hipSetDevice(inputs[0]->device));
 
   // ---- E_0 .. E_{n-1} and the result, float64, all on the device
-  std::vector<void *> held;  // freed after the one synchronisation (the copy to the host)
+  std::vector<void *> held;  // freed after the one wait for device work (the copy to the host)
   double *dev_e[OLAP_FORMULA_MAX_INPUTS] = {};
   double *dev_out = nullptr;
   hipError_t e = dev_alloc((void **)&dev_out, s.ext * sizeof(double));
@@ -811,24 +883,7 @@ extern "C" int olap_formula_totals(const int32_t *code, int n_code, const double
   int n_launch = 0;
   uint64_t bytes = 0;
   rc = OLAP_OK;
-  if (e == hipSuccess && s.ext <= kLdsCells) {
-    e = totals_lds_batch<int32_t>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
-    if (e == hipSuccess) e = totals_lds_batch<uint32_t>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
-    if (e == hipSuccess) e = totals_lds_batch<float>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
-    if (e == hipSuccess) e = totals_lds_batch<double>(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes);
-  } else if (e == hipSuccess) {
-    for (int i = 0; i < n_inputs && !rc; ++i) {  // each input's own pass plan, queued on the one stream
-      const olap_store *st = inputs[i];
-      TotalsShape si = s;
-      si.def_nan = st->default_kind == OLAP_DEFAULT_NAN;
-      for (int d = 0; d < ndim; ++d) si.method[d] = methods[(size_t)i * ndim + d];
-      int l = 0;
-      uint64_t b = 0;
-      DISPATCH_DTYPE(st->dtype, T, rc = totals_typed<T>(st, si, dev_e[i], nullptr, &l, &b, &held));
-      n_launch += l;
-      bytes += b;
-    }
-  }
+  if (e == hipSuccess) rc = queue_extended_cubes(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes, &held, &e);
   if (e == hipSuccess && !rc) {
     static thread_local FormulaProgram p;
     memset(&p, 0, sizeof p);
@@ -846,13 +901,154 @@ extern "C" int olap_formula_totals(const int32_t *code, int n_code, const double
     ++n_launch;
     bytes += (uint64_t)n_inputs * s.ext * sizeof(double);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(host_values, dev_out, s.ext * sizeof(double), hipMemcpyDeviceToHost);  // the one synchronisation
-  } else {
-    (void)hipStreamSynchronize(nullptr);  // whatever was queued has finished before its buffers go back to the pool
+    if (e == hipSuccess) e = hipMemcpy(host_values, dev_out, s.ext * sizeof(double), hipMemcpyDeviceToHost);  // the one wait for device work
   }
+  if (e != hipSuccess || rc) (void)hipStreamSynchronize(nullptr);  // whatever was queued has finished before its buffers go back to the pool
   for (void *q : held) dev_free(q);
   if (rc) return rc;
   if (e != hipSuccess) return hip_fail(e, "formula_totals");
+  if (launches) *launches = n_launch;
+  if (bytes_read) *bytes_read = bytes;
+  return OLAP_OK;
+}
+
+// ---- getNestedObjects(ids, withTotals): several stored and computed measures of one cube in one call ---------------------
+// The per-measure calls above rebuild an input's extended cube for every measure that reads it and pay a call, a copy and
+// a synchronisation each.  Here every distinct input is built once — straight into its slot of the output slab when it is
+// an output itself, into scratch when only formulas read it — one launch evaluates all formulas, and one copy hands the
+// slab to the host: the call's only wait for device work.
+namespace {
+
+// check_formula's refusal, its message prefixed with the output's number
+int fail_output(int rc, int k) {
+  char msg[512];
+  strncpy(msg, olap_last_error(), sizeof msg - 1);
+  msg[sizeof msg - 1] = 0;
+  return fail(rc, "output %d: %s", k, msg);
+}
+
+}  // namespace
+
+extern "C" int olap_totals_report(int n_inputs, const olap_store *const *inputs, int ndim, const uint32_t *lens, const int *methods, int n_outputs,
+                                  const int *out_stored, const int *out_n_code, const int32_t *code, const int *out_n_consts, const double *consts,
+                                  const int *out_n_inputs, const int *formula_inputs, double *host_values, int *launches, uint64_t *bytes_read) {
+  // ---- the host checks, before any HIP call
+  if (n_inputs < 1 || n_inputs > OLAP_REPORT_MAX_INPUTS)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "a totals report needs 1..%d stored measures, got %d", OLAP_REPORT_MAX_INPUTS, n_inputs);
+  if (n_outputs < 1 || n_outputs > OLAP_REPORT_MAX_OUTPUTS)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "a totals report needs 1..%d outputs, got %d", OLAP_REPORT_MAX_OUTPUTS, n_outputs);
+  if (!inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "report inputs are NULL");
+  if (!out_stored || !out_n_code || !out_n_consts || !out_n_inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "report output tables are NULL");
+  // the outputs first: nothing here looks into a store
+  int slot_of[OLAP_REPORT_MAX_INPUTS];  // the output that exports input i, or -1
+  bool used[OLAP_REPORT_MAX_INPUTS];
+  for (int i = 0; i < n_inputs; ++i) slot_of[i] = -1, used[i] = false;
+  size_t code_at[OLAP_REPORT_MAX_OUTPUTS], consts_at[OLAP_REPORT_MAX_OUTPUTS], inputs_at[OLAP_REPORT_MAX_OUTPUTS];
+  size_t n_code_all = 0, n_consts_all = 0, n_fin_all = 0;
+  int n_formulas = 0;
+  for (int k = 0; k < n_outputs; ++k) {
+    code_at[k] = n_code_all, consts_at[k] = n_consts_all, inputs_at[k] = n_fin_all;
+    const int i = out_stored[k];
+    if (i >= 0) {
+      if (i >= n_inputs) return fail(OLAP_ERR_INDEX_RANGE, "output %d: input %d out of range", k, i);
+      if (out_n_code[k] || out_n_consts[k] || out_n_inputs[k]) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: a stored output carries no program", k);
+      if (slot_of[i] >= 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: input %d is output %d already", k, i, slot_of[i]);
+      slot_of[i] = k;
+      used[i] = true;
+      continue;
+    }
+    if (i != -1) return fail(OLAP_ERR_INDEX_RANGE, "output %d: input %d out of range", k, i);
+    const int nc = out_n_code[k], nk = out_n_consts[k], ni = out_n_inputs[k];
+    if (ni < 1 || ni > OLAP_FORMULA_MAX_INPUTS)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: a formula with totals needs 1..%d stored measures, got %d", k, OLAP_FORMULA_MAX_INPUTS, ni);
+    if (!code) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: formula programs are NULL", k);
+    const int32_t *c = code + n_code_all;
+    if (nc > 0 && nc <= OLAP_FORMULA_MAX_CODE)
+      for (int pc = 0; pc < nc; ++pc) {
+        if (c[pc] == F_SCALAR) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: a formula with totals cannot read a measure total (SCALAR)", k);
+        if (c[pc] == F_CONST || c[pc] == F_INPUT) ++pc;
+      }
+    const int rc = check_formula(c, nc, nk, ni, 0);
+    if (rc) return fail_output(rc, k);
+    if (nk && !consts) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: formula constants are NULL", k);
+    if (!formula_inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: formula inputs are NULL", k);
+    for (int j = 0; j < ni; ++j) {
+      const int in = formula_inputs[n_fin_all + j];
+      if (in < 0 || in >= n_inputs) return fail(OLAP_ERR_INDEX_RANGE, "output %d: input %d out of range", k, in);
+      for (int j2 = 0; j2 < j; ++j2)
+        if (formula_inputs[n_fin_all + j2] == in) return fail(OLAP_ERR_INVALID_ARGUMENT, "output %d: input %d is named twice", k, in);
+      used[in] = true;
+    }
+    n_code_all += nc, n_consts_all += nk, n_fin_all += ni;
+    ++n_formulas;
+  }
+  for (int i = 0; i < n_inputs; ++i)
+    if (!used[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "report input %d is used by no output", i);
+  int n_scratch = 0;  // inputs that only formulas read
+  for (int i = 0; i < n_inputs; ++i) n_scratch += slot_of[i] < 0;
+  TotalsShape s;
+  int rc = totals_inputs_shape("report", n_inputs, inputs, ndim, lens, methods, host_values, n_outputs + n_scratch, &s);
+  if (rc) return rc;
+  if ((rc = require_device())) return rc;
+  DeviceGuard guard;
+  HIP_TRY(hipSetDevice(inputs[0]->device));
+
+  // ---- one allocation: the output slab (slot k at k * ext, packed: what the host receives), then the scratch cubes
+  std::vector<void *> held;  // freed after the one wait for device work (the copy to the host)
+  double *slab = nullptr;
+  hipError_t e = dev_alloc((void **)&slab, (size_t)(n_outputs + n_scratch) * s.ext * sizeof(double));
+  if (e == hipSuccess) held.push_back(slab);
+  double *dev_e[OLAP_REPORT_MAX_INPUTS] = {};
+  if (e == hipSuccess) {
+    int next = n_outputs;
+    for (int i = 0; i < n_inputs; ++i) dev_e[i] = slab + (size_t)(slot_of[i] >= 0 ? slot_of[i] : next++) * s.ext;
+  }
+  // the formulas' programs go up first, while the stream is idle: a blocking copy, but it waits for no device work
+  ReportFormula *dev_formulas = nullptr;
+  uint64_t formula_bytes = 0;
+  if (e == hipSuccess && n_formulas) {
+    std::vector<ReportFormula> host(n_formulas);
+    memset(host.data(), 0, host.size() * sizeof(ReportFormula));
+    int f = 0;
+    for (int k = 0; k < n_outputs; ++k) {
+      if (out_stored[k] >= 0) continue;
+      FormulaProgram &p = host[f].prog;
+      p.n_code = out_n_code[k];
+      memcpy(p.code, code + code_at[k], (size_t)p.n_code * sizeof(int32_t));
+      if (out_n_consts[k]) memcpy(p.consts, consts + consts_at[k], (size_t)out_n_consts[k] * sizeof(double));
+      p.n_inputs = out_n_inputs[k];
+      for (int j = 0; j < p.n_inputs; ++j) {  // E_i holds getValue: the default where unset, no mask to consult
+        const int in = formula_inputs[inputs_at[k] + j];
+        p.in_values[j] = dev_e[in];
+        p.in_status[j] = nullptr;
+        p.in_dtype[j] = OLAP_FLOAT64;
+        p.in_def_nan[j] = inputs[in]->default_kind == OLAP_DEFAULT_NAN;
+      }
+      host[f].out = slab + (size_t)k * s.ext;
+      formula_bytes += (uint64_t)p.n_inputs * s.ext * sizeof(double);
+      ++f;
+    }
+    e = dev_alloc((void **)&dev_formulas, host.size() * sizeof(ReportFormula));
+    if (e == hipSuccess) {
+      held.push_back(dev_formulas);
+      e = hipMemcpy(dev_formulas, host.data(), host.size() * sizeof(ReportFormula), hipMemcpyHostToDevice);
+    }
+  }
+  int n_launch = 0;
+  uint64_t bytes = 0;
+  if (e == hipSuccess) rc = queue_extended_cubes(n_inputs, inputs, methods, s, dev_e, &n_launch, &bytes, &held, &e);
+  if (e == hipSuccess && !rc && n_formulas) {
+    hipLaunchKernelGGL(formula_report_eval_kernel, dim3(stride_grid((s.ext + 1) / 2), (unsigned)n_formulas), dim3(kBlock), 0, nullptr, dev_formulas, s.ext);
+    ++n_launch;
+    bytes += formula_bytes;
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess && !rc)
+    e = hipMemcpy(host_values, slab, (size_t)n_outputs * s.ext * sizeof(double), hipMemcpyDeviceToHost);  // the one wait for device work
+  if (e != hipSuccess || rc) (void)hipStreamSynchronize(nullptr);  // whatever was queued has finished before its buffers go back to the pool
+  for (void *q : held) dev_free(q);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(e, "totals_report");
   if (launches) *launches = n_launch;
   if (bytes_read) *bytes_read = bytes;
   return OLAP_OK;

@@ -78,6 +78,39 @@ def formula_totals(code, consts, inputs, lens, methods):
     return vals, launches.value, nbytes.value
 
 
+def totals_report(inputs, lens, methods, outputs):
+    """getNestedObjects(ids, withTotals) (olap_totals_report): the extended cubes of several measures in one call.
+    `inputs` are the distinct stores, `methods[i]` lists input i's rule per dimension; an entry of `outputs` is either an
+    int (the extended cube of that input) or (code, consts, input indices) — a formula whose INPUT operand j reads
+    inputs[indices[j]].  Returns (float64 array [len(outputs), extended cells], launches, bytes read)."""
+    lv = _u32(lens)
+    flat = [_method_code(m) for per_input in methods for m in per_input]
+    if len(flat) != len(inputs) * len(lv):
+        raise ValueError("totals_report: one rule per input and dimension")
+    m = (C.c_int * max(len(flat), 1))(*flat)
+    table = (C.c_void_p * max(len(inputs), 1))(*[s._h.value if s is not None else None for s in inputs])
+    stored, n_code, n_consts, n_in, code, consts, picks = [], [], [], [], [], [], []
+    for out in outputs:
+        if isinstance(out, (int, np.integer)):
+            stored.append(int(out))
+            n_code.append(0), n_consts.append(0), n_in.append(0)
+            continue
+        c, k, idx = out
+        stored.append(-1)
+        n_code.append(len(c)), n_consts.append(len(k)), n_in.append(len(idx))
+        code.extend(int(x) for x in c), consts.extend(float(x) for x in k), picks.extend(int(x) for x in idx)
+    ints = lambda a: (C.c_int * max(len(a), 1))(*a)
+    code_a = np.ascontiguousarray(code if code else [0], dtype=np.int32)
+    consts_a = np.ascontiguousarray(consts if consts else [0.0], dtype=np.float64)
+    ext = int(np.prod([int(l) + 1 for l in lv])) if len(lv) else 1
+    vals = np.zeros((len(outputs), ext), np.float64)
+    launches, nbytes = C.c_int(), C.c_uint64()
+    check(capi.lib().olap_totals_report(len(inputs), table, len(lv), lv.ctypes.data_as(capi._pu32), m, len(outputs), ints(stored), ints(n_code),
+                                         code_a.ctypes.data_as(capi._pi32), ints(n_consts), consts_a.ctypes.data_as(capi._pdbl), ints(n_in),
+                                         ints(picks), vals.ctypes.data_as(capi._pdbl), C.byref(launches), C.byref(nbytes)))
+    return vals, launches.value, nbytes.value
+
+
 def _entries(indexes, values):
     """(n, indexes, values, is_null or None) pointers of a set_values list (each keeps its array alive); None in `values`
     means unset"""

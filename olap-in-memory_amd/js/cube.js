@@ -328,28 +328,42 @@ class Cube {
     // (a measure that tracks its insertion order takes the chain too: every marginal has an order of its own)
     const direct = (id) => this.storedMeasures[id] !== undefined && !this.storedMeasures[id].orderTracked;
     const extended = this.dimensions.map((d) => ({ getItems: () => d.getItems().concat(['all']) }));
-    const found = {};
+    const rulesOf = (id) => {
+      const rules = this.storedMeasuresRules[id] || {};
+      return this.dimensions.map((d) => rules[d.id]);
+    };
+    // A computed measure over stored measures: marginal s of input X is the sub-lattice s of X's extended cube, and
+    // the measure on marginal s is the formula applied cell by cell to its inputs there — so its extended cube is the
+    // formula over the inputs' extended cubes, built and evaluated on the device (olap_formula_totals).
+    const eligible = []; // the ids the device answers, each once: { id, store } | { id, formula }
     const others = [];
     for (const id of measureIds) {
+      if (eligible.some((e) => e.id === id) || others.includes(id)) continue;
       if (direct(id)) {
-        const rules = this.storedMeasuresRules[id] || {};
-        found[id] = toNestedObject(this.storedMeasures[id].totals(this.dimensions, this.dimensions.map((d) => rules[d.id])), extended);
+        eligible.push({ id, store: this.storedMeasures[id] });
         continue;
       }
-      // A computed measure over stored measures: marginal s of input X is the sub-lattice s of X's extended cube, and
-      // the measure on marginal s is the formula applied cell by cell to its inputs there — so its extended cube is the
-      // formula over the inputs' extended cubes, built and evaluated on the device in one call (olap_formula_totals).
       const formula = this._totalsFormula(id);
-      if (formula === null) {
-        others.push(id);
-        continue;
-      }
-      const rulesPerInput = formula.ids.map((input) => {
-        const rules = this.storedMeasuresRules[input] || {};
-        return this.dimensions.map((d) => rules[d.id]);
-      });
-      found[id] = toNestedObject(HipStore.totalsFormula(formula.program, formula.stores, this.dimensions, rulesPerInput), extended);
+      if (formula === null) others.push(id);
+      else eligible.push({ id, formula });
     }
+    const found = {};
+    // Two or more of them leave in ONE device call (olap_totals_report): every distinct stored measure's extended cube
+    // is built once, all formulas are evaluated by one launch, one copy comes back.  null: too large for one call.
+    let slots = null;
+    if (eligible.length >= 2 && eligible.every((e) => (e.store ? [e.store] : e.formula.stores).every((store) => store instanceof HipStore)) && HipStore.canReport()) {
+      slots = HipStore.totalsReport(eligible.map((e) => (e.store
+        ? { store: e.store, rules: rulesOf(e.id) }
+        : { program: e.formula.program, stores: e.formula.stores, rulesPerInput: e.formula.ids.map(rulesOf) })), this.dimensions);
+    }
+    eligible.forEach((e, k) => {
+      let flat;
+      if (slots !== null) flat = slots[k];
+      else if (e.store) flat = e.store.totals(this.dimensions, rulesOf(e.id));
+      else flat = HipStore.totalsFormula(e.formula.program, e.formula.stores, this.dimensions, e.formula.ids.map(rulesOf));
+      found[e.id] = toNestedObject(flat, extended);
+    });
+    HipStore.lastTotalsCalls = slots !== null ? 1 : eligible.length;
     // tracked stored measures, formulas that read `<id>__total`, constants only or more than 8 measures: the chain
     const chained = others.length ? this._getNestedObjectsChain(others) : {};
     const result = {};

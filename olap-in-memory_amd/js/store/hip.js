@@ -500,6 +500,69 @@ class HipStore {
     return values;
   }
 
+  /** Whether the loaded addon answers several measures' totals in one call (HipStore.totalsReport). */
+  static canReport() {
+    return typeof backend.load().totalsReport === 'function';
+  }
+
+  /**
+   * getNestedObjects(ids, withTotals): the extended cubes of several measures of one cube in ONE device call
+   * (olap_totals_report).  An entry of `outputs` is { store, rules } — a stored measure with its rule per dimension (names,
+   * as totals() takes them) — or { program, stores, rulesPerInput } — a computed one, as totalsFormula() takes it.  Every
+   * distinct store is built once, whatever number of outputs reads it.  Returns one Float64Array per output (views of
+   * one buffer), or null when the report would not fit the device call's limits (32 outputs over 32 distinct stores, 4e9
+   * float64 cells on the device): the caller asks measure by measure.
+   * Pending inputs are materialised and sharded ones gathered, as totals() and totalsFormula() do.
+   */
+  static totalsReport(outputs, dimensions) {
+    const addon = backend.load();
+    const nd = dimensions.length;
+    const lens = lengthsOf(dimensions);
+    const stores = []; // the distinct inputs, in order of first use
+    const rulesOf = [];
+    const inputOf = (store, rules) => {
+      let i = stores.indexOf(store);
+      if (i < 0) {
+        i = stores.push(store) - 1;
+        rulesOf.push(rules);
+      }
+      return i;
+    };
+    const n = outputs.length;
+    const outStored = new Int32Array(n).fill(-1);
+    const nCode = new Int32Array(n);
+    const nConsts = new Int32Array(n);
+    const nInputs = new Int32Array(n);
+    const code = [];
+    const consts = [];
+    const picks = [];
+    outputs.forEach((out, k) => {
+      if (out.program === undefined) {
+        outStored[k] = inputOf(out.store, out.rules);
+        return;
+      }
+      nCode[k] = out.program.code.length;
+      nConsts[k] = out.program.consts.length;
+      nInputs[k] = out.stores.length;
+      for (const word of out.program.code) code.push(word);
+      for (const c of out.program.consts) consts.push(c);
+      out.stores.forEach((store, j) => picks.push(inputOf(store, out.rulesPerInput[j])));
+    });
+    const codes = new Int32Array(stores.length * nd);
+    for (let i = 0; i < stores.length; ++i) for (let d = 0; d < nd; ++d) codes[i * nd + d] = addon.methodFromName(rulesOf[i][d]); // throws 'Unsupported aggregation method: <m>'
+    let ext = 1;
+    for (let d = 0; d < nd; ++d) ext *= lens[d] + 1;
+    const exported = new Set(outStored.filter((i) => i >= 0)).size;
+    if (n > 32 || stores.length > 32 || (stores.length - exported + n) * ext > 4.0e9) return null; // OLAP_REPORT_MAX_OUTPUTS / _INPUTS, the cell limit
+    const launchesOut = new Int32Array(1);
+    const natives = stores.map((store) => store._whole);
+    const values = addon.totalsReport(natives, lens, codes, outStored, nCode, Int32Array.from(code), nConsts, Float64Array.from(consts), nInputs,
+      Int32Array.from(picks), launchesOut);
+    HipStore.lastTotalsLaunches = launchesOut[0];
+    if (picks.length > 0) HipStore.lastTotalsPath = 'device';
+    return outputs.map((_, k) => values.subarray(k * ext, (k + 1) * ext));
+  }
+
   /**
    * copyMeasureData from a computed measure: this.setValue(pos, formula(pos)) over a selection of distinct cells
    * (./selection.js copyLevels) in one launch.  This store may be one of `inputs`.  Returns false for a sharded
@@ -568,6 +631,9 @@ HipStore.lastSelectPath = null;
 // launches it reported; never reset here
 HipStore.lastTotalsPath = null;
 HipStore.lastTotalsLaunches = null;
+// the device calls the last Cube.getNestedObjects(ids, withTotals) made for the ids that did not take the chain of
+// drillUps: 1 when they left in one report (HipStore.totalsReport), one per measure otherwise; written by Cube
+HipStore.lastTotalsCalls = null;
 // 'device' after a copyMeasureData that ran as one device scatter (copySelect / copySelectFormula); never reset here
 HipStore.lastCopyPath = null;
 

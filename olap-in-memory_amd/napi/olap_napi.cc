@@ -440,10 +440,11 @@ static napi_value StoreClone(napi_env env, napi_callback_info info) {
   return wrap_new_store(env, c);
 }
 
-// totals(lens: Uint32Array, methods: Int32Array) -> Float64Array of the extended cube (olap_store_totals)
+// totals(lens: Uint32Array, methods: Int32Array, launchesOut?: Int32Array) -> Float64Array of the extended cube (olap_store_totals)
 static bool get_u32_vec(napi_env env, napi_value v, std::vector<uint32_t> &out);
+static void set_path(napi_env env, napi_value out, int path);
 static napi_value StoreTotals(napi_env env, napi_callback_info info) {
-  STORE_METHOD_PROLOGUE(2)
+  STORE_METHOD_PROLOGUE(3)
   std::vector<uint32_t> lens, methods;
   if (argc < 2 || !get_u32_vec(env, argv[0], lens) || !get_u32_vec(env, argv[1], methods) || lens.size() != methods.size()) {
     napi_throw_type_error(env, nullptr, "totals(lens: Uint32Array, methods: Int32Array)");
@@ -459,9 +460,11 @@ static napi_value StoreTotals(napi_env env, napi_callback_info info) {
   napi_value ta = make_ta(env, napi_float64_array, 8, (size_t)n, &data);
   if (!ta) return nullptr;
   static const uint32_t none = 0;
+  int launches = 0;
   int rc = olap_store_totals(s, (int)lens.size(), lens.empty() ? &none : lens.data(), lens.empty() ? (const int *)&none : (const int *)methods.data(),
-                             (double *)data, nullptr, nullptr, nullptr);
+                             (double *)data, nullptr, &launches, nullptr);
   if (rc) return throw_olap(env, rc);
+  if (argc > 2) set_path(env, argv[2], launches);
   return ta;
 }
 
@@ -857,6 +860,77 @@ static napi_value TotalsFormula(napi_env env, napi_callback_info info) {
                                (double *)data, &launches, nullptr);
   if (rc) return throw_olap(env, rc);
   if (argc > 5) set_path(env, argv[5], launches);
+  return ta;
+}
+
+// totalsReport(stores: Store[], lens: Uint32Array, methods: Int32Array /* stores.length * lens.length */, outStored: Int32Array,
+//              nCode: Int32Array, code: Int32Array, nConsts: Int32Array, consts: Float64Array, nInputs: Int32Array,
+//              formulaInputs: Int32Array, launchesOut?: Int32Array)
+//   -> Float64Array of outStored.length extended cubes, one after the other (olap_totals_report; the flat arrays as there)
+static napi_value TotalsReport(napi_env env, napi_callback_info info) {
+  size_t argc = 11;
+  napi_value argv[11];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  const char *usage =
+      "totalsReport(stores: Store[], lens: Uint32Array, methods: Int32Array, outStored: Int32Array, nCode: Int32Array, code: Int32Array, "
+      "nConsts: Int32Array, consts: Float64Array, nInputs: Int32Array, formulaInputs: Int32Array)";
+  if (argc < 10) return bad_args(env, usage);
+  bool is_arr = false;
+  napi_is_array(env, argv[0], &is_arr);
+  if (!is_arr) return bad_args(env, usage);
+  uint32_t n_stores = 0;
+  napi_get_array_length(env, argv[0], &n_stores);
+  std::vector<const olap_store *> stores(n_stores);
+  for (uint32_t i = 0; i < n_stores; ++i) {
+    napi_value e;
+    NAPI_OK(napi_get_element(env, argv[0], i, &e));
+    stores[i] = unwrap(env, e);
+    if (!stores[i]) return nullptr;
+  }
+  std::vector<uint32_t> lens, methods, out_stored, n_code, code, n_consts, n_inputs, formula_inputs;
+  napi_typedarray_type t;
+  size_t consts_len = 0;
+  void *consts = nullptr;
+  if (!get_u32_vec(env, argv[1], lens) || !get_u32_vec(env, argv[2], methods) || !get_u32_vec(env, argv[3], out_stored) ||
+      !get_u32_vec(env, argv[4], n_code) || !get_u32_vec(env, argv[5], code) || !get_u32_vec(env, argv[6], n_consts) ||
+      napi_get_typedarray_info(env, argv[7], &t, &consts_len, &consts, nullptr, nullptr) != napi_ok || t != napi_float64_array ||
+      !get_u32_vec(env, argv[8], n_inputs) || !get_u32_vec(env, argv[9], formula_inputs))
+    return bad_args(env, usage);
+  const size_t n_out = out_stored.size();
+  if (methods.size() != stores.size() * lens.size() || n_code.size() != n_out || n_consts.size() != n_out || n_inputs.size() != n_out) return bad_args(env, usage);
+  // the programs lie one after the other: the flat arrays must hold what the counts announce
+  uint64_t words = 0, constants = 0, picks = 0;
+  for (size_t k = 0; k < n_out; ++k) {
+    if ((int32_t)n_code[k] < 0 || (int32_t)n_consts[k] < 0 || (int32_t)n_inputs[k] < 0) return bad_args(env, usage);
+    words += n_code[k], constants += n_consts[k], picks += n_inputs[k];
+  }
+  if (words > code.size() || constants > consts_len || picks > formula_inputs.size()) return bad_args(env, usage);
+  // the size limit of olap_totals_report, before the result is allocated: the outputs and the stores no output exports
+  std::vector<bool> exported(stores.size(), false);
+  for (uint32_t i : out_stored)
+    if (i < stores.size()) exported[i] = true;
+  size_t scratch = 0;
+  for (bool x : exported) scratch += !x;
+  double ext = 1;
+  for (uint32_t l : lens) ext *= (double)l + 1;
+  const double n = (double)n_out * ext;
+  if ((double)(n_out + scratch) * ext > 4.0e9) {
+    napi_throw_range_error(env, nullptr, "totals: extended cube too large");
+    return nullptr;
+  }
+  void *data;
+  napi_value ta = make_ta(env, napi_float64_array, 8, (size_t)n, &data);
+  if (!ta) return nullptr;
+  static const uint32_t none = 0;
+  static const double zero = 0;
+  int launches = 0;
+  int rc = olap_totals_report((int)stores.size(), stores.data(), (int)lens.size(), lens.empty() ? &none : lens.data(),
+                              methods.empty() ? (const int *)&none : (const int *)methods.data(), (int)n_out, (const int *)out_stored.data(),
+                              (const int *)n_code.data(), code.empty() ? (const int32_t *)&none : (const int32_t *)code.data(), (const int *)n_consts.data(),
+                              consts ? (const double *)consts : &zero, (const int *)n_inputs.data(),
+                              formula_inputs.empty() ? (const int *)&none : (const int *)formula_inputs.data(), (double *)data, &launches, nullptr);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 10) set_path(env, argv[10], launches);
   return ta;
 }
 
@@ -1478,6 +1552,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"evalFormula", nullptr, EvalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"selectTotalFormula", nullptr, SelectTotalFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"totalsFormula", nullptr, TotalsFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"totalsReport", nullptr, TotalsReport, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillUpMulti", nullptr, DrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
