@@ -412,6 +412,14 @@ int olap_store_eval_formula(const int32_t *code, int n_code, const double *const
                             const olap_store *const *inputs, const double *scalars, int n_scalars,
                             double *host_out);
 
+/* olap_store_set_data_f64(target, olap_store_eval_formula(...)) without the host: the program is evaluated at every cell
+ * and written into `target` as typed cells (and its mask, where the store keeps one) by one launch — the same bits, and a
+ * tracked target ends with the same key order.  Refused before any device work: the program checks of olap_eval_formula,
+ * n_inputs < 1 or a NULL input, inputs of another size than the target (OLAP_ERR_LENGTH_MISMATCH), a target that is one of
+ * the inputs, inputs on another device than the target.  A target of 0 cells is left alone. */
+int olap_store_set_formula(olap_store *target, const int32_t *code, int n_code, const double *consts, int n_consts,
+                           int n_inputs, const olap_store *const *inputs, const double *scalars, int n_scalars);
+
 /* The five bulk operations; each returns a NEW store (load mutates `store`). */
 int olap_store_drillup(const olap_store *store, olap_store **out, int ndim, const uint32_t *old_len,
                        const uint32_t *new_len, const uint32_t *const *maps, int method);
@@ -593,6 +601,11 @@ int olap_sharded_store_clone(const olap_sharded_store *store, olap_sharded_store
 int olap_sharded_store_eval_formula(const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
                                     const olap_sharded_store *const *inputs, const double *scalars, int n_scalars,
                                     double *host_out);
+/* olap_store_set_formula over a sharded target and sharded inputs, one launch per shard on the shard's device; the
+ * scalars are the same for every shard.  Target and inputs must be partitioned alike: anything else answers "sharded: …" */
+int olap_sharded_store_set_formula(olap_sharded_store *target, const int32_t *code, int n_code, const double *consts,
+                                   int n_consts, int n_inputs, const olap_sharded_store *const *inputs,
+                                   const double *scalars, int n_scalars);
 /* whole measure on the device of local rank 0 as an ordinary store, and back (one-process
  * communicators: device-to-device copies; one process per GPU: RCCL broadcasts of the slabs) */
 int olap_sharded_store_gather(const olap_sharded_store *store, olap_store **out);

@@ -73,6 +73,7 @@ SIGNATURES = {
     "olap_average_finish": (_i32, [_vp, _vp, _vp, _u64, _i32, _i32, _vp]),
     "olap_eval_formula": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _pvp, C.POINTER(C.c_int), C.POINTER(C.c_int), _pdbl, _i32, _vp, _u64, _vp]),
     "olap_store_eval_formula": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _pdbl, _i32, _pdbl]),
+    "olap_store_set_formula": (_i32, [_vp, _pi32, _i32, _pdbl, _i32, _i32, _pvp, _pdbl, _i32]),
     "olap_total": (_i32, [_vp, _vp, _u64, _i32, _i32, _pdbl, _pu64, _vp]),
     "olap_store_create": (_i32, [_pvp, _u64, _i32, _i32]),
     "olap_store_destroy": (None, [_vp]),
@@ -165,6 +166,7 @@ SIGNATURES = {
     "olap_sharded_store_fill": (_i32, [_vp, _dbl]),
     "olap_sharded_store_total": (_i32, [_vp, _pdbl]),
     "olap_sharded_store_eval_formula": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _pdbl, _i32, _pdbl]),
+    "olap_sharded_store_set_formula": (_i32, [_vp, _pi32, _i32, _pdbl, _i32, _i32, _pvp, _pdbl, _i32]),
     "olap_sharded_store_clone": (_i32, [_vp, _pvp]),
     "olap_sharded_store_gather": (_i32, [_vp, _pvp]),
     "olap_sharded_store_scatter": (_i32, [_pvp, _vp, _vp, _i32, _pu32]),

@@ -2087,12 +2087,12 @@ extern "C" int olap_diag_read_ceiling(const void *device, uint64_t bytes, void *
 }
 
 // ---- computed measures --------------------------------------------------------------------------
-int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars) {
+int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars, int *max_depth) {
   if (!code || n_code <= 0 || n_code > OLAP_FORMULA_MAX_CODE) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula program has %d words (1..%d allowed)", n_code, OLAP_FORMULA_MAX_CODE);
   if (n_consts < 0 || n_consts > OLAP_FORMULA_MAX_CONSTS || n_inputs < 0 || n_inputs > OLAP_FORMULA_MAX_INPUTS || n_scalars < 0 ||
       n_scalars > OLAP_FORMULA_MAX_INPUTS)
     return fail(OLAP_ERR_INVALID_ARGUMENT, "formula uses too many constants / measures / totals");
-  int depth = 0;
+  int depth = 0, deepest = 0;
   for (int pc = 0; pc < n_code; ++pc) {
     const int op = code[pc];
     if (op == F_CONST || op == F_INPUT || op == F_SCALAR) {
@@ -2113,8 +2113,10 @@ int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, i
       return fail(OLAP_ERR_INVALID_ARGUMENT, "unknown formula opcode %d", op);
     }
     if (depth > OLAP_FORMULA_MAX_STACK) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula needs a stack deeper than %d", OLAP_FORMULA_MAX_STACK);
+    if (depth > deepest) deepest = depth;
   }
   if (depth != 1) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula program leaves %d values on its stack", depth);
+  if (max_depth) *max_depth = deepest;
   return OLAP_OK;
 }
 
@@ -2575,6 +2577,83 @@ extern "C" int olap_store_eval_formula(const int32_t *code, int n_code, const do
   dev_free(dev);
   if (rc) return rc;
   if (e != hipSuccess) return hip_fail(e, "store_eval_formula");
+  return OLAP_OK;
+}
+
+// The formula written straight into a store: olap_store_set_data_f64(target, olap_store_eval_formula(...)) as one launch.
+// The kernel's stack is a column of LDS per lane sized by the program's real depth, and programs of plain opcodes run
+// the instantiation without the library routines (NOTEBOOK.md, "formula_store_kernel").
+template <typename T, bool HAS_STATUS, bool ALL>
+static hipError_t launch_formula_store_as(int depth, const FormulaProgram &p, void *values, int32_t *status, uint64_t n, int def_nan) {
+  constexpr uint64_t W = 16 / sizeof(T);
+  const size_t lds = formula_store_lds(depth, sizeof(T));
+  if (lds > 48 * 1024) {
+    static PerDeviceFlag raised;  // (per instantiation, per device)
+    static std::mutex raising;    // (the shard workers of one process may come here together)
+    std::lock_guard<std::mutex> lock(raising);
+    if (!raised.test_and_set()) {
+      const hipError_t e = hipFuncSetAttribute((const void *)formula_store_kernel<T, HAS_STATUS, ALL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)formula_store_lds(OLAP_FORMULA_MAX_STACK, sizeof(T)));
+      if (e != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL((formula_store_kernel<T, HAS_STATUS, ALL>), grid_stride_for((n + W - 1) / W), kBlock, lds, nullptr, p, (T *)values, status, n, def_nan);
+  return hipGetLastError();
+}
+template <typename T>
+static hipError_t launch_formula_store(bool plain, int depth, const FormulaProgram &p, void *values, int32_t *status, uint64_t n, int def_nan) {
+  if constexpr (sizeof(T) == 4 && !IsFloatCell<T>::value) {  // only integer cells (under a NaN default) keep a mask of their own
+    if (status) return plain ? launch_formula_store_as<T, true, false>(depth, p, values, status, n, def_nan) : launch_formula_store_as<T, true, true>(depth, p, values, status, n, def_nan);
+  }
+  return plain ? launch_formula_store_as<T, false, false>(depth, p, values, nullptr, n, def_nan) : launch_formula_store_as<T, false, true>(depth, p, values, nullptr, n, def_nan);
+}
+
+extern "C" int olap_store_set_formula(olap_store *target, const int32_t *code, int n_code, const double *consts, int n_consts, int n_inputs,
+                                      const olap_store *const *inputs, const double *scalars, int n_scalars) {
+  int depth = 0;
+  int rc = check_formula(code, n_code, n_consts, n_inputs, n_scalars, &depth);
+  if (rc) return rc;
+  if (!target) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (n_inputs < 1 || !inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula needs at least one stored measure to read");
+  if ((n_consts && !consts) || (n_scalars && !scalars)) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula argument arrays must not be NULL");
+  const uint64_t n = target->size;
+  for (int k = 0; k < n_inputs; ++k) {
+    if (!inputs[k]) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is NULL", k);
+    if (inputs[k]->size != n) return fail(OLAP_ERR_LENGTH_MISMATCH, "formula input %d holds %llu cells, the target %llu", k, (unsigned long long)inputs[k]->size, (unsigned long long)n);
+    if (inputs[k] == target) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is the target itself", k);  // (the kernel's loads are __restrict__)
+    if (inputs[k]->device != target->device) return fail(OLAP_ERR_INVALID_ARGUMENT, "the formula's inputs and the target live on different devices");
+  }
+  if (n == 0) return OLAP_OK;
+  OnStoreDevice on_device__(target);
+  if ((rc = require_device())) return rc;
+  static thread_local FormulaProgram p;
+  p.n_code = n_code;
+  memcpy(p.code, code, n_code * sizeof(int32_t));
+  if (n_consts) memcpy(p.consts, consts, n_consts * sizeof(double));
+  p.n_inputs = n_inputs;
+  bool aligned = ((uintptr_t)target->values & 15u) == 0 && (!mask_is_primary(target) || ((uintptr_t)target->status & 15u) == 0);
+  for (int k = 0; k < n_inputs; ++k) {  // what olap_store_eval_formula hands its kernel
+    p.in_values[k] = inputs[k]->values;
+    p.in_status[k] = mask_is_primary(inputs[k]) ? inputs[k]->status : nullptr;
+    p.in_dtype[k] = inputs[k]->dtype;
+    p.in_def_nan[k] = inputs[k]->default_kind == OLAP_DEFAULT_NAN;
+    aligned = aligned && ((uintptr_t)p.in_values[k] & 15u) == 0 && ((uintptr_t)p.in_status[k] & 15u) == 0;
+  }
+  for (int k = 0; k < n_scalars; ++k) p.scalars[k] = scalars[k];
+  // the kernel's lanes take 16 bytes at a time from the start of every buffer (pooled allocations are 256-byte aligned)
+  if (!aligned) return fail(OLAP_ERR_INVALID_ARGUMENT, "set_formula: a store's buffer is not 16-byte aligned");
+  if ((rc = order_before_bulk_write(target))) return rc;
+  drop_lazy_status(target);
+  bool plain = !getenv("OLAP_SET_FORMULA_ALL_OPS");  // developer knob: every program runs the instantiation with the library routines
+  for (int pc = 0; pc < n_code; ++pc) {
+    plain = plain && formula_op_is_plain(code[pc]);
+    if (code[pc] == F_CONST || code[pc] == F_INPUT || code[pc] == F_SCALAR) ++pc;  // (the operand is no opcode)
+  }
+  hipError_t e = hipSuccess;
+  DISPATCH_DTYPE(target->dtype, T, e = launch_formula_store<T>(plain, depth, p, target->values, target->status, n, target->default_kind == OLAP_DEFAULT_NAN));
+  if (e != hipSuccess) return hip_fail(e, "formula_store_kernel");
+  if ((rc = order_after_bulk_write(target))) return rc;
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return OLAP_OK;
 }
 

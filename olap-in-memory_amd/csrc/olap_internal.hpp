@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -66,6 +67,12 @@ struct olap_store {
   bool maybe_nonempty = false;       // some cell may be set (false only for a store nothing was written to)
   uint64_t hi_index = 0;             // no set cell lies above this index (valid while seq == nullptr)
 };
+
+// tests/test_set_formula_host.py restates the fields up to `status` (a ctypes stand-in for refusals decided without a
+// device): a change of their order or types must be made there too
+static_assert(offsetof(olap_store, size) == 0 && offsetof(olap_store, dtype) == 8 && offsetof(olap_store, default_kind) == 12 &&
+                  offsetof(olap_store, device) == 16 && offsetof(olap_store, values) == 24 && offsetof(olap_store, status) == 32,
+              "struct olap_store moved: update FakeStore in tests/test_set_formula_host.py");
 
 // The handle layer runs every operation on the device its store lives on, whatever device the
 // calling thread had current (one process may drive several GPUs: the sharded stores hand whole
@@ -140,8 +147,8 @@ OLAP_INTERNAL int select_cert(const olap_store *s, int ndim, const uint32_t *len
                               double *sum, double *abs_sum, int *min_exp, unsigned *flags);
 // 1 and *total when the certificate proves the order-free sum (times m) equal to the sequential one
 OLAP_INTERNAL int select_certified_total(double sum, double abs_sum, int min_exp, unsigned flags, double m, double *total);
-// the program checks of olap_eval_formula (olap_capi.hip): length, operands, stack
-OLAP_INTERNAL int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars);
+// the program checks of olap_eval_formula (olap_capi.hip): length, operands, stack; *max_depth: the deepest the stack gets
+OLAP_INTERNAL int check_formula(const int32_t *code, int n_code, int n_consts, int n_inputs, int n_scalars, int *max_depth = nullptr);
 OLAP_INTERNAL int select_copy(olap_store *target, const olap_store *source, int ndim, const uint32_t *lens, int nlev, const int *axis,
                               const uint32_t *n_sel, const int32_t *const *sel);
 

@@ -3477,6 +3477,81 @@ __device__ __forceinline__ double formula_input(const FormulaProgram &p, int k, 
   return v;
 }
 
+// The opcodes in two classes.  "Plain" ones are a handful of instructions each; the others pull in library routines of
+// hundreds (pow, tan, fmod, ...) that cost a kernel ~200 VGPRs whether or not the program at hand uses them.  A kernel
+// instantiated with ALL = false leaves those cases out: it may only run programs for which formula_is_plain() holds.
+__device__ __host__ __forceinline__ bool formula_op_is_plain(int op) {
+  switch (op) {
+    case F_CONST: case F_INPUT: case F_SCALAR: case F_ADD: case F_SUB: case F_MUL: case F_DIV: case F_NEG: case F_NANADD: case F_SELECT:
+    case F_MIN: case F_MAX: case F_ISNAN: case F_ABS: case F_CEIL: case F_FLOOR: case F_ROUND: case F_TRUNC: case F_SQRT: case F_SIGN: case F_NOT:
+      return true;
+    default:
+      return false;
+  }
+}
+
+// one-operand opcodes (F_NEG, F_ISNAN, F_ABS .. F_NOT)
+template <bool ALL = true>
+__device__ __forceinline__ double formula_unary(int op, double a) {
+  switch (op) {
+    case F_NEG: return -a;
+    case F_ISNAN: return (a != a) ? 1.0 : 0.0;
+    case F_ABS: return fabs(a);
+    case F_CEIL: return ceil(a);
+    case F_FLOOR: return floor(a);
+    case F_ROUND: return js_round(a);
+    case F_TRUNC: return trunc(a);
+    case F_SQRT: return sqrt(a);
+    case F_SIGN: return (a != a) ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : a));
+    case F_NOT: return js_truthy(a) ? 0.0 : 1.0;
+    default: break;
+  }
+  if constexpr (ALL) {
+    switch (op) {
+      case F_CBRT: return cbrt(a);
+      case F_EXP: return exp(a);
+      case F_LN: return log(a);
+      case F_LOG10: return log10(a);
+      case F_LOG2: return log2(a);
+      case F_SIN: return sin(a);
+      case F_COS: return cos(a);
+      case F_TAN: return tan(a);
+      case F_ASIN: return asin(a);
+      case F_ACOS: return acos(a);
+      default: return atan(a);  // F_ATAN
+    }
+  }
+  return __builtin_nan("");  // (not reached: the host never hands such a program to an ALL = false kernel)
+}
+
+// two-operand opcodes (F_ADD .. F_ROUNDTO)
+template <bool ALL = true>
+__device__ __forceinline__ double formula_binary(int op, double a, double b) {
+  switch (op) {
+    case F_ADD: return a + b;
+    case F_SUB: return a - b;
+    case F_MUL: return a * b;
+    case F_DIV: return a / b;
+    case F_NANADD: return (a != a && b == b) ? b : ((a == a && b != b) ? a : a + b);  // src/parser.js:18-23
+    case F_MIN: return js_min(a, b);
+    case F_MAX: return js_max(a, b);
+    default: break;
+  }
+  if constexpr (ALL) {
+    switch (op) {
+      case F_MOD: return fmod(a, b);
+      case F_POW: return pow(a, b);
+      case F_ATAN2: return atan2(a, b);
+      case F_HYPOT: return hypot(a, b);
+      default: {  // F_ROUNDTO
+        const double f = pow(10.0, trunc(b));
+        return js_round(a * f) / f;
+      }
+    }
+  }
+  return __builtin_nan("");  // (not reached, as above)
+}
+
 // The program at one cell; input(k) gives the value of input k there.
 template <int STACK, typename Input>
 __device__ __forceinline__ double formula_run(const FormulaProgram &p, Input input) {
@@ -3495,55 +3570,11 @@ __device__ __forceinline__ double formula_run(const FormulaProgram &p, Input inp
       sp -= 2;
       st[sp - 1] = js_truthy(c) ? a : b;
     } else if (op == F_NEG || op == F_ISNAN || op >= F_ABS) {
-      const double a = st[sp - 1];
-      double r;
-      switch (op) {
-        case F_NEG: r = -a; break;
-        case F_ISNAN: r = (a != a) ? 1.0 : 0.0; break;
-        case F_ABS: r = fabs(a); break;
-        case F_CEIL: r = ceil(a); break;
-        case F_FLOOR: r = floor(a); break;
-        case F_ROUND: r = js_round(a); break;
-        case F_TRUNC: r = trunc(a); break;
-        case F_SQRT: r = sqrt(a); break;
-        case F_CBRT: r = cbrt(a); break;
-        case F_EXP: r = exp(a); break;
-        case F_LN: r = log(a); break;
-        case F_LOG10: r = log10(a); break;
-        case F_LOG2: r = log2(a); break;
-        case F_SIGN: r = (a != a) ? a : (a > 0.0 ? 1.0 : (a < 0.0 ? -1.0 : a)); break;
-        case F_SIN: r = sin(a); break;
-        case F_COS: r = cos(a); break;
-        case F_TAN: r = tan(a); break;
-        case F_ASIN: r = asin(a); break;
-        case F_ACOS: r = acos(a); break;
-        case F_ATAN: r = atan(a); break;
-        default: r = js_truthy(a) ? 0.0 : 1.0; break;  // F_NOT
-      }
-      st[sp - 1] = r;
+      st[sp - 1] = formula_unary(op, st[sp - 1]);
     } else {
       const double a = st[sp - 2], b = st[sp - 1];
       --sp;
-      double r;
-      switch (op) {
-        case F_ADD: r = a + b; break;
-        case F_SUB: r = a - b; break;
-        case F_MUL: r = a * b; break;
-        case F_DIV: r = a / b; break;
-        case F_MOD: r = fmod(a, b); break;
-        case F_POW: r = pow(a, b); break;
-        case F_NANADD: r = (a != a && b == b) ? b : ((a == a && b != b) ? a : a + b); break;  // src/parser.js:18-23
-        case F_MIN: r = js_min(a, b); break;
-        case F_MAX: r = js_max(a, b); break;
-        case F_ATAN2: r = atan2(a, b); break;
-        case F_HYPOT: r = hypot(a, b); break;
-        default: {  // F_ROUNDTO
-          const double f = pow(10.0, trunc(b));
-          r = js_round(a * f) / f;
-          break;
-        }
-      }
-      st[sp - 1] = r;
+      st[sp - 1] = formula_binary(op, a, b);
     }
   }
   return sp > 0 ? st[sp - 1] : __builtin_nan("");
@@ -3564,6 +3595,136 @@ __device__ __forceinline__ double formula_at_missing(const FormulaProgram &p) {
 template <int STACK>  // a template only so that the header may be included by several translation units
 __global__ __launch_bounds__(kBlock) void eval_formula_kernel(const FormulaProgram p, double *__restrict__ out, uint64_t n) {
   for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) out[i] = formula_at<STACK>(p, i);
+}
+
+// ---- formula_store_kernel: the program written straight into a typed store (olap_store_set_formula) ----------------
+// W cells of one input from cell i0 on, widened to float64 by the input's own type: one streaming load of the W cells
+// (two 16-byte halves for 8-byte cells feeding four 4-byte ones), cell by cell in the last, partial group (cnt < W).
+template <typename S, int W>
+__device__ __forceinline__ void formula_cells_wide(const void *base, uint64_t i0, int cnt, double (&v)[W]) {
+  const S *src = (const S *)base + i0;
+  if (cnt == W) {
+    const Vec<S, W> x = load_stream<S, W>(src);
+#pragma unroll
+    for (int c = 0; c < W; ++c) v[c] = (double)x.v[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < W; ++c) v[c] = c < cnt ? (double)src[c] : 0.0;
+  }
+}
+
+// formula_input for the W cells from i0 on; the switch over the input's type is uniform across the wave
+template <int W>
+__device__ __forceinline__ void formula_input_wide(const FormulaProgram &p, int k, uint64_t i0, int cnt, double (&v)[W]) {
+  switch (p.in_dtype[k]) {
+    case OLAP_INT32: formula_cells_wide<int32_t, W>(p.in_values[k], i0, cnt, v); break;
+    case OLAP_UINT32: formula_cells_wide<uint32_t, W>(p.in_values[k], i0, cnt, v); break;
+    case OLAP_FLOAT32: formula_cells_wide<float, W>(p.in_values[k], i0, cnt, v); break;
+    default: formula_cells_wide<double, W>(p.in_values[k], i0, cnt, v); break;
+  }
+  if (p.in_status[k]) {
+    const int32_t *st = p.in_status[k] + i0;
+    const double unset = p.in_def_nan[k] ? __builtin_nan("") : 0.0;
+    if (cnt == W) {
+      const Vec<int32_t, W> m = load_stream<int32_t, W>(st);
+#pragma unroll
+      for (int c = 0; c < W; ++c) v[c] = (m.v[c] & OLAP_STATUS_SET) ? v[c] : unset;
+    } else {
+#pragma unroll
+      for (int c = 0; c < W; ++c)
+        if (c < cnt && !(st[c] & OLAP_STATUS_SET)) v[c] = unset;
+    }
+  }
+}
+
+// formula_run over the W cells a lane owns: every opcode is decoded once and applied to the W columns of the stack,
+// each column going through the very operations formula_run applies to its one cell.  pc, sp and the opcode come from
+// the kernel arguments, so the control flow is scalar.  The newest value of the stack stays in registers (`top`); the ones
+// below it live in this lane's column of LDS (`below`: slot s holds its W cells as W / 2 pairs, pair j at
+// below[(s * (W / 2) + j) * kBlock] — lane after lane 16 bytes apart, so a wave's access has no bank conflict), which
+// keeps a stack that is indexed at run time out of scratch memory and sizes it by the program's real depth.
+template <int W, bool ALL, typename Input>
+__device__ __forceinline__ void formula_run_wide(const FormulaProgram &p, Input input, Vec<double, 2> *below, double (&top)[W]) {
+  constexpr int P = W / 2;
+  int sp = 0;  // values on the stack: `top` and slots 0 .. sp - 2
+  for (int pc = 0; pc < p.n_code; ++pc) {
+    const int op = p.code[pc];
+    if (op == F_CONST || op == F_SCALAR || op == F_INPUT) {
+      if (sp > 0) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) below[((sp - 1) * P + j) * kBlock] = Vec<double, 2>{{top[2 * j], top[2 * j + 1]}};
+      }
+      const int k = p.code[++pc];
+      if (op == F_INPUT) {
+        input(k, top);
+      } else {
+        const double x = op == F_CONST ? p.consts[k] : p.scalars[k];
+#pragma unroll
+        for (int c = 0; c < W; ++c) top[c] = x;
+      }
+      ++sp;
+    } else if (op == F_SELECT) {
+      sp -= 2;  // condition: slot sp - 1, then-value: slot sp, else-value: top
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const Vec<double, 2> c = below[((sp - 1) * P + j) * kBlock], a = below[(sp * P + j) * kBlock];
+        top[2 * j] = js_truthy(c.v[0]) ? a.v[0] : top[2 * j];
+        top[2 * j + 1] = js_truthy(c.v[1]) ? a.v[1] : top[2 * j + 1];
+      }
+    } else if (op == F_NEG || op == F_ISNAN || op >= F_ABS) {
+#pragma unroll
+      for (int c = 0; c < W; ++c) top[c] = formula_unary<ALL>(op, top[c]);
+    } else {
+      --sp;  // left operand: slot sp - 1, right operand: top
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const Vec<double, 2> a = below[((sp - 1) * P + j) * kBlock];
+        top[2 * j] = formula_binary<ALL>(op, a.v[0], top[2 * j]);
+        top[2 * j + 1] = formula_binary<ALL>(op, a.v[1], top[2 * j + 1]);
+      }
+    }
+  }
+}
+
+// bytes of LDS a workgroup of formula_store_kernel needs for a program whose stack gets `depth` deep
+inline size_t formula_store_lds(int depth, size_t cell_bytes) { return (size_t)(depth > 1 ? depth - 1 : 0) * 16 / cell_bytes * sizeof(double) * kBlock; }
+
+// values[i] (and status[i], where the store keeps its mask) = the typed cell of formula_at(p, i) for every i < n: what
+// eval_formula_kernel followed by from_f64_kernel leave, without the float64 cube in between.  A lane owns 16 bytes of
+// output — W = 16 / sizeof(T) cells — reads them from every input with streaming loads and writes them with one streaming
+// store (one more for the mask).  ALL = false: the program holds plain opcodes only (formula_op_is_plain).  Dynamic LDS:
+// formula_store_lds(depth).  Every buffer starts 16-byte aligned (the host checks); the last group may be partial and
+// is read and written cell by cell.
+template <typename T, bool HAS_STATUS, bool ALL>
+__global__ __launch_bounds__(kBlock) void formula_store_kernel(const FormulaProgram p, T *__restrict__ values, int32_t *__restrict__ status, uint64_t n,
+                                                               int def_nan_i) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char formula_stack_raw[];
+  Vec<double, 2> *below = reinterpret_cast<Vec<double, 2> *>(formula_stack_raw) + threadIdx.x;
+  constexpr int W = 16 / (int)sizeof(T);
+  const bool def_nan = def_nan_i != 0;
+  const uint64_t groups = (n + W - 1) / W;
+  for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < groups; g += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t i0 = g * W;
+    const int cnt = n - i0 < (uint64_t)W ? (int)(n - i0) : W;
+    double r[W];
+    formula_run_wide<W, ALL>(p, [&](int k, double (&v)[W]) { formula_input_wide<W>(p, k, i0, cnt, v); }, below, r);
+    Vec<T, W> ov;
+    Vec<int32_t, W> os;
+#pragma unroll
+    for (int c = 0; c < W; ++c) emit_cell<T>(r[c], !is_default_f64(r[c], def_nan), def_nan, ov.v[c], os.v[c]);
+    if (cnt == W) {
+      store_stream<T, W>(values + i0, ov);
+      if constexpr (HAS_STATUS) store_stream<int32_t, W>(status + i0, os);
+    } else {
+#pragma unroll
+      for (int c = 0; c < W; ++c) {
+        if (c < cnt) {
+          values[i0 + c] = ov.v[c];
+          if constexpr (HAS_STATUS) status[i0 + c] = os.v[c];
+        }
+      }
+    }
+  }
 }
 
 // ======================================================================= sparse <-> dense

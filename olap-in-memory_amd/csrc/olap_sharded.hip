@@ -1820,6 +1820,31 @@ extern "C" int olap_sharded_store_eval_formula(const int32_t *code, int n_code, 
   });
 }
 
+// a computed measure written into a sharded target: olap_store_set_formula per shard, each on its own device
+extern "C" int olap_sharded_store_set_formula(olap_sharded_store *target, const int32_t *code, int n_code, const double *consts, int n_consts,
+                                              int n_inputs, const olap_sharded_store *const *inputs, const double *scalars, int n_scalars) {
+  int rc = check_formula(code, n_code, n_consts, n_inputs, n_scalars);
+  if (rc) return rc;
+  if (!target) return fail(OLAP_ERR_INVALID_ARGUMENT, "store is NULL");
+  if (n_inputs < 1 || !inputs) return fail(OLAP_ERR_INVALID_ARGUMENT, "a formula needs at least one stored measure to read");
+  if ((n_consts && !consts) || (n_scalars && !scalars)) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula argument arrays must not be NULL");
+  for (int k = 0; k < n_inputs; ++k) {
+    if (!inputs[k]) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is NULL", k);
+    if (inputs[k]->size != target->size)
+      return fail(OLAP_ERR_LENGTH_MISMATCH, "formula input %d holds %llu cells, the target %llu", k, (unsigned long long)inputs[k]->size, (unsigned long long)target->size);
+    if (inputs[k] == target) return fail(OLAP_ERR_INVALID_ARGUMENT, "formula input %d is the target itself", k);
+  }
+  for (int k = 0; k < n_inputs; ++k)
+    if (inputs[k]->comm != target->comm || inputs[k]->bounds != target->bounds || inputs[k]->inner0 != target->inner0)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "sharded: the formula's inputs and the target are not partitioned alike; gather first");
+  return for_each_shard(target, [&](int i, olap_store *sh) -> int {
+    if (!sh->size) return OLAP_OK;
+    const olap_store *shards[OLAP_FORMULA_MAX_INPUTS];
+    for (int k = 0; k < n_inputs; ++k) shards[k] = inputs[k]->shard[i];
+    return olap_store_set_formula(sh, code, n_code, consts, n_consts, n_inputs, shards, scalars, n_scalars);
+  });
+}
+
 static bool identity_map(const uint32_t *m, uint32_t old_len, uint32_t new_len) {
   if (old_len != new_len) return false;
   for (uint32_t k = 0; k < old_len; ++k)

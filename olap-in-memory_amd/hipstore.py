@@ -554,6 +554,14 @@ class HipStore:
                                                        n.ctypes.data_as(capi._pu32), arr))
         return self
 
+    def set_formula(self, code, consts, inputs, scalars=()):
+        """olap_store_set_formula: self.set_data_f64(formula over `inputs`) in one launch, without the host.  `code` /
+        `consts` as olap_eval_formula takes them, `inputs` the stores INPUT k reads, `scalars` the values SCALAR k reads."""
+        prog = _formula(code, consts, inputs)
+        sc = np.ascontiguousarray(scalars if len(scalars) else [0.0], dtype=np.float64).reshape(-1)
+        check(self._lib.olap_store_set_formula(self._h, *prog[:-1], sc.ctypes.data_as(capi._pdbl), len(scalars)))
+        return self
+
     def load(self, other, my_len, his_len, his_to_mine):
         ml, hl = _u32(my_len), _u32(his_len)
         keep, arr = _tables(his_to_mine, np.int32, C.c_int32)

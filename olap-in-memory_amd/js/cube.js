@@ -128,18 +128,81 @@ class Cube {
     this.computedMeasures[measureId] = expression;
   }
 
+  /**
+   * src/cube.js:205-233.  A source that reads stored measures is written into the new measure by one device call
+   * (_materializeOnDevice); anything else takes the host path, with its messages and the state it leaves when it throws.
+   */
   copyToStoredMeasure(computedMeasureId, storedMeasureId, rules = {}, type = 'float32', defaultValue = 0) {
+    HipStore.lastMaterializePath = null;
+    if (this._materializeOnDevice(computedMeasureId, storedMeasureId, rules, type, defaultValue, false)) return;
+    this._copyToStoredMeasureHost(computedMeasureId, storedMeasureId, rules, type, defaultValue, false);
+  }
+
+  convertToStoredMeasure(measureId, rules = {}, type = 'float32', defaultValue = 0) {
+    HipStore.lastMaterializePath = null;
+    if (this.computedMeasures[measureId] && this._materializeOnDevice(measureId, measureId, rules, type, defaultValue, true)) return;
+    this._copyToStoredMeasureHost(measureId, measureId, rules, type, defaultValue, true);
+  }
+
+  /** Both methods through the host: a plain Array of every cell down, a Float64Array of every cell up. */
+  _copyToStoredMeasureHost(computedMeasureId, storedMeasureId, rules, type, defaultValue, convert) {
+    HipStore.lastMaterializePath = 'host';
+    if (convert && !this.computedMeasures[computedMeasureId]) throw new Error(`convertToStoredMeasure: no such computed measure: ${computedMeasureId}`);
     const data = this.getData(computedMeasureId);
+    if (convert) this.dropMeasure(computedMeasureId);
     this.createStoredMeasure(storedMeasureId, rules, type, defaultValue);
     this.setData(storedMeasureId, data);
   }
 
-  convertToStoredMeasure(measureId, rules = {}, type = 'float32', defaultValue = 0) {
-    if (!this.computedMeasures[measureId]) throw new Error(`convertToStoredMeasure: no such computed measure: ${measureId}`);
-    const data = this.getData(measureId);
-    this.dropMeasure(measureId);
-    this.createStoredMeasure(measureId, rules, type, defaultValue);
-    this.setData(measureId, data);
+  /**
+   * What getData(sourceId) evaluates, as a device program: { program, stores, totals } for a stored measure (`INPUT 0`) and
+   * for a computed one that reads at least one stored measure; null otherwise.
+   */
+  _materializeSource(sourceId) {
+    const stored = this.storedMeasures[sourceId];
+    if (stored !== undefined) return { program: { code: Int32Array.of(1, 0), consts: new Float64Array(0) }, stores: [stored], totals: [] };
+    const expression = this.computedMeasures[sourceId];
+    if (expression === undefined) return null;
+    const inputs = {};
+    const scalars = {};
+    const stores = [];
+    const totals = [];
+    for (const name of expression.variables({ withMembers: true })) {
+      const store = this.storedMeasures[name.replace('__total', '')];
+      if (store === undefined) return null;
+      if (name.includes('__total')) scalars[name] = totals.push(store.total) - 1;
+      else inputs[name] = stores.push(store) - 1;
+    }
+    if (stores.length === 0) return null;
+    return { program: expression.compile(inputs, scalars), stores, totals };
+  }
+
+  /**
+   * copyToStoredMeasure / convertToStoredMeasure without the host (DESIGN.md §3 K10).  The new store is filled by
+   * HipStore.setFormula BEFORE the cube changes; then dropMeasure (for a conversion) and the new measure follow, in the order
+   * of the host path.  Returns false with the cube untouched whenever the host path would throw somewhere (an unknown
+   * source, an id that is taken or invalid, a type or default the store refuses), when the source reads no stored measure,
+   * when the device call refuses the program (its limits are the C ABI's), and when a sharded target cannot read the inputs
+   * in place: the host path then runs, with its messages.
+   */
+  _materializeOnDevice(sourceId, targetId, rules, type, defaultValue, convert) {
+    if (!MEASURE_ID.test(targetId) || (this.storedMeasures[targetId] !== undefined)) return false;
+    if (!['int32', 'uint32', 'float32', 'float64'].includes(type) || !(Number.isNaN(defaultValue) || defaultValue === 0)) return false;
+    const source = this._materializeSource(sourceId);
+    if (source === null) return false;
+    const ordered = Object.values(rules || {}).some((rule) => rule === 'first' || rule === 'last');
+    // a target split over several devices reads inputs that are split too (no store is created for the others)
+    if (!ordered && HipStore.splits(this.dimensions.map((d) => d.numItems)) && !source.stores.every((store) => store._native.isSharded)) return false;
+    const store = this._newStore(type, defaultValue, rules);
+    try {
+      if (!store.setFormula(source.program, source.stores, source.totals)) return false;
+    } catch (e) {
+      return false; // refused (a program beyond the device call's limits): the host path says so in its own words
+    }
+    if (convert) this.dropMeasure(sourceId);
+    this.storedMeasures[targetId] = store;
+    this.storedMeasuresRules[targetId] = rules;
+    return true;
   }
 
   replaceStoredMeasure(toKeep, toDrop) {

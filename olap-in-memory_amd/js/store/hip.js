@@ -182,9 +182,14 @@ class HipStore {
   static _create(size, type, defaultValue, lengths) {
     const addon = backend.load();
     const def = Number.isNaN(defaultValue) ? 1 : 0;
-    const world = addon.shardWorld();
-    if (world >= 2 && lengths && lengths.length >= 1 && lengths[0] >= world) return new addon.ShardedStore(Uint32Array.from(lengths), TYPE_CODE[type], def);
+    if (HipStore.splits(lengths)) return new addon.ShardedStore(Uint32Array.from(lengths), TYPE_CODE[type], def);
     return new addon.Store(size, TYPE_CODE[type], def);
+  }
+
+  /** Whether a new store laid out as `lengths` is split over the devices of the list (see _create). */
+  static splits(lengths) {
+    const world = backend.load().shardWorld();
+    return world >= 2 && !!lengths && lengths.length >= 1 && lengths[0] >= world;
   }
 
   /** The device store (one device, or sharded); a pending dice is executed on first use. */
@@ -577,6 +582,32 @@ class HipStore {
     return true;
   }
 
+  /**
+   * this.data = the formula over `inputs`, cell by cell, as ONE device call (olap_store_set_formula): `program` (formula.js
+   * compile()) reads the stores `inputs` and the numbers `totals` (its SCALAR operands).  The cells, the mask and the key
+   * order end as `this.data = <the formula's plain Array>` leaves them; nothing crosses to the host.  Pending dices among
+   * the inputs are materialised; an input is gathered only when this store is on one device and that input is not.
+   * Returns false when this store is sharded and the inputs are not partitioned like it: the caller goes through the host.
+   */
+  setFormula(program, inputs, totals) {
+    const target = this._writable;
+    const scalars = Float64Array.from(totals);
+    if (target.isSharded) {
+      const natives = inputs.map((store) => store._native);
+      if (!natives.every((native) => native.isSharded)) return false;
+      try {
+        target.setFormula(program.code, program.consts, natives, scalars);
+      } catch (e) {
+        if (!/^sharded:/.test(e.message)) throw e;
+        return false;
+      }
+    } else {
+      target.setFormula(program.code, program.consts, inputs.map((store) => store._whole), scalars);
+    }
+    HipStore.lastMaterializePath = 'device';
+    return true;
+  }
+
   /** in-memory.js:178-211 */
   reorder(oldDimensions, newDimensions) {
     const perm = Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
@@ -636,6 +667,10 @@ HipStore.lastTotalsLaunches = null;
 HipStore.lastTotalsCalls = null;
 // 'device' after a copyMeasureData that ran as one device scatter (copySelect / copySelectFormula); never reset here
 HipStore.lastCopyPath = null;
+
+// what the last Cube.copyToStoredMeasure / convertToStoredMeasure did: 'device' (setFormula: one device call, no host copy)
+// or 'host' (getData, then setData); Cube resets it to null when such a call starts
+HipStore.lastMaterializePath = null;
 
 module.exports = HipStore;
 module.exports.toPlainArray = toPlainArray;

@@ -741,40 +741,77 @@ static napi_value StoreCopySelect(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// The (code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array) of evalFormula and setFormula.
+// An empty typed array may come without a buffer: the C ABI then gets the address of a zero instead of NULL.
+struct ProgramArgs {
+  size_t n_code = 0, n_consts = 0, n_scalars = 0;
+  void *code_p = nullptr, *consts_p = nullptr, *scalars_p = nullptr;
+  uint32_t n_inputs = 0;
+  bool no_list = false;  // (after a failed decode_program) the typed arrays were fine, `stores` is no array
+  std::vector<const olap_store *> stores;
+  const int32_t *code() const { return (const int32_t *)code_p; }
+  const double *consts() const { return consts_p ? (const double *)consts_p : &zero(); }
+  const double *scalars() const { return scalars_p ? (const double *)scalars_p : &zero(); }
+  static const double &zero() {
+    static const double z = 0;
+    return z;
+  }
+  // the three typed arrays and the length of the store list; false: the arguments have the wrong types
+  bool decode_program(napi_env env, const napi_value *argv) {
+    napi_typedarray_type t;
+    if (napi_get_typedarray_info(env, argv[0], &t, &n_code, &code_p, nullptr, nullptr) != napi_ok || t != napi_int32_array ||
+        napi_get_typedarray_info(env, argv[1], &t, &n_consts, &consts_p, nullptr, nullptr) != napi_ok || t != napi_float64_array ||
+        napi_get_typedarray_info(env, argv[3], &t, &n_scalars, &scalars_p, nullptr, nullptr) != napi_ok || t != napi_float64_array)
+      return false;
+    bool is_arr = false;
+    napi_is_array(env, argv[2], &is_arr);
+    no_list = !is_arr;
+    if (!is_arr) return false;
+    napi_get_array_length(env, argv[2], &n_inputs);
+    return true;
+  }
+  // the stores of a Store[]; false with an exception pending when an element is not a Store
+  bool decode_stores(napi_env env, napi_value list) {
+    stores.resize(n_inputs);
+    for (uint32_t i = 0; i < n_inputs; ++i) {
+      napi_value e;
+      if (napi_get_element(env, list, i, &e) != napi_ok) return false;
+      stores[i] = unwrap(env, e);
+      if (!stores[i]) return false;
+    }
+    return true;
+  }
+};
+
 // evalFormula(code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array) -> Float64Array
 static napi_value EvalFormula(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   if (argc < 4) return bad_args(env, "evalFormula(code, consts, stores, scalars)");
-  napi_typedarray_type t;
-  size_t n_code = 0, n_consts = 0, n_scalars = 0;
-  void *code = nullptr, *consts = nullptr, *scalars = nullptr;
-  if (napi_get_typedarray_info(env, argv[0], &t, &n_code, &code, nullptr, nullptr) != napi_ok || t != napi_int32_array ||
-      napi_get_typedarray_info(env, argv[1], &t, &n_consts, &consts, nullptr, nullptr) != napi_ok || t != napi_float64_array ||
-      napi_get_typedarray_info(env, argv[3], &t, &n_scalars, &scalars, nullptr, nullptr) != napi_ok || t != napi_float64_array)
-    return bad_args(env, "evalFormula(code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array)");
-  bool is_arr = false;
-  napi_is_array(env, argv[2], &is_arr);
-  if (!is_arr) return bad_args(env, "evalFormula: stores must be an array of Store");
-  uint32_t n_inputs = 0;
-  napi_get_array_length(env, argv[2], &n_inputs);
-  std::vector<const olap_store *> stores(n_inputs);
-  for (uint32_t i = 0; i < n_inputs; ++i) {
-    napi_value e;
-    NAPI_OK(napi_get_element(env, argv[2], i, &e));
-    stores[i] = unwrap(env, e);
-    if (!stores[i]) return nullptr;
-  }
-  const uint64_t n = n_inputs ? olap_store_size(stores[0]) : 0;
+  ProgramArgs a;
+  if (!a.decode_program(env, argv))
+    return bad_args(env, a.no_list ? "evalFormula: stores must be an array of Store" : "evalFormula(code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array)");
+  if (!a.decode_stores(env, argv[2])) return nullptr;
+  const uint64_t n = a.n_inputs ? olap_store_size(a.stores[0]) : 0;
   void *out;
   napi_value ta = make_ta(env, napi_float64_array, 8, n, &out);
   if (!ta) return nullptr;
-  static const double zero = 0;
-  int rc = olap_store_eval_formula((const int32_t *)code, (int)n_code, consts ? (const double *)consts : &zero, (int)n_consts, (int)n_inputs,
-                                   stores.data(), scalars ? (const double *)scalars : &zero, (int)n_scalars, (double *)out);
+  int rc = olap_store_eval_formula(a.code(), (int)a.n_code, a.consts(), (int)a.n_consts, (int)a.n_inputs, a.stores.data(), a.scalars(), (int)a.n_scalars,
+                                   (double *)out);
   if (rc) return throw_olap(env, rc);
   return ta;
+}
+
+// store.setFormula(code, consts, stores: Store[], scalars): store.setData(evalFormula(...)) in one device call, without the host
+static napi_value StoreSetFormula(napi_env env, napi_callback_info info) {
+  STORE_METHOD_PROLOGUE(4)
+  ProgramArgs a;
+  if (argc < 4 || !a.decode_program(env, argv)) return bad_args(env, "setFormula(code: Int32Array, consts: Float64Array, stores: Store[], scalars: Float64Array)");
+  if (!a.decode_stores(env, argv[2])) return nullptr;
+  int rc = olap_store_set_formula(s, a.code(), (int)a.n_code, a.consts(), (int)a.n_consts, (int)a.n_inputs, a.stores.data(), a.scalars(), (int)a.n_scalars);
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
 }
 
 // A formula over a selection: code (Int32Array), consts (Float64Array) and stores (Store[], the inputs)
@@ -1367,40 +1404,52 @@ static napi_value ShardStore(napi_env env, napi_callback_info info) {
   return wrap_new_sharded(env, s, g_comm);
 }
 
+// the ShardedStore[] of evalFormulaSharded / setFormula; false with an exception pending when an element is not one
+static bool decode_sharded_stores(napi_env env, napi_value list, uint32_t n, std::vector<const olap_sharded_store *> &stores) {
+  stores.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value e;
+    if (napi_get_element(env, list, i, &e) != napi_ok) return false;
+    ShardedBox *box = unwrap_sharded(env, e);
+    if (!box) return false;
+    stores[i] = box->store;
+  }
+  return true;
+}
+
 // evalFormulaSharded(code, consts, stores: ShardedStore[], scalars) -> Float64Array: per shard, no gather
 static napi_value EvalFormulaSharded(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   if (argc < 4) return bad_args(env, "evalFormulaSharded(code, consts, stores, scalars)");
-  napi_typedarray_type t;
-  size_t n_code = 0, n_consts = 0, n_scalars = 0;
-  void *code = nullptr, *consts = nullptr, *scalars = nullptr;
-  if (napi_get_typedarray_info(env, argv[0], &t, &n_code, &code, nullptr, nullptr) != napi_ok || t != napi_int32_array ||
-      napi_get_typedarray_info(env, argv[1], &t, &n_consts, &consts, nullptr, nullptr) != napi_ok || t != napi_float64_array ||
-      napi_get_typedarray_info(env, argv[3], &t, &n_scalars, &scalars, nullptr, nullptr) != napi_ok || t != napi_float64_array)
+  ProgramArgs a;
+  if (!a.decode_program(env, argv) && !a.no_list)
     return bad_args(env, "evalFormulaSharded(code: Int32Array, consts: Float64Array, stores: ShardedStore[], scalars: Float64Array)");
-  bool is_arr = false;
-  napi_is_array(env, argv[2], &is_arr);
-  uint32_t n_inputs = 0;
-  if (is_arr) napi_get_array_length(env, argv[2], &n_inputs);
-  if (!is_arr || n_inputs == 0) return bad_args(env, "evalFormulaSharded: stores must be a non-empty array of ShardedStore");
-  std::vector<const olap_sharded_store *> stores(n_inputs);
-  for (uint32_t i = 0; i < n_inputs; ++i) {
-    napi_value e;
-    NAPI_OK(napi_get_element(env, argv[2], i, &e));
-    ShardedBox *box = unwrap_sharded(env, e);
-    if (!box) return nullptr;
-    stores[i] = box->store;
-  }
+  if (a.no_list || a.n_inputs == 0) return bad_args(env, "evalFormulaSharded: stores must be a non-empty array of ShardedStore");
+  std::vector<const olap_sharded_store *> stores;
+  if (!decode_sharded_stores(env, argv[2], a.n_inputs, stores)) return nullptr;
   void *out;
   napi_value ta = make_ta(env, napi_float64_array, 8, olap_sharded_store_size(stores[0]), &out);
   if (!ta) return nullptr;
-  static const double zero = 0;
-  int rc = olap_sharded_store_eval_formula((const int32_t *)code, (int)n_code, consts ? (const double *)consts : &zero, (int)n_consts, (int)n_inputs,
-                                           stores.data(), scalars ? (const double *)scalars : &zero, (int)n_scalars, (double *)out);
+  int rc = olap_sharded_store_eval_formula(a.code(), (int)a.n_code, a.consts(), (int)a.n_consts, (int)a.n_inputs, stores.data(), a.scalars(), (int)a.n_scalars,
+                                           (double *)out);
   if (rc) return throw_olap(env, rc);
   return ta;
+}
+
+// sharded.setFormula(code, consts, stores: ShardedStore[], scalars): Store.setFormula per shard; "sharded: ..." when the
+// stores are not partitioned like this one
+static napi_value ShardedSetFormula(napi_env env, napi_callback_info info) {
+  SHARDED_PROLOGUE(4)
+  ProgramArgs a;
+  if (argc < 4 || !a.decode_program(env, argv))
+    return bad_args(env, "setFormula(code: Int32Array, consts: Float64Array, stores: ShardedStore[], scalars: Float64Array)");
+  std::vector<const olap_sharded_store *> stores;
+  if (!decode_sharded_stores(env, argv[2], a.n_inputs, stores)) return nullptr;
+  int rc = olap_sharded_store_set_formula(s, a.code(), (int)a.n_code, a.consts(), (int)a.n_consts, (int)a.n_inputs, stores.data(), a.scalars(), (int)a.n_scalars);
+  if (rc) return throw_olap(env, rc);
+  return nullptr;
 }
 
 // setDevices(devices: number[] | null): the devices new sharded measures are split over
@@ -1510,6 +1559,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"selectTotal", nullptr, StoreSelectTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"copySelect", nullptr, StoreCopySelect, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"copySelectFormula", nullptr, StoreCopySelectFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"setFormula", nullptr, StoreSetFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
   };
   napi_value ctor;
   if (napi_define_class(env, "Store", NAPI_AUTO_LENGTH, StoreNew, nullptr, sizeof(props) / sizeof(props[0]), props, &ctor) != napi_ok) return nullptr;
@@ -1528,6 +1578,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"getValue", nullptr, ShardedGetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setValue", nullptr, ShardedSetValue, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"setValues", nullptr, ShardedSetValues, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"setFormula", nullptr, ShardedSetFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"fill", nullptr, ShardedFill, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"total", nullptr, ShardedTotal, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"clone", nullptr, ShardedClone, nullptr, nullptr, nullptr, napi_default, nullptr},

@@ -330,6 +330,17 @@ class ShardedStore:
         check(self._lib.olap_sharded_store_set_data_f64(self._h, v.ctypes.data_as(capi._pdbl), v.size))
         return self
 
+    def set_formula(self, code, consts, inputs, scalars=()):
+        """olap_sharded_store_set_formula: HipStore.set_formula per shard; `inputs` are sharded stores partitioned like
+        this one (anything else raises "sharded: ...")."""
+        c = np.ascontiguousarray(code, dtype=np.int32).reshape(-1)
+        k = np.ascontiguousarray(consts if len(consts) else [0.0], dtype=np.float64).reshape(-1)
+        sc = np.ascontiguousarray(scalars if len(scalars) else [0.0], dtype=np.float64).reshape(-1)
+        table = (C.c_void_p * max(len(inputs), 1))(*[s._h.value if s is not None else None for s in inputs])
+        check(self._lib.olap_sharded_store_set_formula(self._h, c.ctypes.data_as(capi._pi32), len(c), k.ctypes.data_as(capi._pdbl), len(consts),
+                                                       len(inputs), table, sc.ctypes.data_as(capi._pdbl), len(scalars)))
+        return self
+
     def get_data_f64(self):
         """Full-size array; only the rows of this process' ranks are filled (the rest stay NaN)."""
         out = np.full(max(self.size, 1), np.nan)
