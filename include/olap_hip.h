@@ -171,8 +171,12 @@ int olap_plan_run(olap_plan *plan, const void *in_values, const int32_t *in_stat
  * type, default and rule: Cube.drillUp calls the store once per measure (src/cube.js:1012-1020), and on cubes of a
  * few MB a launch costs more than the bytes it moves.  drillUp plans of one dimension outside the few-outputs reduce
  * regime run up to 8 pairs per LAUNCH (the grid's second dimension picks the pair; pairs must all carry masks or
- * none); every other plan runs pair by pair behind this one call.  in_status / out_status may be NULL (no masks) or
- * lists whose entries may be NULL.  Same results as n olap_plan_run calls. */
+ * none).  So do the gather family (a dice without masks as a lane loop over the pairs instead): dice plans (and a
+ * reorder that runs as a gather), fused dice -> drillUp plans and
+ * the row forms of drillDown, when every buffer of the eight starts on a 16-byte boundary.  Pair by pair behind this
+ * one call: pairs with mixed masks, buffers off the 16-byte grid, the two-pass drillDown, drillDown with distributions
+ * and its per-cell form, the two-axis transpose, load and the other drillUp regimes.  in_status / out_status may be
+ * NULL (no masks) or lists whose entries may be NULL.  Same results as n olap_plan_run calls. */
 int olap_plan_run_batch(olap_plan *plan, int n, const void *const *in_values, const int32_t *const *in_status,
                         void *const *out_values, int32_t *const *out_status, void *stream);
 /* A drillUp plan over n pairs with a rule EACH (methods[i], one of the seven reference methods; the rule the plan
@@ -448,6 +452,24 @@ int olap_store_dice_drillup(const olap_store *store, olap_store **out, int ndim,
                             const uint32_t *const *maps, int method);
 int olap_store_reorder(const olap_store *store, olap_store **out, int ndim,
                        const uint32_t *old_len, const int32_t *perm);
+/* dice, the fused dice -> drillUp and drillDown of n stores — ALL stored measures of one cube, which Cube._derive and
+ * Cube.drillUp hand to the store one by one: the same tables for every store, a rule each where the operation has one
+ * (methods[i]; olap_store_drilldown_multi takes OLAP_DRILLDOWN_INTEGER_MEASURE in it and has no distributions).
+ * Stores that share cell type, default, device and rule share one plan and leave in launches of up to 8
+ * (olap_plan_run_batch, which also names what stays pair by pair behind the call); a store alone in its group runs as
+ * the single-store call does.  out[i] receives the new store of stores[i]; on an error none is returned.  Checked on
+ * the host before any device work, with the same codes and messages on a machine without a device: a NULL list or
+ * n < 0, a NULL entry ("store i of the batch is NULL"), a rule outside the seven reference methods
+ * (OLAP_ERR_UNSUPPORTED_METHOD), a tracked store ("ordered: ...": its key order needs the single-store call), ndim
+ * and the length vectors, a store whose size is not the product of old_len (OLAP_ERR_LENGTH_MISMATCH).  *launches
+ * (may be NULL): the kernel launches the call made.  Same results as n single-store calls. */
+int olap_store_dice_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *old_len,
+                          const uint32_t *new_len, const int32_t *const *sel, int *launches);
+int olap_store_dice_drillup_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                                  const uint32_t *old_len, const uint32_t *mid_len, const uint32_t *new_len,
+                                  const int32_t *const *sel, const uint32_t *const *maps, int *launches);
+int olap_store_drilldown_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                               const uint32_t *old_len, const uint32_t *new_len, const uint32_t *const *maps, int *launches);
 int olap_store_load(olap_store *store, const olap_store *other, int ndim, const uint32_t *my_len,
                     const uint32_t *his_len, const int32_t *const *his_to_mine);
 

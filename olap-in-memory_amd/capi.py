@@ -108,6 +108,9 @@ SIGNATURES = {
     "olap_store_dice": (_i32, [_vp, _pvp, _i32, _pu32, _pu32, _ppi32]),
     "olap_store_dice_drillup": (_i32, [_vp, _pvp, _i32, _pu32, _pu32, _pu32, _ppi32, _ppu32, _i32]),
     "olap_store_reorder": (_i32, [_vp, _pvp, _i32, _pu32, _pi32]),
+    "olap_store_dice_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _pu32, _ppi32, C.POINTER(C.c_int)]),
+    "olap_store_dice_drillup_multi": (_i32, [_i32, _pvp, C.POINTER(C.c_int), _pvp, _i32, _pu32, _pu32, _pu32, _ppi32, _ppu32, C.POINTER(C.c_int)]),
+    "olap_store_drilldown_multi": (_i32, [_i32, _pvp, C.POINTER(C.c_int), _pvp, _i32, _pu32, _pu32, _ppu32, C.POINTER(C.c_int)]),
     "olap_store_load": (_i32, [_vp, _vp, _i32, _pu32, _pu32, _ppi32]),
     "olap_store_select_total": (_i32, [_vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
     "olap_store_copy_select": (_i32, [_vp, _vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),

@@ -1667,6 +1667,16 @@ static int remap_for_launch(Remap &r, int vec, bool aligned) {
   return 1;
 }
 
+// Which row form of drillDown a launch over axis `a` (axis_for_launch) takes, for one pair and for a batch alike.
+// Rows off the 128-byte grid store line-aligned windows from LDS (drilldown_rows_lines_kernel) unless integer remainders
+// are spread, which only drilldown_rows_kernel does.  *whole_groups: rows are whole 16-byte groups.
+template <typename T>
+static bool drilldown_takes_lines(const olap_plan *p, const DrillUpAxis &a, int vec, bool *whole_groups) {
+  const bool spread = p->method == OLAP_SUM && p->dd.use_rounding;
+  *whole_groups = vec * sizeof(T) == 16;
+  return !spread && a.aligned16 && (a.inner * sizeof(T)) % 128 != 0 && (*whole_groups || a.inner * sizeof(T) >= 2048) && !getenv("OLAP_DD_NO_LINES");
+}
+
 // `rule` >= 0: the drillUp rule to run with instead of the one the plan was built for (a drillUp plan's tables do not
 // depend on it; nothing in the plan is written, so a cached plan stays shareable)
 template <typename T>
@@ -1734,11 +1744,8 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
         int vec;
         const DrillUpAxis a = axis_for_launch(p, all_aligned16(in, in_s, out, out_s), &vec);
         const bool divide = p->method == OLAP_SUM;
-        const bool spread = divide && p->dd.use_rounding;
-        // rows off the 128-byte grid: store line-aligned windows from LDS (drilldown_rows_lines_kernel)
-        const bool whole_groups = vec * sizeof(T) == 16;  // rows are whole 16-byte groups
-        if (!spread && a.aligned16 && (a.inner * sizeof(T)) % 128 != 0 && (whole_groups || a.inner * sizeof(T) >= 2048) &&
-            !getenv("OLAP_DD_NO_LINES"))
+        bool whole_groups;
+        if (drilldown_takes_lines<T>(p, a, vec, &whole_groups))
           e = Launch<T>::drilldown_rows_lines(hs, !whole_groups, in, in_s, out, out_s, a, divide, p->dd_longest, stream);
         else
           e = Launch<T>::drilldown_rows(hs, vec, in, in_s, out, out_s, a, divide, p->dd.use_rounding, p->dd_longest, stream);
@@ -1822,7 +1829,8 @@ static Batch<T> fill_batch(const Pairs &q, int first, int nb, const int *methods
 }
 
 // One launch for several measures (Batch<T>): drillUp plans of one axis outside the cooperative reduce regime (whose
-// workspace belongs to the plan); everything else runs pair by pair — still one call for the host.
+// workspace belongs to the plan) here, the gather family in run_gather_family_typed; everything else runs pair by
+// pair — still one call for the host.
 // `methods`: the pairs' rules differ (same plan otherwise) and go out as mixed-rule launches; OLAP_MIXED_NOT_APPLICABLE
 // (nothing launched) when this plan / these buffers need rule-by-rule launches.
 constexpr int OLAP_MIXED_NOT_APPLICABLE = -1000;
@@ -1840,6 +1848,62 @@ static int run_batch_typed(olap_plan *p, const Pairs &q, const int *methods, hip
                                  : Launch<T>::drillup_axis_batch(p->method, q.masks(), vec, b, (unsigned)nb, a, stream);
     if (methods && e == hipErrorNotSupported && first == 0) return OLAP_MIXED_NOT_APPLICABLE;
     if (e != hipSuccess) return hip_fail(e, methods ? "drillup_rows_mixed_kernel" : p->kernel_name.c_str());
+  }
+  return OLAP_OK;
+}
+
+// The gather family (K7 extended): dice and the other remapped copies, the fused dice -> drillUp and the row forms of
+// drillDown put up to kMaxBatch pairs behind one launch.  What stays pair by pair: the two-axis transpose of a reorder
+// without masks, the two-pass drillDown (its quotients live in ONE buffer of the plan), drillDown with distributions
+// and the per-cell drilldown_kernel.
+static bool gather_family_batches(const olap_plan *p, bool masks) {
+  switch (p->kind) {
+    case PLAN_GATHER: return !(p->xy_ok && !masks);
+    case PLAN_GATHER_REDUCE: return true;
+    case PLAN_DRILLDOWN: return p->dd_rows;
+    default: return false;
+  }
+}
+
+// kernel launches of one olap_plan_run of this plan
+static int launches_per_pair(const olap_plan *p) { return p->kind == PLAN_DRILLDOWN && p->dd_two_pass ? 2 : 1; }
+
+static int run_pair_by_pair(olap_plan *p, const Pairs &q, const int *methods, void *stream);
+
+// A chunk whose buffers are not all on the 16-byte grid runs pair by pair: each pair then takes the lane width (and,
+// for a dice, the kernel) its own alignment allows, exactly as olap_plan_run decides it.
+template <typename T>
+static int run_gather_family_typed(olap_plan *p, const Pairs &q, hipStream_t stream, int *launches) {
+  for (int first = 0; first < q.n; first += kMaxBatch) {
+    const int nb = std::min(q.n - first, (int)kMaxBatch);
+    bool aligned;
+    const Batch<T> b = fill_batch<T>(q, first, nb, nullptr, &aligned);
+    if (nb == 1 || !aligned) {
+      const Pairs part{nb, q.in_v + first, q.in_s ? q.in_s + first : nullptr, q.out_v + first, q.out_s ? q.out_s + first : nullptr};
+      const int rc = run_pair_by_pair(p, part, nullptr, stream);
+      if (rc) return rc;
+      *launches += nb * launches_per_pair(p);
+      continue;
+    }
+    const bool hs = q.masks();
+    hipError_t e = hipSuccess;
+    if (p->kind == PLAN_GATHER) {
+      e = p->dice_direct ? Launch<T>::dice_direct_batch(hs, b, (unsigned)nb, p->dice_rows, stream)
+                         : Launch<T>::gather_batch(hs, p->vec, b, (unsigned)nb, p->remap, stream);
+    } else if (p->kind == PLAN_GATHER_REDUCE) {
+      e = Launch<T>::gather_reduce_batch(p->method, hs, p->vec, b, (unsigned)nb, p->gr, stream);
+    } else {  // the row forms of drillDown, chosen as run_typed chooses them
+      int vec;
+      const DrillUpAxis a = axis_for_launch(p, true, &vec);
+      const bool divide = p->method == OLAP_SUM;
+      bool whole_groups;
+      if (drilldown_takes_lines<T>(p, a, vec, &whole_groups))
+        e = Launch<T>::drilldown_rows_lines_batch(hs, !whole_groups, b, (unsigned)nb, a, divide, p->dd_longest, stream);
+      else
+        e = Launch<T>::drilldown_rows_batch(hs, vec, b, (unsigned)nb, a, divide, p->dd.use_rounding, p->dd_longest, stream);
+    }
+    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+    *launches += 1;
   }
   return OLAP_OK;
 }
@@ -1895,8 +1959,9 @@ extern "C" int olap_plan_run_batch_rules(olap_plan *p, int n, const int *methods
   return run_pair_by_pair(p, q, methods, stream);
 }
 
-extern "C" int olap_plan_run_batch(olap_plan *p, int n, const void *const *in_values, const int32_t *const *in_status,
-                                   void *const *out_values, int32_t *const *out_status, void *stream) {
+// olap_plan_run_batch; *launches grows by the kernel launches made (drillUp plans are not counted: nobody asks)
+static int plan_run_batch_counted(olap_plan *p, int n, const void *const *in_values, const int32_t *const *in_status,
+                                  void *const *out_values, int32_t *const *out_status, void *stream, int *launches) {
   if (!p) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan is NULL");
   if (n < 0 || (n > 0 && (!in_values || !out_values))) return fail(OLAP_ERR_INVALID_ARGUMENT, "batch of %d: values pointer lists must not be NULL", n);
   if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
@@ -1904,12 +1969,25 @@ extern "C" int olap_plan_run_batch(olap_plan *p, int n, const void *const *in_va
   bool mixed_masks;
   const int rc = check_pairs(p, q, nullptr, &mixed_masks);
   if (rc) return rc;
-  const bool one_launch = p->kind == PLAN_DRILLUP_AXIS && p->reduce.S == 0 && !mixed_masks && n > 1;
-  if (!one_launch) return run_pair_by_pair(p, q, nullptr, stream);
   hipStream_t s = (hipStream_t)stream;
   int cur;
+  if (n > 1 && !mixed_masks && gather_family_batches(p, q.masks())) {
+    if (!begin_run(p, s, &cur)) return foreign_device(p, cur);
+    DISPATCH_DTYPE(p->dtype, T, return run_gather_family_typed<T>(p, q, s, launches));
+  }
+  const bool one_launch = p->kind == PLAN_DRILLUP_AXIS && p->reduce.S == 0 && !mixed_masks && n > 1;
+  if (!one_launch) {
+    *launches += n * launches_per_pair(p);
+    return run_pair_by_pair(p, q, nullptr, stream);
+  }
   if (!begin_run(p, s, &cur)) return foreign_device(p, cur);
   DISPATCH_DTYPE(p->dtype, T, return run_batch_typed<T>(p, q, nullptr, s));
+}
+
+extern "C" int olap_plan_run_batch(olap_plan *p, int n, const void *const *in_values, const int32_t *const *in_status,
+                                   void *const *out_values, int32_t *const *out_status, void *stream) {
+  int launches = 0;
+  return plan_run_batch_counted(p, n, in_values, in_status, out_values, out_status, stream, &launches);
 }
 
 extern "C" int olap_plan_status(olap_plan *p) {
@@ -3196,6 +3274,107 @@ extern "C" int olap_store_dice_drillup(const olap_store *s, olap_store **out, in
   }
   return run_cached(s, out, dice_drillup_key(s, method, ndim, old_len, mid_len, new_len, sel, maps),
                     [&](olap_plan **p) { return olap_dice_drillup_plan(p, s->dtype, s->default_kind, method, ndim, old_len, mid_len, new_len, sel, maps); });
+}
+
+// ---- dice, the fused dice -> drillUp and drillDown over ALL stored measures of a cube (Cube._derive calls the store
+// once per measure).  Measures that share cell type, default, size, device and rule share one plan and leave in
+// launches of up to 8 (olap_plan_run_batch); a measure alone in its group runs as the single-store call does.
+static int check_multi(int n, const olap_store *const *stores, const int *methods, bool need_methods, int method_mask, olap_store **out, int ndim,
+                       const uint32_t *old_len, const uint32_t *new_len) {
+  if (n < 0 || (n > 0 && (!stores || !out || (need_methods && !methods)))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store / method list is NULL");
+  for (int i = 0; i < n; ++i) out[i] = nullptr;
+  for (int i = 0; i < n; ++i)
+    if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  // the lists, the rules and the lengths first: refused without looking into a store
+  for (int i = 0; i < n && need_methods; ++i)
+    if ((methods[i] & ~method_mask) < OLAP_SUM || (methods[i] & ~method_mask) > OLAP_PRODUCT)
+      return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
+  const int rc = check_dims(ndim, old_len, new_len);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    if (stores[i]->track_order)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use the single-store call", i);
+  const uint64_t cells = product(old_len, ndim);
+  for (int i = 0; i < n; ++i)
+    if (stores[i]->size != cells)
+      return fail(OLAP_ERR_LENGTH_MISMATCH, "store holds %llu cells but the dimensions describe %llu", (unsigned long long)stores[i]->size, (unsigned long long)cells);
+  return OLAP_OK;
+}
+
+// key(store, rule) / build(&plan, store, rule): the operation's plan for a group, named by its first member
+template <typename Key, typename Build>
+static int run_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int *launches, Key key, Build build,
+                     bool (*keep)(const olap_plan *) = nullptr) {
+  int made = 0;
+  std::vector<char> done(n, 0);
+  for (int i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    const olap_store *s0 = stores[i];
+    const int rule = methods ? methods[i] : 0;
+    std::vector<int> members;
+    for (int j = i; j < n; ++j)
+      if (!done[j] && (!methods || methods[j] == rule) && stores[j]->dtype == s0->dtype && stores[j]->default_kind == s0->default_kind &&
+          stores[j]->device == s0->device) {
+        members.push_back(j);
+        done[j] = 1;
+      }
+    const int m = (int)members.size();
+    std::vector<const olap_store *> in(m);
+    std::vector<olap_store *> res(m, nullptr);
+    for (int k = 0; k < m; ++k) in[k] = stores[members[k]];
+    OnStoreDevice on_device__(s0);
+    PlanRef ref;
+    int rc = ref.acquire(key(s0, rule), [&](olap_plan **p) { return build(p, s0, rule); }, keep);
+    BatchBuffers b(m);
+    if (!rc) rc = check_store_cells(s0, ref.plan);
+    if (!rc) rc = b.alloc(ref.plan, in.data(), res.data());
+    if (!rc) rc = plan_run_batch_counted(ref.plan, m, b.in_v.data(), b.in_s.data(), b.out_v.data(), b.out_s.data(), nullptr, &made);
+    if (rc) {
+      drop_results(m, res.data(), rc);
+      return drop_results(n, out, rc);
+    }
+    for (int k = 0; k < m; ++k) out[members[k]] = res[k];
+  }
+  if (launches) *launches = made;
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_dice_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *old_len,
+                                     const uint32_t *new_len, const int32_t *const *sel, int *launches) {
+  if (launches) *launches = 0;
+  const int rc = check_multi(n, stores, nullptr, false, 0, out, ndim, old_len, new_len);
+  if (rc) return rc;
+  return run_multi(
+      n, stores, nullptr, out, launches, [&](const olap_store *s, int) { return dice_key(s, ndim, old_len, new_len, sel); },
+      [&](olap_plan **p, const olap_store *s, int) { return olap_dice_plan(p, s->dtype, s->default_kind, ndim, old_len, new_len, sel); });
+}
+
+extern "C" int olap_store_dice_drillup_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                                             const uint32_t *old_len, const uint32_t *mid_len, const uint32_t *new_len,
+                                             const int32_t *const *sel, const uint32_t *const *maps, int *launches) {
+  if (launches) *launches = 0;
+  int rc = check_multi(n, stores, methods, true, 0, out, ndim, old_len, mid_len);
+  if (!rc) rc = check_dims(ndim, mid_len, new_len);
+  if (rc) return rc;
+  return run_multi(
+      n, stores, methods, out, launches,
+      [&](const olap_store *s, int rule) { return dice_drillup_key(s, rule, ndim, old_len, mid_len, new_len, sel, maps); },
+      [&](olap_plan **p, const olap_store *s, int rule) {
+        return olap_dice_drillup_plan(p, s->dtype, s->default_kind, rule, ndim, old_len, mid_len, new_len, sel, maps);
+      });
+}
+
+extern "C" int olap_store_drilldown_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                                          const uint32_t *old_len, const uint32_t *new_len, const uint32_t *const *maps, int *launches) {
+  if (launches) *launches = 0;
+  const int rc = check_multi(n, stores, methods, true, OLAP_DRILLDOWN_INTEGER_MEASURE, out, ndim, old_len, new_len);
+  if (rc) return rc;
+  return run_multi(
+      n, stores, methods, out, launches, [&](const olap_store *s, int rule) { return drilldown_key(s, rule, ndim, old_len, new_len, maps); },
+      [&](olap_plan **p, const olap_store *s, int rule) {
+        return olap_drilldown_plan(p, s->dtype, s->default_kind, rule, ndim, old_len, new_len, maps, nullptr, 0);
+      },
+      [](const olap_plan *p) { return p->dev_tmp == nullptr; });
 }
 
 static int store_reorder_plain(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len, const int32_t *perm) {

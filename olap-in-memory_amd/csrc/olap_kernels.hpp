@@ -51,6 +51,8 @@ struct DrillUpAxis {
 // kMaxBatch independent (input, output) buffer pairs; blockIdx.y picks the pair.  Cube.drillUp calls the store once
 // per measure (src/cube.js:1012-1020); on cubes of a few MB a launch costs more than the bytes it moves, so the
 // measures that share a rule share a launch (olap_plan_run_batch).  A single measure is a batch of one.
+// The gather family (dice, fused dice -> drillUp, the row forms of drillDown) has batched kernels of its own beside
+// the single-pair ones: *_batch_kernel, the same body over the pair blockIdx.y picks.
 constexpr int kMaxBatch = 8;
 template <typename T>
 struct Batch {
@@ -2142,14 +2144,9 @@ struct Remap {
 // collapsed dim is contiguous in both (plan guarantees divisibility).
 // IDX: uint32_t when every index of the launch fits 32 bits (the usual case: 64-bit divisions are
 // several times dearer and the decode is most of this kernel's instruction count), else uint64_t.
-template <typename T, bool HAS_STATUS, int VEC, typename IDX = uint64_t>
-__global__ __launch_bounds__(kBlock) void gather_kernel(const T *__restrict__ in,
-                                                        const int32_t *__restrict__ st_in,
-                                                        T *__restrict__ out,
-                                                        int32_t *__restrict__ st_out, const Remap r) {
-  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (t >= r.total) return;
-  const bool def_nan = r.def_nan != 0;
+// the source offset of lane t's destination cells; false: they have no source
+template <int VEC, typename IDX>
+__device__ __forceinline__ bool gather_source(uint64_t t, const Remap &r, uint64_t &src_out) {
   IDX c = (IDX)(t * VEC);
   uint64_t src = 0;
   bool ok = true;
@@ -2168,29 +2165,82 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(const T *__restrict__ in
       }
     }
   }
+  src_out = src;
+  return ok;
+}
+
+// the loaded cells of a source (ok) or none, as the destination holds them, streamed to lane t's place
+template <typename T, bool HAS_STATUS, int VEC>
+__device__ __forceinline__ void gather_store(bool ok, const Vec<T, VEC> &v, const Vec<int32_t, VEC> &s, bool def_nan, T *__restrict__ out,
+                                             int32_t *__restrict__ st_out, uint64_t t) {
   Vec<T, VEC> ov;
   Vec<int32_t, VEC> os;
-  if (ok) {
-    // the source may be re-read (a drillDown broadcast reads each parent many times): cached loads;
-    // the destination is written once: streaming stores
-    const Vec<T, VEC> v = load_vec<T, VEC>(in + src);
-    Vec<int32_t, VEC> s;
-    if constexpr (HAS_STATUS) s = load_vec<int32_t, VEC>(st_in + src);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      const bool set = cell_is_set<T>(v.v[e], HAS_STATUS ? s.v[e] : OLAP_STATUS_SET, HAS_STATUS, def_nan);
-      ov.v[e] = set ? v.v[e] : Cell<T>::default_value(def_nan);
-      os.v[e] = set ? OLAP_STATUS_SET : 0;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      ov.v[e] = Cell<T>::default_value(def_nan);
-      os.v[e] = 0;
-    }
+  for (int e = 0; e < VEC; ++e) {
+    const bool set = ok && cell_is_set<T>(v.v[e], HAS_STATUS ? s.v[e] : OLAP_STATUS_SET, HAS_STATUS, def_nan);
+    ov.v[e] = set ? v.v[e] : Cell<T>::default_value(def_nan);
+    os.v[e] = set ? OLAP_STATUS_SET : 0;
   }
   store_stream<T, VEC>(out + t * VEC, ov);
   if (st_out) store_stream<int32_t, VEC>(st_out + t * VEC, os);
+}
+
+template <typename T, bool HAS_STATUS, int VEC, typename IDX = uint64_t>
+__device__ __forceinline__ void gather_cells(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                             int32_t *__restrict__ st_out, const Remap &r) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= r.total) return;
+  uint64_t src;
+  const bool ok = gather_source<VEC, IDX>(t, r, src);
+  // the source may be re-read (a drillDown broadcast reads each parent many times): cached loads;
+  // the destination is written once: streaming stores
+  Vec<T, VEC> v{};
+  Vec<int32_t, VEC> s{};
+  if (ok) {
+    v = load_vec<T, VEC>(in + src);
+    if constexpr (HAS_STATUS) s = load_vec<int32_t, VEC>(st_in + src);
+  }
+  gather_store<T, HAS_STATUS, VEC>(ok, v, s, r.def_nan != 0, out, st_out, t);
+}
+
+template <typename T, bool HAS_STATUS, int VEC, typename IDX = uint64_t>
+__global__ __launch_bounds__(kBlock) void gather_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                                        int32_t *__restrict__ st_out, const Remap r) {
+  gather_cells<T, HAS_STATUS, VEC, IDX>(in, st_in, out, st_out, r);
+}
+
+// K7 for the gather family: the same remap over up to kMaxBatch (input, output) pairs, blockIdx.y picks the pair (the
+// measures of a cube that share cell type and default are diced by one launch, olap_plan_run_batch).
+template <typename T, bool HAS_STATUS, int VEC, typename IDX = uint64_t>
+__global__ __launch_bounds__(kBlock) void gather_batch_kernel(const Batch<T> b, const Remap r) {
+  const uint32_t pair = blockIdx.y;
+  gather_cells<T, HAS_STATUS, VEC, IDX>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], r);
+}
+
+// The lane-loop form of the same: a lane decodes its destination index ONCE (the decode is most of gather_kernel's
+// instruction count) and moves the cells of every pair; the loads of all pairs are issued before the first store.
+// nb is uniform, so the tests on it are scalar branches.
+template <typename T, bool HAS_STATUS, int VEC, typename IDX = uint64_t>
+__global__ __launch_bounds__(kBlock) void gather_pairs_kernel(const Batch<T> b, const uint32_t nb, const Remap r) {
+  const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= r.total) return;
+  uint64_t src;
+  const bool ok = gather_source<VEC, IDX>(t, r, src);
+  Vec<T, VEC> v[kMaxBatch];
+  Vec<int32_t, VEC> s[kMaxBatch];
+#pragma unroll
+  for (int p = 0; p < kMaxBatch; ++p) {
+    v[p] = Vec<T, VEC>{};
+    s[p] = Vec<int32_t, VEC>{};
+    if ((uint32_t)p < nb && ok) {
+      v[p] = load_vec<T, VEC>(b.in[p] + src);
+      if constexpr (HAS_STATUS) s[p] = load_vec<int32_t, VEC>(b.st_in[p] + src);
+    }
+  }
+  const bool def_nan = r.def_nan != 0;
+#pragma unroll
+  for (int p = 0; p < kMaxBatch; ++p)
+    if ((uint32_t)p < nb) gather_store<T, HAS_STATUS, VEC>(ok, v[p], s[p], def_nan, b.out[p], b.st_out[p], t);
 }
 
 // K5: fused dice -> drillUp.  Iterates the OUTPUT cube; the source offset of an output cell is the
@@ -2204,11 +2254,11 @@ struct GatherReduce {
 };
 
 template <typename T, int METHOD, bool HAS_STATUS, int VEC, bool FAST>
-__global__ __launch_bounds__(kBlock) void gather_reduce_kernel(const T *__restrict__ in,
+__device__ __forceinline__ void gather_reduce_cells(const T *__restrict__ in,
                                                                const int32_t *__restrict__ st_in,
                                                                T *__restrict__ out,
                                                                int32_t *__restrict__ st_out,
-                                                               const GatherReduce a) {
+                                                               const GatherReduce &a) {
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= a.r.total) return;
   const bool def_nan = a.r.def_nan != 0;
@@ -2255,6 +2305,19 @@ __global__ __launch_bounds__(kBlock) void gather_reduce_kernel(const T *__restri
     }
   }
   lane.template finish_and_store<false>(def_nan, out, st_out, t * VEC);
+}
+
+template <typename T, int METHOD, bool HAS_STATUS, int VEC, bool FAST>
+__global__ __launch_bounds__(kBlock) void gather_reduce_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                                               int32_t *__restrict__ st_out, const GatherReduce a) {
+  gather_reduce_cells<T, METHOD, HAS_STATUS, VEC, FAST>(in, st_in, out, st_out, a);
+}
+
+// the measures of a cube that share a rule: blockIdx.y picks the pair
+template <typename T, int METHOD, bool HAS_STATUS, int VEC, bool FAST>
+__global__ __launch_bounds__(kBlock) void gather_reduce_batch_kernel(const Batch<T> b, const GatherReduce a) {
+  const uint32_t pair = blockIdx.y;
+  gather_reduce_cells<T, METHOD, HAS_STATUS, VEC, FAST>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a);
 }
 
 // load (in-memory.js:139-176): iterate the SOURCE (the other store, dense over all its cells,
@@ -2768,9 +2831,9 @@ inline bool dice_direct_fits(const DiceRows &p, DiceDirect *out) {
 }
 
 template <typename T, bool HAS_STATUS, int U>
-__global__ __launch_bounds__(kBlock) void dice_direct_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in,
+__device__ __forceinline__ void dice_direct_cells(const T *__restrict__ in, const int32_t *__restrict__ st_in,
                                                              T *__restrict__ out, int32_t *__restrict__ st_out,
-                                                             const DiceDirect a) {
+                                                             const DiceDirect &a) {
   constexpr uint32_t V = 16 / sizeof(T);
   constexpr uint32_t SPAN = U * kBlock * V;  // destination cells per workgroup
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -2886,6 +2949,19 @@ __global__ __launch_bounds__(kBlock) void dice_direct_kernel(const T *__restrict
   }
 }
 
+template <typename T, bool HAS_STATUS, int U>
+__global__ __launch_bounds__(kBlock) void dice_direct_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                                             int32_t *__restrict__ st_out, const DiceDirect a) {
+  dice_direct_cells<T, HAS_STATUS, U>(in, st_in, out, st_out, a);
+}
+
+// several measures: blockIdx.y picks the pair (every workgroup of a pair fills the same row table)
+template <typename T, bool HAS_STATUS, int U>
+__global__ __launch_bounds__(kBlock) void dice_direct_batch_kernel(const Batch<T> b, const DiceDirect a) {
+  const uint32_t pair = blockIdx.y;
+  dice_direct_cells<T, HAS_STATUS, U>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a);
+}
+
 // ======================================================================= K3: drillDown
 // in-memory.js:336-430.  One lane per NEW cell: parent offset, sibling count n and this child's
 // ordinal c (its rank among the parent's children in ascending new index) come from per-dim
@@ -2983,11 +3059,11 @@ __global__ __launch_bounds__(kBlock) void drilldown_kernel(const T *__restrict__
 constexpr uint32_t kChildrenPerBlock = 8;  // children rows written by one workgroup (measured: 4 is latency-bound, 16 no better)
 
 template <typename T, bool HAS_STATUS, int VEC>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const T *__restrict__ in,
+__device__ __forceinline__ void drilldown_rows_cells(const T *__restrict__ in,
                                                                 const int32_t *__restrict__ st_in,
                                                                 T *__restrict__ out,
                                                                 int32_t *__restrict__ st_out,
-                                                                const DrillUpAxis a, int divide, int use_rounding,
+                                                                const DrillUpAxis &a, int divide, int use_rounding,
                                                                 uint32_t segments) {
   // blockIdx.x = ((og * segments) + seg) * blocks_per_row + chunk   (uniform math)
   const uint32_t bpr = (uint32_t)a.blocks_per_row;
@@ -3046,6 +3122,19 @@ __global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const T *__restr
   }
 }
 
+template <typename T, bool HAS_STATUS, int VEC>
+__global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                                                int32_t *__restrict__ st_out, const DrillUpAxis a, int divide, int use_rounding, uint32_t segments) {
+  drilldown_rows_cells<T, HAS_STATUS, VEC>(in, st_in, out, st_out, a, divide, use_rounding, segments);
+}
+
+// the measures of a cube that share sum-or-copy and the integer flag: blockIdx.y picks the pair
+template <typename T, bool HAS_STATUS, int VEC>
+__global__ __launch_bounds__(kBlock) void drilldown_rows_batch_kernel(const Batch<T> b, const DrillUpAxis a, int divide, int use_rounding, uint32_t segments) {
+  const uint32_t pair = blockIdx.y;
+  drilldown_rows_cells<T, HAS_STATUS, VEC>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a, divide, use_rounding, segments);
+}
+
 // The same, for rows that do not start on a 128-byte line (inner * sizeof(T) % 128 != 0) and no
 // remainder spreading: the children's rows are then misaligned by a different amount each, and a
 // workgroup that stores "its" 256 slots writes partial lines at both ends of every wave (measured:
@@ -3058,11 +3147,11 @@ __global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const T *__restr
 // offset (4 LDS reads per group instead of one) and the groups that straddle a row's ends are
 // stored cell by cell — everything in between still leaves as aligned 16-byte stores.
 template <typename T, bool HAS_STATUS, int VEC, bool ANY>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_kernel(const T *__restrict__ in,
+__device__ __forceinline__ void drilldown_rows_lines_cells(const T *__restrict__ in,
                                                                       const int32_t *__restrict__ st_in,
                                                                       T *__restrict__ out,
                                                                       int32_t *__restrict__ st_out,
-                                                                      const DrillUpAxis a, int divide, uint32_t segments,
+                                                                      const DrillUpAxis &a, int divide, uint32_t segments,
                                                                       uint32_t bpr) {
   constexpr uint32_t LINE = 128 / sizeof(T);  // cells per line
   constexpr uint32_t CH = kBlock * VEC;       // cells a workgroup stores per child row
@@ -3179,6 +3268,19 @@ __global__ __launch_bounds__(kBlock) void drilldown_rows_lines_kernel(const T *_
       }
     }
   }
+}
+
+template <typename T, bool HAS_STATUS, int VEC, bool ANY>
+__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
+                                                                      int32_t *__restrict__ st_out, const DrillUpAxis a, int divide, uint32_t segments, uint32_t bpr) {
+  drilldown_rows_lines_cells<T, HAS_STATUS, VEC, ANY>(in, st_in, out, st_out, a, divide, segments, bpr);
+}
+
+// several measures: blockIdx.y picks the pair (a row's shift is taken from its own pair's output pointer)
+template <typename T, bool HAS_STATUS, int VEC, bool ANY>
+__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_batch_kernel(const Batch<T> b, const DrillUpAxis a, int divide, uint32_t segments, uint32_t bpr) {
+  const uint32_t pair = blockIdx.y;
+  drilldown_rows_lines_cells<T, HAS_STATUS, VEC, ANY>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a, divide, segments, bpr);
 }
 
 // Float cells, no distributions: every child of a parent receives the SAME value (old / n, or a
@@ -3825,6 +3927,16 @@ struct Launch {
                                          const DrillUpAxis &a, int divide, uint32_t longest_group, hipStream_t stream);
   static hipError_t drilldown_scale(bool has_status, const T *in, const int32_t *st_in, T *q, const DrillDownScale &a,
                                     hipStream_t stream);
+  // the gather family over nb (<= kMaxBatch) buffer pairs in one launch (blockIdx.y picks the pair); all pairs with or
+  // all without a mask, every argument besides the buffers as the single-pair launcher of the same name takes it
+  static hipError_t gather_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
+  static hipError_t dice_direct_batch(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &a, hipStream_t stream);
+  static hipError_t gather_reduce_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
+                                        hipStream_t stream);
+  static hipError_t drilldown_rows_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
+                                         int use_rounding, uint32_t longest_group, hipStream_t stream);
+  static hipError_t drilldown_rows_lines_batch(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+                                               int divide, uint32_t longest_group, hipStream_t stream);
   static hipError_t canonicalize(T *values, int32_t *status, uint64_t n, int def_nan, int use_status,
                                  hipStream_t stream);
   static hipError_t from_f64(const double *src, T *values, int32_t *status, uint64_t n, int def_nan,
@@ -4282,9 +4394,11 @@ hipError_t Launch<T>::drillup_generic(int method, bool has_status, const T *in, 
                     : drillup_generic_method<T, false>(method, in, st_in, out, st_out, a, stream);
 }
 
+// `b` (nb pairs): the batched launch; else the one pair (in, st_in, out, st_out).  The launchers of the gather family
+// below all take their buffers this way.
 template <typename T>
-hipError_t Launch<T>::dice_direct(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const DiceRows &p,
-                                  hipStream_t stream) {
+static hipError_t dice_direct_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
+                                     unsigned nb, const DiceRows &p, hipStream_t stream) {
   DiceDirect a;
   if (!dice_direct_fits<T>(p, &a)) return hipErrorInvalidValue;
   const int groups = dice_direct_groups();
@@ -4293,7 +4407,11 @@ hipError_t Launch<T>::dice_direct(bool has_status, const T *in, const int32_t *s
   if (n_out == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((n_out + SPAN - 1) / SPAN);
   const size_t lds = (size_t)a.rows * sizeof(int64_t);  // <= (SPAN / V + 3) entries
-#define OLAP_DD(HS, UU) hipLaunchKernelGGL((dice_direct_kernel<T, HS, UU>), blocks, kBlock, lds, stream, in, st_in, out, st_out, a)
+#define OLAP_DD(HS, UU)                                                                                                     \
+  do {                                                                                                                      \
+    if (b) hipLaunchKernelGGL((dice_direct_batch_kernel<T, HS, UU>), dim3(blocks, nb), kBlock, lds, stream, *b, a);         \
+    else hipLaunchKernelGGL((dice_direct_kernel<T, HS, UU>), blocks, kBlock, lds, stream, in, st_in, out, st_out, a);       \
+  } while (0)
   if (has_status) {
     if (groups == 1) OLAP_DD(true, 1); else if (groups == 2) OLAP_DD(true, 2); else if (groups == 8) OLAP_DD(true, 8); else OLAP_DD(true, 4);
   } else {
@@ -4304,14 +4422,40 @@ hipError_t Launch<T>::dice_direct(bool has_status, const T *in, const int32_t *s
 }
 
 template <typename T>
-hipError_t Launch<T>::gather(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                             const Remap &r, hipStream_t stream) {
+hipError_t Launch<T>::dice_direct(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const DiceRows &p,
+                                  hipStream_t stream) {
+  return dice_direct_launch<T>(has_status, in, st_in, out, st_out, nullptr, 1, p, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::dice_direct_batch(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &p, hipStream_t stream) {
+  return dice_direct_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &b, nb, p, stream);
+}
+
+// Which batched gather runs: the lane-loop form (gather_pairs_kernel) or the blockIdx.y form (gather_batch_kernel).
+// Measured on Float32 pairs without masks (profiles/multi_gather_r31.txt): the two tie within the run's spread for 2 and
+// 4 pairs and for a middle dimension, the lane loop wins at 8 pairs of an innermost-dimension dice (9.3 against 12.0 us),
+// so pairs without masks take it; masked pairs (twice the loads in flight per lane, not measured) keep blockIdx.y.
+// OLAP_GATHER_BATCH_FORM = pairs | blocks overrides that for an A/B in one process (read at every launch).
+inline bool gather_batch_lane_loop(bool has_status) {
+  const char *e = getenv("OLAP_GATHER_BATCH_FORM");
+  return e ? e[0] == 'p' : !has_status;
+}
+
+template <typename T>
+static hipError_t gather_launch(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
+                                unsigned nb, const Remap &r, hipStream_t stream) {
   if (r.total == 0) return hipSuccess;
   const unsigned grid = grid_for(r.total);
   const bool idx32 = r.total * (uint64_t)vec < 0xFFFFFFFFull;
+  const bool lane_loop = b && gather_batch_lane_loop(has_status);
 #define OLAP_G(HS, V)                                                                                                        \
   do {                                                                                                                       \
-    if (idx32) hipLaunchKernelGGL((gather_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, in, st_in, out, st_out, r);  \
+    if (b && lane_loop && idx32) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, *b, nb, r); \
+    else if (b && lane_loop) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, *b, nb, r); \
+    else if (b && idx32) hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, *b, r); \
+    else if (b) hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);     \
+    else if (idx32) hipLaunchKernelGGL((gather_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, in, st_in, out, st_out, r); \
     else hipLaunchKernelGGL((gather_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, in, st_in, out, st_out, r);        \
   } while (0)
   if (has_status) {
@@ -4323,13 +4467,28 @@ hipError_t Launch<T>::gather(bool has_status, int vec, const T *in, const int32_
   return hipGetLastError();
 }
 
+template <typename T>
+hipError_t Launch<T>::gather(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+                             const Remap &r, hipStream_t stream) {
+  return gather_launch<T>(has_status, vec, in, st_in, out, st_out, nullptr, 1, r, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::gather_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
+  return gather_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, r, stream);
+}
+
 template <typename T, int METHOD, bool HS>
-static hipError_t gather_reduce_vec(int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+static hipError_t gather_reduce_vec(int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b, unsigned nb,
                                     const GatherReduce &a, hipStream_t stream) {
   constexpr bool kAdditive = (METHOD == OLAP_SUM || METHOD == OLAP_AVERAGE || METHOD == OLAP_PARTIAL_AVERAGE);
   const bool fast = kAdditive && !HS && !a.r.def_nan;
   const unsigned grid = grid_for(a.r.total);
-#define OLAP_GR(V, F) hipLaunchKernelGGL((gather_reduce_kernel<T, METHOD, HS, V, F>), grid, kBlock, 0, stream, in, st_in, out, st_out, a)
+#define OLAP_GR(V, F)                                                                                                              \
+  do {                                                                                                                             \
+    if (b) hipLaunchKernelGGL((gather_reduce_batch_kernel<T, METHOD, HS, V, F>), dim3(grid, nb), kBlock, 0, stream, *b, a);        \
+    else hipLaunchKernelGGL((gather_reduce_kernel<T, METHOD, HS, V, F>), grid, kBlock, 0, stream, in, st_in, out, st_out, a);      \
+  } while (0)
   if constexpr (kAdditive && !HS) {
     if (fast) {
       if (vec == 4) OLAP_GR(4, true); else if (vec == 2) OLAP_GR(2, true); else OLAP_GR(1, true);
@@ -4342,17 +4501,17 @@ static hipError_t gather_reduce_vec(int vec, const T *in, const int32_t *st_in, 
 }
 
 template <typename T, bool HS>
-static hipError_t gather_reduce_method(int method, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                       const GatherReduce &a, hipStream_t stream) {
+static hipError_t gather_reduce_method(int method, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
+                                       unsigned nb, const GatherReduce &a, hipStream_t stream) {
   switch (method) {
-    case OLAP_SUM: return gather_reduce_vec<T, OLAP_SUM, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_AVERAGE: return gather_reduce_vec<T, OLAP_AVERAGE, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_HIGHEST: return gather_reduce_vec<T, OLAP_HIGHEST, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_LOWEST: return gather_reduce_vec<T, OLAP_LOWEST, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_FIRST: return gather_reduce_vec<T, OLAP_FIRST, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_LAST: return gather_reduce_vec<T, OLAP_LAST, HS>(vec, in, st_in, out, st_out, a, stream);
-    case OLAP_PARTIAL_AVERAGE: return gather_reduce_vec<T, OLAP_PARTIAL_AVERAGE, HS>(vec, in, st_in, out, st_out, a, stream);
-    default: return gather_reduce_vec<T, OLAP_PRODUCT, HS>(vec, in, st_in, out, st_out, a, stream);
+    case OLAP_SUM: return gather_reduce_vec<T, OLAP_SUM, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_AVERAGE: return gather_reduce_vec<T, OLAP_AVERAGE, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_HIGHEST: return gather_reduce_vec<T, OLAP_HIGHEST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_LOWEST: return gather_reduce_vec<T, OLAP_LOWEST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_FIRST: return gather_reduce_vec<T, OLAP_FIRST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_LAST: return gather_reduce_vec<T, OLAP_LAST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_PARTIAL_AVERAGE: return gather_reduce_vec<T, OLAP_PARTIAL_AVERAGE, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    default: return gather_reduce_vec<T, OLAP_PRODUCT, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
   }
 }
 
@@ -4360,8 +4519,16 @@ template <typename T>
 hipError_t Launch<T>::gather_reduce(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out,
                                     int32_t *st_out, const GatherReduce &a, hipStream_t stream) {
   if (a.r.total == 0) return hipSuccess;
-  return has_status ? gather_reduce_method<T, true>(method, vec, in, st_in, out, st_out, a, stream)
-                    : gather_reduce_method<T, false>(method, vec, in, st_in, out, st_out, a, stream);
+  return has_status ? gather_reduce_method<T, true>(method, vec, in, st_in, out, st_out, nullptr, 1, a, stream)
+                    : gather_reduce_method<T, false>(method, vec, in, st_in, out, st_out, nullptr, 1, a, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::gather_reduce_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
+                                          hipStream_t stream) {
+  if (a.r.total == 0) return hipSuccess;
+  return has_status ? gather_reduce_method<T, true>(method, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream)
+                    : gather_reduce_method<T, false>(method, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream);
 }
 
 template <typename T>
@@ -4463,13 +4630,18 @@ hipError_t Launch<T>::drilldown(bool has_status, const T *in, const int32_t *st_
 }
 
 template <typename T>
-hipError_t Launch<T>::drilldown_rows(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                     const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group, hipStream_t stream) {
+static hipError_t drilldown_rows_launch(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
+                                        unsigned nb, const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group,
+                                        hipStream_t stream) {
   const uint32_t segments = (longest_group + kChildrenPerBlock - 1) / kChildrenPerBlock;
   const uint64_t blocks = a.outer * a.G * a.blocks_per_row * segments;
   if (blocks == 0) return hipSuccess;
   if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-#define OLAP_DD(HS, V) hipLaunchKernelGGL((drilldown_rows_kernel<T, HS, V>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, use_rounding, segments)
+#define OLAP_DD(HS, V)                                                                                                                        \
+  do {                                                                                                                                        \
+    if (b) hipLaunchKernelGGL((drilldown_rows_batch_kernel<T, HS, V>), dim3((unsigned)blocks, nb), kBlock, 0, stream, *b, a, divide, use_rounding, segments); \
+    else hipLaunchKernelGGL((drilldown_rows_kernel<T, HS, V>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, use_rounding, segments); \
+  } while (0)
   if (has_status) {
     if (vec == 4) OLAP_DD(true, 4); else if (vec == 2) OLAP_DD(true, 2); else OLAP_DD(true, 1);
   } else {
@@ -4480,8 +4652,21 @@ hipError_t Launch<T>::drilldown_rows(bool has_status, int vec, const T *in, cons
 }
 
 template <typename T>
-hipError_t Launch<T>::drilldown_rows_lines(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                           const DrillUpAxis &a, int divide, uint32_t longest_group, hipStream_t stream) {
+hipError_t Launch<T>::drilldown_rows(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+                                     const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group, hipStream_t stream) {
+  return drilldown_rows_launch<T>(has_status, vec, in, st_in, out, st_out, nullptr, 1, a, divide, use_rounding, longest_group, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::drilldown_rows_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
+                                           int use_rounding, uint32_t longest_group, hipStream_t stream) {
+  return drilldown_rows_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, divide, use_rounding, longest_group, stream);
+}
+
+template <typename T>
+static hipError_t drilldown_rows_lines_launch(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+                                              const Batch<T> *b, unsigned nb, const DrillUpAxis &a, int divide, uint32_t longest_group,
+                                              hipStream_t stream) {
   constexpr int V = 16 / (int)sizeof(T);
   constexpr uint32_t LINE = 128 / sizeof(T);
   const uint32_t segments = (longest_group + kChildrenPerBlock - 1) / kChildrenPerBlock;
@@ -4489,11 +4674,27 @@ hipError_t Launch<T>::drilldown_rows_lines(bool has_status, bool any_shift, cons
   const uint64_t blocks = a.outer * a.G * bpr * segments;
   if (blocks == 0) return hipSuccess;
   if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-#define OLAP_DDL(HS, ANY) hipLaunchKernelGGL((drilldown_rows_lines_kernel<T, HS, V, ANY>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, segments, (uint32_t)bpr)
+#define OLAP_DDL(HS, ANY)                                                                                                                     \
+  do {                                                                                                                                        \
+    if (b) hipLaunchKernelGGL((drilldown_rows_lines_batch_kernel<T, HS, V, ANY>), dim3((unsigned)blocks, nb), kBlock, 0, stream, *b, a, divide, segments, (uint32_t)bpr); \
+    else hipLaunchKernelGGL((drilldown_rows_lines_kernel<T, HS, V, ANY>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, segments, (uint32_t)bpr); \
+  } while (0)
   if (has_status) { if (any_shift) OLAP_DDL(true, true); else OLAP_DDL(true, false); }
   else { if (any_shift) OLAP_DDL(false, true); else OLAP_DDL(false, false); }
 #undef OLAP_DDL
   return hipGetLastError();
+}
+
+template <typename T>
+hipError_t Launch<T>::drilldown_rows_lines(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+                                           const DrillUpAxis &a, int divide, uint32_t longest_group, hipStream_t stream) {
+  return drilldown_rows_lines_launch<T>(has_status, any_shift, in, st_in, out, st_out, nullptr, 1, a, divide, longest_group, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::drilldown_rows_lines_batch(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+                                                 int divide, uint32_t longest_group, hipStream_t stream) {
+  return drilldown_rows_lines_launch<T>(has_status, any_shift, nullptr, nullptr, nullptr, nullptr, &b, nb, a, divide, longest_group, stream);
 }
 
 template <typename T>

@@ -520,6 +520,46 @@ class HipStore:
                                                 _method_code(method)))
         return HipStore(0, _handle=h)
 
+    # ---- all stored measures of a cube in one call (olap_store_*_multi): (new stores in order, kernel launches made)
+    @staticmethod
+    def _multi_result(n, outs, launches):
+        return [HipStore(0, _handle=C.c_void_p(outs[i])) for i in range(n)], launches.value
+
+    @staticmethod
+    def dice_multi(stores, old_len, new_len, sel):
+        ol, nl = _u32(old_len), _u32(new_len)
+        keep, arr = _tables(sel, np.int32, C.c_int32)
+        n = len(stores)
+        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        check(capi.lib().olap_store_dice_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
+                                               C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
+    @staticmethod
+    def dice_drillup_multi(stores, methods, old_len, mid_len, new_len, sel, maps):
+        ol, ml, nl = _u32(old_len), _u32(mid_len), _u32(new_len)
+        keep_s, arr_s = _tables(sel, np.int32, C.c_int32)
+        keep_m, arr_m = _tables(maps, np.uint32, C.c_uint32)
+        n = len(stores)
+        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
+        check(capi.lib().olap_store_dice_drillup_multi(n, hs, codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), ml.ctypes.data_as(capi._pu32),
+                                                       nl.ctypes.data_as(capi._pu32), arr_s, arr_m, C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
+    @staticmethod
+    def drill_down_multi(stores, methods, old_len, new_len, maps, integer_measures=None):
+        """`integer_measures[i]`: as drill_down's integer_measure, for stores[i]"""
+        ol, nl = _u32(old_len), _u32(new_len)
+        keep, arr = _tables(maps, np.uint32, C.c_uint32)
+        n = len(stores)
+        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        flags = integer_measures or [False] * n
+        codes = (C.c_int * max(n, 1))(*[_method_code(m) | (capi.DRILLDOWN_INTEGER_MEASURE if f else 0) for m, f in zip(methods, flags)])
+        check(capi.lib().olap_store_drilldown_multi(n, hs, codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
+                                                    C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
     def reorder(self, old_len, perm):
         ol, p = _u32(old_len), _i32(perm)
         h = C.c_void_p()

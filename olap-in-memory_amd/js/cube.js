@@ -671,6 +671,31 @@ class Cube {
     return cube;
   }
 
+  /**
+   * The reference hands its measures to the store one call at a time (src/cube.js:1012-1020); here two or more stored
+   * measures go to their store class TOGETHER where it has the static many-call `name` (HipStore.diceMany, drillUpMany,
+   * drillDownMany: one device launch for the measures that can share it).  `call(Store, stores)` returns the new stores
+   * in order.  Returns them by measure id — empty for a single measure or a store class without the call: the caller
+   * then goes measure by measure.
+   */
+  _together(ids, name, call) {
+    const Store = ids.length >= 2 ? this.storedMeasures[ids[0]].constructor : null;
+    const out = {};
+    if (!Store || typeof Store[name] !== 'function') return out;
+    const results = call(Store, ids.map((id) => this.storedMeasures[id]));
+    ids.forEach((id, i) => {
+      out[id] = results[i];
+    });
+    return out;
+  }
+
+  /** Pending selections of two or more stored measures are diced together before every measure's cells are needed. */
+  _materializeStores() {
+    const ids = this.storedMeasureIds;
+    const Store = ids.length >= 2 ? this.storedMeasures[ids[0]].constructor : null;
+    if (Store && typeof Store.materializeMany === 'function') Store.materializeMany(ids.map((id) => this.storedMeasures[id]));
+  }
+
   _withDimension(index, dimension) {
     const list = this.dimensions.slice();
     list[index] = dimension;
@@ -690,17 +715,9 @@ class Cube {
       return this;
     }
     const newDimensions = this._withDimension(index, rolled);
-    // The reference rolls its measures up one store call at a time (src/cube.js:1012-1020); here the stored measures go
-    // to the device together, each with its rule for this dimension (HipStore.drillUpMany: one launch where possible).
+    // the stored measures go to the device together, each with its rule for this dimension (HipStore.drillUpMany)
     const ids = this.storedMeasureIds;
-    const rolledUp = {};
-    const Store = ids.length ? this.storedMeasures[ids[0]].constructor : null;
-    if (ids.length >= 2 && typeof Store.drillUpMany === 'function') {
-      const results = Store.drillUpMany(ids.map((id) => this.storedMeasures[id]), this.dimensions, newDimensions, ids.map((id) => this.storedMeasuresRules[id][dimensionId]));
-      ids.forEach((id, i) => {
-        rolledUp[id] = results[i];
-      });
-    }
+    const rolledUp = this._together(ids, 'drillUpMany', (Store, stores) => Store.drillUpMany(stores, this.dimensions, newDimensions, ids.map((id) => this.storedMeasuresRules[id][dimensionId])));
     return this._derive(newDimensions, (store, id) => rolledUp[id] || store.drillUp(this.dimensions, newDimensions, this.storedMeasuresRules[id][dimensionId]));
   }
 
@@ -712,7 +729,9 @@ class Cube {
     // eslint-disable-next-line eqeqeq
     if (refined == current) return this;
     const newDimensions = this._withDimension(index, refined);
-    return this._derive(newDimensions, (store, id) => store.drillDown(this.dimensions, newDimensions, this.storedMeasuresRules[id][dimensionId]));
+    const ids = this.storedMeasureIds;
+    const refinedStores = this._together(ids, 'drillDownMany', (Store, stores) => Store.drillDownMany(stores, this.dimensions, newDimensions, ids.map((id) => this.storedMeasuresRules[id][dimensionId]), []));
+    return this._derive(newDimensions, (store, id) => refinedStores[id] || store.drillDown(this.dimensions, newDimensions, this.storedMeasuresRules[id][dimensionId]));
   }
 
   // ------------------------------------------------------------------ dice / slice
@@ -720,7 +739,8 @@ class Cube {
     // eslint-disable-next-line eqeqeq
     if (dimension == this.dimensions[index]) return this;
     const newDimensions = this._withDimension(index, dimension);
-    return this._derive(newDimensions, (store) => store.dice(this.dimensions, newDimensions));
+    const diced = this._together(this.storedMeasureIds, 'diceMany', (Store, stores) => Store.diceMany(stores, this.dimensions, newDimensions));
+    return this._derive(newDimensions, (store, id) => diced[id] || store.dice(this.dimensions, newDimensions));
   }
 
   dice(dimensionId, attribute, items, reorder = false) {
@@ -784,7 +804,8 @@ class Cube {
     const rules = {};
     const wanted = (id) => measures.length === 0 || measures.includes(id);
     for (const id of this.storedMeasureIds.filter(wanted)) rules[id] = deepCopy(this.storedMeasuresRules[id]);
-    return this._derive(newDimensions, (store) => store.dice(this.dimensions, newDimensions), rules, wanted);
+    const diced = this._together(this.storedMeasureIds.filter(wanted), 'diceMany', (Store, stores) => Store.diceMany(stores, this.dimensions, newDimensions));
+    return this._derive(newDimensions, (store, id) => diced[id] || store.dice(this.dimensions, newDimensions), rules, wanted);
   }
 
   scan(dimensionIds, cb) {
@@ -831,12 +852,15 @@ class Cube {
     newDimensions[at] = newDimension;
     const rules = deepCopy(this.storedMeasuresRules);
     for (const id of Object.keys(rules)) rules[id][newDimension.id] = aggregation[id];
-    return this._derive(newDimensions, (store, id) => store.drillDown(oldDimensions, newDimensions, aggregation[id], distributions[id]), rules);
+    const ids = this.storedMeasureIds;
+    const added = this._together(ids, 'drillDownMany', (Store, stores) => Store.drillDownMany(stores, oldDimensions, newDimensions, ids.map((id) => aggregation[id]), ids.map((id) => distributions[id])));
+    return this._derive(newDimensions, (store, id) => added[id] || store.drillDown(oldDimensions, newDimensions, aggregation[id], distributions[id]), rules);
   }
 
   reorderDimensions(dimensionIds) {
     if (this.dimensions.every((d, i) => dimensionIds[i] === d.id)) return this;
     const newDimensions = dimensionIds.map((id) => this.dimensions.find((d) => d.id === id));
+    this._materializeStores();
     return this._derive(newDimensions, (store) => store.reorder(this.dimensions, newDimensions));
   }
 
@@ -903,6 +927,7 @@ class Cube {
   // ------------------------------------------------------------------ wire format ("next" row f3)
   /** Same container as the reference (src/cube.js:1135-1151); computed measures are not carried. */
   serialize() {
+    this._materializeStores();
     return toBuffer({
       dimensions: this.dimensions.map((d) => d.serialize()),
       storedMeasuresKeys: this.storedMeasureIds,

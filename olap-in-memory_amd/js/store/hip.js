@@ -132,6 +132,36 @@ function visibleDims(pending, lengths) {
 }
 
 /**
+ * The tables of a dice, the same for every measure of a cube: per dimension the old item of each new item (-1: none),
+ * the new lengths and the new size.
+ */
+function diceTables(oldDimensions, newDimensions) {
+  const sel = newDimensions.map((dim, i) => {
+    const position = oldDimensions[i].getItemsToIdx();
+    return Int32Array.from(dim.getItems(), (item) => (position[item] === undefined ? -1 : position[item]));
+  });
+  const midLen = lengthsOf(newDimensions);
+  return { oldLen: lengthsOf(oldDimensions), midLen, size: midLen.reduce((n, l) => n * l, 1), sel: sel.map(effectiveSelection) };
+}
+
+/**
+ * The pending selections among `stores` that can leave together, grouped by selection: measures diced by one
+ * HipStore.diceMany call hold the SAME table objects, so a group is an identity comparison.  `eligible(store)` narrows
+ * further.  Returns [[index, ...], ...] of the groups of two or more; sources are whole on one device and untracked.
+ */
+function pendingGroups(stores, eligible = () => true) {
+  const groups = new Map();
+  stores.forEach((store, i) => {
+    const p = store._pending;
+    if (!p || p.source.isSharded || p.source.orderTracked || !eligible(store)) return;
+    const group = groups.get(p.sel);
+    if (group === undefined) groups.set(p.sel, [i]);
+    else if (stores[group[0]]._pending.oldLen === p.oldLen && stores[group[0]]._pending.midLen === p.midLen) group.push(i);
+  });
+  return Array.from(groups.values()).filter((group) => group.length >= 2);
+}
+
+/**
  * Calls `native[method](...args)`.  A sharded measure answers in place whatever leaves its outermost
  * dimension alone (and the roll-up of that dimension itself: one collective); for the rest the C ABI
  * refuses with a message starting "sharded:" (include/olap_hip.h) and the measure is gathered onto one
@@ -360,9 +390,49 @@ class HipStore {
    */
   static drillUpMany(stores, oldDimensions, newDimensions, methods) {
     const out = new Array(stores.length);
+    const lengths = lengthsOf(oldDimensions);
+    let launches = 0;
+    // pending selections that share one selection (diceMany): a roll-up of one dimension runs fused over the SOURCE cubes
+    // (K5), all measures behind one call (addon diceDrillUpMulti -> olap_store_dice_drillup_multi: one launch per rule and
+    // cell type).  A roll-up that changes nothing stays pending, measure by measure, as drillUp leaves it.
+    const fusable = pendingGroups(stores, (store) => visibleDims(store._pending, lengths) !== null);
+    if (fusable.length > 0) {
+      const addon = backend.load();
+      const maps = newDimensions.map((dim, i) => asU32(oldDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
+      const rolled = maps.filter((map, i) => map.length !== newDimensions[i].numItems || map.some((g, k) => g !== k)).length;
+      for (const group of rolled === 1 ? fusable : []) {
+        const p = stores[group[0]]._pending;
+        const at = visibleDims(p, lengths);
+        const newLen = Uint32Array.from(p.midLen, () => 1); // dimensions the cube has dropped keep their single item
+        const allMaps = Array.from(p.midLen, () => Uint32Array.of(0));
+        at.forEach((d, v) => {
+          newLen[d] = newDimensions[v].numItems;
+          allMaps[d] = maps[v];
+        });
+        const codes = Int32Array.from(group, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
+        const launchesOut = new Int32Array(1);
+        const natives = addon.diceDrillUpMulti(group.map((i) => stores[i]._pending.source), codes, p.oldLen, p.midLen, newLen, p.sel, allMaps, launchesOut);
+        group.forEach((i, j) => {
+          out[i] = stores[i]._wrap(natives[j]);
+        });
+        launches += launchesOut[0];
+      }
+      // more than one dimension rolled up: no fused form, the measures are diced together first
+      if (rolled > 1) {
+        HipStore.materializeMany(stores);
+        launches += HipStore.lastBatchLaunches;
+      }
+    }
+    // pending selections whose dimensions no longer line up with the cube's cannot fuse either
+    const unfusable = stores.filter((store, i) => !out[i] && store._pending && !store._pending.source.isSharded && visibleDims(store._pending, lengths) === null);
+    if (unfusable.length >= 2) {
+      HipStore.materializeMany(unfusable);
+      launches += HipStore.lastBatchLaunches;
+    }
+    HipStore.lastBatchLaunches = launches;
     const together = [];
     stores.forEach((store, i) => {
-      const native = store._pending ? null : store._nativeStore;
+      const native = store._pending || out[i] ? null : store._nativeStore;
       if (native && !native.isSharded && !native.orderTracked) together.push(i);
     });
     if (together.length >= 2) {
@@ -389,32 +459,113 @@ class HipStore {
     return this._wrap(onShards(this._native, 'drillDown', [lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, (method === 'sum' ? 0 : 4) | integerMeasure, weights]));
   }
 
+  /**
+   * drillDown of the stored measures of one cube, each by its own rule — what Cube.drillDown and Cube.addDimension ask
+   * of every stored measure in turn.  Measures held whole on one device, untracked and without a distribution go to the
+   * device TOGETHER (addon drillDownMulti -> olap_store_drilldown_multi: one launch for up to 8 measures that share cell
+   * type, default, sum-or-copy and the integer remainder rule); the others take drillDown one by one.  Pending
+   * selections are diced together first (materializeMany).  Returns the new stores in the order given.
+   */
+  static drillDownMany(stores, oldDimensions, newDimensions, methods, distributionsPerStore = []) {
+    const out = new Array(stores.length);
+    HipStore.materializeMany(stores);
+    let launches = HipStore.lastBatchLaunches;
+    const together = [];
+    stores.forEach((store, i) => {
+      const native = store._pending ? null : store._nativeStore;
+      if (native && !native.isSharded && !native.orderTracked && !distributionsPerStore[i]) together.push(i);
+    });
+    if (together.length >= 2) {
+      const maps = oldDimensions.map((dim, i) => asU32(newDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
+      // the codes drillDown() hands over: sum or a copy, and the remainder rule of the DECLARED type
+      const codes = Int32Array.from(together, (i) => (methods[i] === undefined || methods[i] === 'sum' ? 0 : 4) |
+        (stores[i]._type === 'int32' || stores[i]._type === 'uint32' ? 0x100 : 0));
+      const launchesOut = new Int32Array(1);
+      const natives = backend.load().drillDownMulti(together.map((i) => stores[i]._nativeStore), codes, lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, launchesOut);
+      together.forEach((i, j) => {
+        out[i] = stores[i]._wrap(natives[j]);
+      });
+      launches += launchesOut[0];
+    }
+    HipStore.lastBatchLaunches = launches;
+    stores.forEach((store, i) => {
+      if (!out[i]) out[i] = store.drillDown(oldDimensions, newDimensions, methods[i], distributionsPerStore[i]);
+    });
+    return out;
+  }
+
   /** in-memory.js:213-263 — the new dimensions' item ORDER decides where cells land */
   dice(oldDimensions, newDimensions) {
-    const sel = newDimensions.map((dim, i) => {
-      const position = oldDimensions[i].getItemsToIdx();
-      return Int32Array.from(dim.getItems(), (item) => (position[item] === undefined ? -1 : position[item]));
-    });
-    const midLen = lengthsOf(newDimensions);
-    const size = midLen.reduce((n, l) => n * l, 1);
-    let composed = sel.map(effectiveSelection);
-    const at = this._pending ? visibleDims(this._pending, lengthsOf(oldDimensions)) : null;
+    return this._diceWith(diceTables(oldDimensions, newDimensions), new Map());
+  }
+
+  /**
+   * dice by ready-made tables (diceTables).  `compositions`: what the tables give on top of a pending selection, by that
+   * selection — measures that share one (diceMany) compose it once and go on sharing the result.
+   */
+  _diceWith(tables, compositions) {
+    const { oldLen, midLen, size, sel } = tables;
+    const at = this._pending ? visibleDims(this._pending, oldLen) : null;
     if (at) {
       // dice of a pending dice: compose the selections, still nothing is materialised
       const p = this._pending;
-      const all = p.sel.slice();
-      const allLen = Uint32Array.from(p.midLen);
-      at.forEach((d, v) => {
-        all[d] = Int32Array.from(composed[v], (j) => (j < 0 ? -1 : p.sel[d][j]));
-        allLen[d] = midLen[v];
-      });
-      return new HipStore(size, this._type, this._defaultValue, { source: p.source, oldLen: p.oldLen, midLen: allLen, sel: all });
+      let composed = compositions.get(p.sel);
+      if (composed === undefined || composed.from !== p.midLen) {
+        const all = p.sel.slice();
+        const allLen = Uint32Array.from(p.midLen);
+        at.forEach((d, v) => {
+          all[d] = Int32Array.from(sel[v], (j) => (j < 0 ? -1 : p.sel[d][j]));
+          allLen[d] = midLen[v];
+        });
+        composed = { from: p.midLen, midLen: allLen, sel: all };
+        compositions.set(p.sel, composed);
+      }
+      return new HipStore(size, this._type, this._defaultValue, { source: p.source, oldLen: p.oldLen, midLen: composed.midLen, sel: composed.sel });
     }
     const source = this._native; // (materialises a pending selection whose dimensions no longer line up)
     // a tracked measure: the diced store has an order of its own that the next operation must see
-    if (!source.isSharded && source.orderTracked) return this._wrap(source.dice(lengthsOf(oldDimensions), midLen, composed));
+    if (!source.isSharded && source.orderTracked) return this._wrap(source.dice(oldLen, midLen, sel));
     this._lent = true;
-    return new HipStore(size, this._type, this._defaultValue, { source, oldLen: lengthsOf(oldDimensions), midLen, sel: composed });
+    return new HipStore(size, this._type, this._defaultValue, { source, oldLen, midLen, sel });
+  }
+
+  /**
+   * dice of the stored measures of one cube — what Cube._diced asks of every stored measure in turn: the selection is
+   * computed once and every pending store this creates holds the SAME table objects, so that what follows (drillUpMany,
+   * materializeMany) finds the measures that can leave in one launch by comparing identities.  Nothing is launched here
+   * (selections stay pending, as dice() leaves them); tracked measures are diced at once, as dice() does.
+   */
+  static diceMany(stores, oldDimensions, newDimensions) {
+    const tables = diceTables(oldDimensions, newDimensions);
+    const compositions = new Map();
+    // (selections whose dimensions no longer line up with the cube's are diced first — together: the only launches here)
+    HipStore.materializeMany(stores.filter((store) => store._pending && !visibleDims(store._pending, tables.oldLen)));
+    return stores.map((store) => store._diceWith(tables, compositions));
+  }
+
+  /**
+   * Runs the pending selections among `stores` that share one selection (diceMany) as ONE device call per group (addon
+   * diceMulti -> olap_store_dice_multi: one launch for up to 8 measures of one cell type and default) and installs the
+   * results, so that an operation that needs the cells of every measure does not dice them one by one.  A selection on
+   * its own, or over a sharded source, stays pending.
+   */
+  static materializeMany(stores) {
+    let launches = 0;
+    const groups = pendingGroups(stores);
+    if (groups.length > 0) {
+      const addon = backend.load();
+      for (const group of groups) {
+        const p = stores[group[0]]._pending;
+        const launchesOut = new Int32Array(1);
+        const natives = addon.diceMulti(group.map((i) => stores[i]._pending.source), p.oldLen, p.midLen, p.sel, launchesOut);
+        group.forEach((i, j) => {
+          stores[i]._nativeStore = natives[j];
+          stores[i]._pending = null;
+        });
+        launches += launchesOut[0];
+      }
+    }
+    HipStore.lastBatchLaunches = launches;
   }
 
   /**
@@ -658,6 +809,9 @@ class HipStore {
 }
 
 HipStore.lastSelectPath = null;
+// kernel launches the device reported for the last many-call (diceMany: 0 where every selection stays pending; materializeMany,
+// drillDownMany and the pending selections of drillUpMany: what diceMulti / drillDownMulti / diceDrillUpMulti launched)
+HipStore.lastBatchLaunches = null;
 // 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the
 // launches it reported; never reset here
 HipStore.lastTotalsPath = null;
@@ -674,4 +828,4 @@ HipStore.lastMaterializePath = null;
 
 module.exports = HipStore;
 module.exports.toPlainArray = toPlainArray;
-module.exports._internals = { visibleDims, effectiveSelection }; // host-side logic, unit-tested without a device
+module.exports._internals = { visibleDims, effectiveSelection, diceTables, pendingGroups }; // host-side logic, unit-tested without a device

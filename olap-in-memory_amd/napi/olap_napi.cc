@@ -1032,6 +1032,125 @@ static napi_value DrillUpMulti(napi_env env, napi_callback_info info) {
   return arr;
 }
 
+// ---- diceMulti / diceDrillUpMulti / drillDownMulti: ALL stored measures of a cube behind one call (olap_store_*_multi)
+namespace {
+// the Store[] and (where the operation has rules) the Int32Array with a rule per store
+struct MultiArgs {
+  std::vector<const olap_store *> stores;
+  const int *methods = nullptr;
+  // false with an exception pending, or — *usage_error — arguments of the wrong shape
+  bool decode(napi_env env, napi_value list, const napi_value *rules, bool *usage_error) {
+    *usage_error = true;
+    bool is_arr = false;
+    if (napi_is_array(env, list, &is_arr) != napi_ok || !is_arr) return false;
+    uint32_t n = 0;
+    napi_get_array_length(env, list, &n);
+    if (rules) {
+      napi_typedarray_type mt;
+      size_t n_methods = 0;
+      void *mdata = nullptr;
+      bool is_ta = false;
+      if (napi_is_typedarray(env, *rules, &is_ta) != napi_ok || !is_ta || napi_get_typedarray_info(env, *rules, &mt, &n_methods, &mdata, nullptr, nullptr) != napi_ok ||
+          mt != napi_int32_array || n_methods != n)
+        return false;
+      static const int none = 0;
+      methods = n ? (const int *)mdata : &none;
+    }
+    *usage_error = false;
+    stores.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      napi_value e;
+      if (napi_get_element(env, list, i, &e) != napi_ok) return false;
+      stores[i] = unwrap(env, e);
+      if (!stores[i]) return false;
+    }
+    return true;
+  }
+};
+}  // namespace
+
+static napi_value wrap_new_stores(napi_env env, std::vector<olap_store *> &outs) {
+  const uint32_t n = (uint32_t)outs.size();
+  napi_value arr;
+  NAPI_OK(napi_create_array_with_length(env, n, &arr));
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value w = wrap_new_store(env, outs[i]);
+    if (!w) {
+      for (uint32_t j = i + 1; j < n; ++j) olap_store_destroy(outs[j]);
+      return nullptr;
+    }
+    napi_set_element(env, arr, i, w);
+  }
+  return arr;
+}
+
+// diceMulti(stores: Store[], oldLen, newLen, sel: Int32Array[], launchesOut?: Int32Array) -> Store[]
+static napi_value DiceMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "diceMulti(stores: Store[], oldLen: Uint32Array, newLen: Uint32Array, sel: Int32Array[], launchesOut?: Int32Array)";
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs m;
+  bool bad = true;
+  if (argc < 4 || !a.decode(env, argv[1], argv[2], argv[3])) return bad_args(env, usage);
+  if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int launches = 0;
+  int rc = olap_store_dice_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
+                                 (const int32_t *const *)a.ptrs.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 4) set_path(env, argv[4], launches);
+  return wrap_new_stores(env, outs);
+}
+
+// diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?) -> Store[]
+static napi_value DiceDrillUpMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?: Int32Array)";
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs m;
+  std::vector<uint32_t> new_len;
+  std::vector<std::vector<uint32_t>> maps;
+  bool bad = true;
+  if (argc < 7 || !a.decode(env, argv[2], argv[3], argv[5]) || !get_u32_vec(env, argv[4], new_len) || !get_tables(env, argv[6], maps) ||
+      new_len.size() != a.a_len.size() || maps.size() != a.a_len.size())
+    return bad_args(env, usage);
+  if (!m.decode(env, argv[0], &argv[1], &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<const uint32_t *> map_ptrs;
+  for (auto &t : maps) map_ptrs.push_back(t.empty() ? &OpArgs::dummy : t.data());
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int launches = 0;
+  int rc = olap_store_dice_drillup_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
+                                         new_len.data(), (const int32_t *const *)a.ptrs.data(), map_ptrs.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 7) set_path(env, argv[7], launches);
+  return wrap_new_stores(env, outs);
+}
+
+// drillDownMulti(stores: Store[], methods: Int32Array, oldLen, newLen, maps: Uint32Array[], launchesOut?) -> Store[]
+// methods[i]: the code Store.drillDown takes (0 = sum, else a copy; | 0x100: a measure declared int32 / uint32); no distributions
+static napi_value DrillDownMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "drillDownMulti(stores: Store[], methods: Int32Array, oldLen: Uint32Array, newLen: Uint32Array, maps: Uint32Array[], launchesOut?: Int32Array)";
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs m;
+  bool bad = true;
+  if (argc < 5 || !a.decode(env, argv[2], argv[3], argv[4])) return bad_args(env, usage);
+  if (!m.decode(env, argv[0], &argv[1], &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int launches = 0;
+  int rc = olap_store_drilldown_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
+                                      a.ptrs.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 5) set_path(env, argv[5], launches);
+  return wrap_new_stores(env, outs);
+}
+
 // ---- ShardedStore: a measure split along dimension 0 over the devices of setDevices() -----------
 // Wraps olap_sharded_store* (include/olap_hip.h, "Multi-GPU").  Method names and argument shapes are
 // those of Store, so the JS HipStore drives either; what a sharded store cannot do in place throws an
@@ -1605,6 +1724,9 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"totalsFormula", nullptr, TotalsFormula, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"totalsReport", nullptr, TotalsReport, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillUpMulti", nullptr, DrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"diceMulti", nullptr, DiceMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"diceDrillUpMulti", nullptr, DiceDrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"heldBytes", nullptr, HeldBytes, nullptr, nullptr, nullptr, napi_default, nullptr},
