@@ -3564,7 +3564,45 @@ struct FormulaProgram {
 };
 
 __device__ __forceinline__ bool js_truthy(double v) { return v == v && v != 0.0; }
-__device__ __forceinline__ double js_round(double v) { return floor(v + 0.5); }  // Math.round: halves go up
+// Math.round: the nearest integer, halves towards +inf, and -0 on [-0.5, -0].  The distance to floor(v) decides (v + 0.5 would
+// round 0.49999999999999994 and the odd integers above 2^52 up); an infinity or a NaN fails the comparison and stays.
+__device__ __forceinline__ double js_round(double v) {
+  const double f = floor(v);
+  return copysign(v - f >= 0.5 ? f + 1.0 : f, v);
+}
+// a^b by squaring for an integral |b| <= 64, where it is certain: true when every product came out without a rounding
+// error (the fma gives each one's), so that `out` is the exact power for b >= 0 and its correctly rounded reciprocal for
+// b < 0.  The library's pow is a unit in the last place off at 6^8, 10^17, 10^-5, ...: an integer power that a double can
+// hold has to be that integer (2 ^ n into an Int32 measure), and roundTo needs the correctly rounded 10^k.  |a| >= 2^-8
+// keeps every product and its error term away from underflow; an overflow makes the error term a NaN, which is not 0.
+__device__ __forceinline__ bool pow_by_exact_products(double a, double b, double &out) {
+  const double m = fabs(b);
+  if (!(m <= 64.0) || m != trunc(m) || !(fabs(a) >= 0x1p-8)) return false;
+  bool exact = true;
+  double r = 1.0, x = a;
+  for (unsigned n = (unsigned)m; n != 0;) {
+    if (n & 1u) {
+      const double p = r * x;
+      exact &= fma(r, x, -p) == 0.0;
+      r = p;
+    }
+    n >>= 1;
+    if (n != 0) {
+      const double p = x * x;
+      exact &= fma(x, x, -p) == 0.0;
+      x = p;
+    }
+  }
+  out = b < 0.0 ? 1.0 / r : r;
+  return exact;
+}
+// Math.pow: NaN for x ^ NaN and (+-1) ^ +-inf, which C99 answers with 1; the exact power where products give it; else C's pow
+__device__ __forceinline__ double js_pow(double a, double b) {
+  if (b != b || (fabs(a) == 1.0 && fabs(b) == __builtin_inf())) return __builtin_nan("");
+  double r;
+  if (pow_by_exact_products(a, b, r)) return r;
+  return pow(a, b);
+}
 
 // getValue(i) of input k (in-memory.js:118-120): the stored value, or the default where unset
 __device__ __forceinline__ double formula_input(const FormulaProgram &p, int k, uint64_t i) {
@@ -3642,11 +3680,11 @@ __device__ __forceinline__ double formula_binary(int op, double a, double b) {
   if constexpr (ALL) {
     switch (op) {
       case F_MOD: return fmod(a, b);
-      case F_POW: return pow(a, b);
+      case F_POW: return js_pow(a, b);
       case F_ATAN2: return atan2(a, b);
       case F_HYPOT: return hypot(a, b);
-      default: {  // F_ROUNDTO
-        const double f = pow(10.0, trunc(b));
+      default: {  // F_ROUNDTO: roundTo(v, digits) of formula.js, whose `digits || 0` reads NaN digits as 0
+        const double f = js_pow(10.0, b != b ? 0.0 : trunc(b));  // exact for |digits| <= 22
         return js_round(a * f) / f;
       }
     }

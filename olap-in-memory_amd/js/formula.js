@@ -38,8 +38,10 @@ const OP = {
   ABS: 20, CEIL: 21, FLOOR: 22, ROUND: 23, TRUNC: 24, SQRT: 25, CBRT: 26, EXP: 27, LN: 28, LOG10: 29, LOG2: 30, SIGN: 31,
   SIN: 32, COS: 33, TAN: 34, ASIN: 35, ACOS: 36, ATAN: 37, NOT: 38,
 };
-// Opcodes whose device result is bit-equal to evaluate() here (DESIGN.md §3 K8).  ROUND (js_round is floor(v + 0.5)),
-// POW, ROUNDTO, HYPOT, ATAN2, CBRT and the transcendental ops differ from V8's Math in the last bits; SCALAR reads a
+// Opcodes whose device result is bit-equal to evaluate() here (DESIGN.md §3 K8).  POW, ROUNDTO, HYPOT, ATAN2, CBRT and the
+// transcendental ops follow Math's rules for NaN, the infinities and the zeros but may differ from V8 in the last bit
+// (about 1 ulp from the correctly rounded value on either side: profiles/formula_ulp_r33.txt).  ROUND is exact Math.round on
+// the device (tests/test_formula_ops_gpu.py) and stays out only because K8 has not been routed to it; SCALAR reads a
 // measure total, which getSingleData cannot.
 const DEVICE_EXACT_OPS = new Set([OP.CONST, OP.INPUT, OP.ADD, OP.SUB, OP.MUL, OP.DIV, OP.MOD, OP.NEG, OP.NANADD, OP.SELECT, OP.MIN, OP.MAX, OP.ISNAN,
   OP.ABS, OP.CEIL, OP.FLOOR, OP.TRUNC, OP.SQRT, OP.SIGN, OP.NOT]);

@@ -585,7 +585,8 @@ describe('computed measures (formula.js + the device interpreter)', () => {
     cube.setData('cc', Array.from({ length: n }, () => (rnd() < 0.3 ? NaN_ : Math.floor(rnd() * 21) - 10)));
     const formulas = ['aa + bb * cc - 2', 'aa / bb', 'cc % 3 + 2 ^ bb', '-aa || bb', 'abs aa + sqrt(bb) + floor(aa / 3) + ceil aa + round(aa) + trunc aa',
       'min(aa, bb, cc) + max(aa, 1) * hypot(bb, cc)', 'bb ? aa : cc', 'if(isNaN(aa), bb, aa) + not bb', 'exp(bb / 4) + ln(bb + 1) + log10(bb + 1) + log2(bb + 2) + cbrt aa',
-      'sin aa + cos(aa) * tan(bb / 10) + atan2(aa, bb) + asin(bb / 8) + acos(bb / 8) + atan cc', 'sign(aa) * roundTo(aa, 2) + PI * E', 'aa__total + bb__total / cc__total', '(aa + 1) * (bb - 2) / (cc + 0.5) ^ 2'];
+      'sin aa + cos(aa) * tan(bb / 10) + atan2(aa, bb) + asin(bb / 8) + acos(bb / 8) + atan cc', 'sign(aa) * roundTo(aa, 2) + PI * E', 'aa__total + bb__total / cc__total', '(aa + 1) * (bb - 2) / (cc + 0.5) ^ 2',
+      '1 ^ aa', 'round(aa / 7)'];
     // An INDEPENDENT restatement of the same formulas as plain JavaScript closures (neither formula.js's parser nor its
     // evaluator is involved): expr-eval's published operator semantics (^ = Math.pow, % = JS remainder, ?: and if() by
     // truthiness, `not`, roundTo(x, n) = round at n decimals), with `||` and isNaN exactly as the reference
@@ -599,7 +600,7 @@ describe('computed measures (formula.js + the device interpreter)', () => {
       (a, b) => Math.exp(b / 4) + Math.log(b + 1) + Math.log10(b + 1) + Math.log2(b + 2) + Math.cbrt(a),
       (a, b, c) => Math.sin(a) + Math.cos(a) * Math.tan(b / 10) + Math.atan2(a, b) + Math.asin(b / 8) + Math.acos(b / 8) + Math.atan(c),
       (a) => Math.sign(a) * roundTo(a, 2) + Math.PI * Math.E, (a, b, c, t) => t.aa__total + t.bb__total / t.cc__total,
-      (a, b, c) => ((a + 1) * (b - 2)) / Math.pow(c + 0.5, 2)];
+      (a, b, c) => ((a + 1) * (b - 2)) / Math.pow(c + 0.5, 2), (a) => Math.pow(1, a), (a) => Math.round(a / 7)];
     const close = (x, y) => (Number.isNaN(x) && Number.isNaN(y)) || x === y || Math.abs(x - y) <= 1e-12 * Math.max(1, Math.abs(x));
     formulas.forEach((formula, k) => {
       cube.createComputedMeasure(`f_${k}x`, formula);
