@@ -156,6 +156,14 @@ int olap_reorder_plan(olap_plan **plan, int dtype, int default_kind, int ndim,
 int olap_load_plan(olap_plan **plan, int dtype, int my_default_kind, int his_default_kind,
                    int ndim, const uint32_t *my_len, const uint32_t *his_len,
                    const int32_t *const *his_to_mine);
+/* The same between stores whose cell types may differ: `in` holds cells of his_dtype, `out` cells of my_dtype.  The
+ * result is, cell for cell and mask for mask, what olap_convert_from_f64 of the other store's float64 values into
+ * my_dtype cells under HIS default, followed by a same-type load, leaves — in one pass, without a cube in between
+ * ("load between cell types").  his_dtype == my_dtype is olap_load_plan.  Between cell types a load with
+ * only the last dimension permuted runs the remapped-innermost form (olap_plan_kernel_name says so). */
+int olap_load_plan_typed(olap_plan **plan, int my_dtype, int his_dtype, int my_default_kind, int his_default_kind,
+                         int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                         const int32_t *const *his_to_mine);
 
 uint64_t olap_plan_in_cells(const olap_plan *plan);
 uint64_t olap_plan_out_cells(const olap_plan *plan);
@@ -172,10 +180,11 @@ int olap_plan_run(olap_plan *plan, const void *in_values, const int32_t *in_stat
  * few MB a launch costs more than the bytes it moves.  drillUp plans of one dimension outside the few-outputs reduce
  * regime run up to 8 pairs per LAUNCH (the grid's second dimension picks the pair; pairs must all carry masks or
  * none).  So do the gather family (a dice without masks as a lane loop over the pairs instead): dice plans (and a
- * reorder that runs as a gather), fused dice -> drillUp plans and
- * the row forms of drillDown, when every buffer of the eight starts on a 16-byte boundary.  Pair by pair behind this
+ * reorder that runs as a gather or through bricks), fused dice -> drillUp plans and
+ * the row forms of drillDown and every form of load (`in` the other stores, `out` the stores updated in place; between
+ * cell types too), when every buffer of the eight starts on a 16-byte boundary.  Pair by pair behind this
  * one call: pairs with mixed masks, buffers off the 16-byte grid, the two-pass drillDown, drillDown with distributions
- * and its per-cell form, the two-axis transpose, load and the other drillUp regimes.  in_status / out_status may be
+ * and its per-cell form, the two-axis transpose of a reorder and the other drillUp regimes.  in_status / out_status may be
  * NULL (no masks) or lists whose entries may be NULL.  Same results as n olap_plan_run calls. */
 int olap_plan_run_batch(olap_plan *plan, int n, const void *const *in_values, const int32_t *const *in_status,
                         void *const *out_values, int32_t *const *out_status, void *stream);
@@ -472,6 +481,26 @@ int olap_store_drilldown_multi(int n, const olap_store *const *stores, const int
                                const uint32_t *old_len, const uint32_t *new_len, const uint32_t *const *maps, int *launches);
 int olap_store_load(olap_store *store, const olap_store *other, int ndim, const uint32_t *my_len,
                     const uint32_t *his_len, const int32_t *const *his_to_mine);
+/* targets[i].load(sources[i]) for n pairs — the measures two cubes share, which Cube.hydrateFromCube hands to the store
+ * one by one: the same lengths and maps for every pair, targets updated in place.  Cell types may differ WITHIN a pair
+ * (olap_load_plan_typed; n == 1 is the way to load across cell types: olap_store_load refuses them).  Pairs that share
+ * (source type, target type, both defaults, device) share one plan, kept by the plan cache (its tables are built and
+ * uploaded once per group, and not at all when the call is repeated), and leave in launches of up to 8
+ * (olap_plan_run_batch).  Checked on the host before any device work, with the same codes and messages on a machine
+ * without a device, in this order: a NULL list or n < 0; a NULL entry ("store i of the batch is NULL"); ndim and the
+ * length vectors; a map entry outside my dimension (OLAP_ERR_INDEX_RANGE, the message of olap_load_plan); a store whose
+ * size is not the product of its lengths (OLAP_ERR_LENGTH_MISMATCH); a pair on two devices; a tracked target
+ * ("ordered: ...": its key order needs the single-store call); a target that appears twice or is also a source
+ * (OLAP_ERR_INVALID_ARGUMENT).  On such an error no target has been touched.  *launches (may be NULL): the kernel
+ * launches the call made. */
+int olap_store_load_multi(int n, olap_store *const *targets, const olap_store *const *sources, int ndim,
+                          const uint32_t *my_len, const uint32_t *his_len,
+                          const int32_t *const *his_to_mine, int *launches);
+/* olap_store_reorder of n stores — all stored measures of one cube (Cube.reorderDimensions) — with the checks, the
+ * grouping and the results of the *_multi calls above.  Reorders that run as a gather or through bricks leave in
+ * launches of up to 8; the two-axis transpose runs pair by pair behind the call. */
+int olap_store_reorder_multi(int n, const olap_store *const *stores, olap_store **out, int ndim,
+                             const uint32_t *old_len, const int32_t *perm, int *launches);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: a cube partitioned along its OUTERMOST dimension.  Row-major layout

@@ -57,6 +57,7 @@ SIGNATURES = {
     "olap_dice_drillup_plan": (_i32, [_pvp, _i32, _i32, _i32, _i32, _pu32, _pu32, _pu32, _ppi32, _ppu32]),
     "olap_reorder_plan": (_i32, [_pvp, _i32, _i32, _i32, _pu32, _pi32]),
     "olap_load_plan": (_i32, [_pvp, _i32, _i32, _i32, _i32, _pu32, _pu32, _ppi32]),
+    "olap_load_plan_typed": (_i32, [_pvp, _i32, _i32, _i32, _i32, _i32, _pu32, _pu32, _ppi32]),
     "olap_plan_in_cells": (_u64, [_vp]),
     "olap_plan_out_cells": (_u64, [_vp]),
     "olap_plan_kernel_name": (C.c_char_p, [_vp]),
@@ -112,6 +113,8 @@ SIGNATURES = {
     "olap_store_dice_drillup_multi": (_i32, [_i32, _pvp, C.POINTER(C.c_int), _pvp, _i32, _pu32, _pu32, _pu32, _ppi32, _ppu32, C.POINTER(C.c_int)]),
     "olap_store_drilldown_multi": (_i32, [_i32, _pvp, C.POINTER(C.c_int), _pvp, _i32, _pu32, _pu32, _ppu32, C.POINTER(C.c_int)]),
     "olap_store_load": (_i32, [_vp, _vp, _i32, _pu32, _pu32, _ppi32]),
+    "olap_store_load_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _pu32, _ppi32, C.POINTER(C.c_int)]),
+    "olap_store_reorder_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _pi32, C.POINTER(C.c_int)]),
     "olap_store_select_total": (_i32, [_vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
     "olap_store_copy_select": (_i32, [_vp, _vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),
     "olap_formula_select_total": (_i32, [_pi32, _i32, _pdbl, _i32, _i32, _pvp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl,

@@ -233,6 +233,7 @@ enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD,
 struct olap_plan {
   PlanKind kind;
   int dtype = 0, def_nan = 0, his_def_nan = 0, method = 0;
+  int his_dtype = -1;                      // load between cell types: the other store's (>= 0 and != dtype: load_convert kernels)
   uint64_t in_cells = 0, out_cells = 0;
   int vec = 1;
   DrillUpAxis axis{};
@@ -1349,13 +1350,9 @@ extern "C" int olap_reorder_plan(olap_plan **out, int dtype, int default_kind, i
 }
 
 // ---- load -----------------------------------------------------------------------------------
-extern "C" int olap_load_plan(olap_plan **out, int dtype, int my_default_kind, int his_default_kind,
-                              int ndim, const uint32_t *my_len, const uint32_t *his_len,
-                              const int32_t *const *his_to_mine) {
-  if (!out) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan out-pointer is NULL");
-  *out = nullptr;
+// the lengths and the maps of a load, checked on the host (the plan builders and olap_store_load_multi)
+static int check_load_maps(int ndim, const uint32_t *my_len, const uint32_t *his_len, const int32_t *const *his_to_mine) {
   int rc;
-  if ((rc = check_dtype(dtype)) || (rc = check_default(my_default_kind)) || (rc = check_default(his_default_kind))) return rc;
   if ((rc = check_dims(ndim, my_len, his_len))) return rc;
   if (ndim > 0 && !his_to_mine) return fail(OLAP_ERR_INVALID_ARGUMENT, "his_to_mine is NULL");
   for (int d = 0; d < ndim; ++d) {
@@ -1364,11 +1361,38 @@ extern "C" int olap_load_plan(olap_plan **out, int dtype, int my_default_kind, i
       if (his_to_mine[d][j] >= 0 && (uint32_t)his_to_mine[d][j] >= my_len[d])
         return fail(OLAP_ERR_INDEX_RANGE, "load map of dimension %d: entry %u = %d is outside this store's dimension (%u items)", d, j, his_to_mine[d][j], my_len[d]);
   }
+  return OLAP_OK;
+}
+
+static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_default_kind, int his_default_kind, int ndim, const uint32_t *my_len,
+                           const uint32_t *his_len, const int32_t *const *his_to_mine);
+
+extern "C" int olap_load_plan(olap_plan **out, int dtype, int my_default_kind, int his_default_kind,
+                              int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                              const int32_t *const *his_to_mine) {
+  return load_plan_build(out, dtype, dtype, my_default_kind, his_default_kind, ndim, my_len, his_len, his_to_mine);
+}
+
+extern "C" int olap_load_plan_typed(olap_plan **out, int my_dtype, int his_dtype, int my_default_kind, int his_default_kind,
+                                    int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                                    const int32_t *const *his_to_mine) {
+  return load_plan_build(out, my_dtype, his_dtype, my_default_kind, his_default_kind, ndim, my_len, his_len, his_to_mine);
+}
+
+static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_default_kind, int his_default_kind, int ndim, const uint32_t *my_len,
+                           const uint32_t *his_len, const int32_t *const *his_to_mine) {
+  if (!out) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan out-pointer is NULL");
+  *out = nullptr;
+  int rc;
+  if ((rc = check_dtype(dtype)) || (rc = check_dtype(his_dtype)) || (rc = check_default(my_default_kind)) || (rc = check_default(his_default_kind))) return rc;
+  if ((rc = check_load_maps(ndim, my_len, his_len, his_to_mine))) return rc;
   if ((rc = require_device())) return rc;
   olap_plan *p = new (std::nothrow) olap_plan();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
+  const bool convert = his_dtype != dtype;
   p->kind = PLAN_LOAD;
   p->dtype = dtype;
+  p->his_dtype = his_dtype;
   p->def_nan = my_default_kind == OLAP_DEFAULT_NAN;
   p->his_def_nan = his_default_kind == OLAP_DEFAULT_NAN;
   p->in_cells = product(his_len, ndim);
@@ -1390,8 +1414,9 @@ extern "C" int olap_load_plan(olap_plan **out, int dtype, int my_default_kind, i
     stride *= my_len[d];
   }
   // the innermost dimension's items in another order and nothing else: rows rearranged through LDS
+  // (same-type loads only: between cell types the remapped-innermost form of load_convert runs it)
   bool permuted_rows = false;
-  if (ndim >= 1 && !getenv("OLAP_LOAD_NO_PERMUTE")) {
+  if (ndim >= 1 && !convert && !getenv("OLAP_LOAD_NO_PERMUTE")) {
     const int last = ndim - 1;
     const uint64_t row_cap = kTileBytes / olap_dtype_size(dtype);
     bool ok = !dims[last].arithmetic && his_len[last] == my_len[last] && his_len[last] >= 2 && his_len[last] <= row_cap;
@@ -1427,10 +1452,26 @@ extern "C" int olap_load_plan(olap_plan **out, int dtype, int my_default_kind, i
       permuted_rows = true;
     }
   }
+  if (convert && dims.empty()) {  // one cell: the load_convert kernels decode at least one dimension
+    RemapDim one{};
+    one.len = 1, one.arithmetic = true, one.stride = 1;
+    dims.push_back(one);
+  }
   // (16-byte lanes when the innermost merged run is contiguous in both stores: finish_remap checks it)
-  if ((rc = finish_remap(p, dims, p->in_cells, true))) {
+  if ((rc = finish_remap(p, dims, p->in_cells, !convert))) {
     olap_plan_destroy(p);
     return rc;
+  }
+  if (convert) {  // a lane holds 16 bytes of HIS: lanes when the contiguous run is a whole number of them
+    Remap &r = p->remap;
+    const uint32_t v = (uint32_t)(16 / olap_dtype_size(his_dtype));
+    if (r.tab_off[r.nd - 1] < 0 && r.stride[r.nd - 1] == 1 && r.len[r.nd - 1] % v == 0) {
+      p->vec = (int)v;
+      r.total = p->in_cells / v;
+    }
+    p->kernel_name = p->vec > 1 ? "load_convert (16-byte lanes of the other store)" : "load_convert (16-byte runs of the other store)";
+    *out = p;
+    return OLAP_OK;
   }
   p->kernel_name = permuted_rows ? "load_permute_rows_kernel"
                    : p->vec > 1  ? "load_scatter (16-byte lanes)"
@@ -1721,6 +1762,12 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
       break;
     }
     case PLAN_LOAD: {
+      if (p->his_dtype != p->dtype) {  // between cell types: a batch of one
+        Remap r = p->remap;
+        const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
+        e = launch_load_convert(p->his_dtype, p->dtype, hs, vec, &in_v, &in_s, &out_v, &out_s, 1, r, stream);
+        break;
+      }
       if (p->lperm.perm) {
         e = Launch<T>::load_permute(hs, in, in_s, out, out_s, p->lperm, stream);
         break;
@@ -1852,8 +1899,9 @@ static int run_batch_typed(olap_plan *p, const Pairs &q, const int *methods, hip
   return OLAP_OK;
 }
 
-// The gather family (K7 extended): dice and the other remapped copies, the fused dice -> drillUp and the row forms of
-// drillDown put up to kMaxBatch pairs behind one launch.  What stays pair by pair: the two-axis transpose of a reorder
+// The gather family (K7 extended): dice and the other remapped copies, the fused dice -> drillUp, the row forms of
+// drillDown and load (every form, between cell types too: `in` is the other store, `out` this one) put up to kMaxBatch
+// pairs behind one launch, and so do the brick forms of reorder.  What stays pair by pair: the two-axis transpose of a reorder
 // without masks, the two-pass drillDown (its quotients live in ONE buffer of the plan), drillDown with distributions
 // and the per-cell drilldown_kernel.
 static bool gather_family_batches(const olap_plan *p, bool masks) {
@@ -1861,6 +1909,8 @@ static bool gather_family_batches(const olap_plan *p, bool masks) {
     case PLAN_GATHER: return !(p->xy_ok && !masks);
     case PLAN_GATHER_REDUCE: return true;
     case PLAN_DRILLDOWN: return p->dd_rows;
+    case PLAN_LOAD: return true;
+    case PLAN_BRICK: return !(p->xy_ok && !masks);
     default: return false;
   }
 }
@@ -1892,6 +1942,14 @@ static int run_gather_family_typed(olap_plan *p, const Pairs &q, hipStream_t str
                          : Launch<T>::gather_batch(hs, p->vec, b, (unsigned)nb, p->remap, stream);
     } else if (p->kind == PLAN_GATHER_REDUCE) {
       e = Launch<T>::gather_reduce_batch(p->method, hs, p->vec, b, (unsigned)nb, p->gr, stream);
+    } else if (p->kind == PLAN_BRICK) {
+      e = Launch<T>::reorder_brick_batch(hs, b, (unsigned)nb, p->brick, p->n_bricks, stream);
+    } else if (p->kind == PLAN_LOAD) {  // the forms as run_typed chooses them
+      if (p->his_dtype != p->dtype)
+        e = launch_load_convert(p->his_dtype, p->dtype, hs, p->vec, q.in_v + first, q.in_s ? q.in_s + first : nullptr, q.out_v + first,
+                                q.out_s ? q.out_s + first : nullptr, (unsigned)nb, p->remap, stream);
+      else if (p->lperm.perm) e = Launch<T>::load_permute_batch(hs, b, (unsigned)nb, p->lperm, stream);
+      else e = Launch<T>::load_scatter_batch(hs, p->vec, b, (unsigned)nb, p->remap, stream);
     } else {  // the row forms of drillDown, chosen as run_typed chooses them
       int vec;
       const DrillUpAxis a = axis_for_launch(p, true, &vec);
@@ -3419,4 +3477,104 @@ extern "C" int olap_store_load(olap_store *s, const olap_store *other, int ndim,
   if (!rc) rc = store_load_plain(s, other, ndim, my_len, his_len, his_to_mine);
   if (!rc) rc = order_after_load(s, other, ndim, my_len, his_len, his_to_mine);
   return rc;
+}
+
+// ---- reorder and load over ALL stored measures of a cube (Cube.reorderDimensions and Cube.hydrateFromCube call the
+// store once per measure)
+extern "C" int olap_store_reorder_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *old_len,
+                                        const int32_t *perm, int *launches) {
+  if (launches) *launches = 0;
+  int rc = check_multi(n, stores, nullptr, false, 0, out, ndim, old_len, old_len);
+  if (rc) return rc;
+  if (ndim > 0 && !perm) return fail(OLAP_ERR_INVALID_ARGUMENT, "perm is NULL");
+  return run_multi(
+      n, stores, nullptr, out, launches, [&](const olap_store *s, int) { return reorder_key(s, ndim, old_len, perm); },
+      [&](olap_plan **p, const olap_store *s, int) { return olap_reorder_plan(p, s->dtype, s->default_kind, ndim, old_len, perm); });
+}
+
+static PlanKey load_key(const olap_store *mine, const olap_store *his, int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                        const int32_t *const *his_to_mine) {
+  PlanKey key;
+  if (bad_dims(ndim, my_len, his_len) || !tables_readable(ndim, his_len, his_to_mine, his_to_mine)) return key;
+  key.i32('L');
+  key.i32(mine->dtype), key.i32(his->dtype), key.i32(mine->default_kind), key.i32(his->default_kind), key.i32(ndim);
+  key.u32s(my_len, ndim), key.u32s(his_len, ndim);
+  key.tables((const uint32_t *const *)his_to_mine, his_len, ndim);
+  return key;
+}
+
+// The arguments of olap_store_load_multi, refused on the host before any device work (so also without a device), in
+// the order the header lists them.
+static int check_load_multi(int n, olap_store *const *targets, const olap_store *const *sources, int ndim, const uint32_t *my_len,
+                            const uint32_t *his_len, const int32_t *const *his_to_mine) {
+  if (n < 0 || (n > 0 && (!targets || !sources))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
+  for (int i = 0; i < n; ++i)
+    if (!targets[i] || !sources[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  int rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  if (rc) return rc;
+  const uint64_t mine = product(my_len, ndim), his = product(his_len, ndim);
+  for (int i = 0; i < n; ++i)
+    if (sources[i]->size != his || targets[i]->size != mine) return fail(OLAP_ERR_LENGTH_MISMATCH, "load: store sizes do not match the dimensions");
+  for (int i = 0; i < n; ++i)
+    if (targets[i]->device != sources[i]->device)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "load: the stores live on different devices (%d and %d)", targets[i]->device, sources[i]->device);
+  for (int i = 0; i < n; ++i)
+    if (targets[i]->track_order)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use the single-store call", i);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j)
+      if ((j > i && targets[j] == targets[i]) || sources[j] == targets[i])
+        return fail(OLAP_ERR_INVALID_ARGUMENT, "load: store %d of the batch is a target twice, or a target and a source", i);
+  return OLAP_OK;
+}
+
+// targets[i].load(sources[i]) for every i (in-memory.js:139-176), cell types free within a pair.  Pairs that share
+// (source type, target type, both defaults, device) share one cached plan and leave in launches of up to 8.
+extern "C" int olap_store_load_multi(int n, olap_store *const *targets, const olap_store *const *sources, int ndim, const uint32_t *my_len,
+                                     const uint32_t *his_len, const int32_t *const *his_to_mine, int *launches) {
+  if (launches) *launches = 0;
+  int rc = check_load_multi(n, targets, sources, ndim, my_len, his_len, his_to_mine);
+  if (rc) return rc;
+  int made = 0;
+  std::vector<char> done(n > 0 ? n : 1, 0);
+  for (int i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    olap_store *t0 = targets[i];
+    const olap_store *s0 = sources[i];
+    std::vector<int> members;
+    for (int j = i; j < n; ++j)
+      if (!done[j] && targets[j]->dtype == t0->dtype && sources[j]->dtype == s0->dtype && targets[j]->default_kind == t0->default_kind &&
+          sources[j]->default_kind == s0->default_kind && targets[j]->device == t0->device) {
+        members.push_back(j);
+        done[j] = 1;
+      }
+    const int m = (int)members.size();
+    OnStoreDevice on_device__(t0);
+    PlanRef ref;
+    rc = ref.acquire(load_key(t0, s0, ndim, my_len, his_len, his_to_mine), [&](olap_plan **p) {
+      return olap_load_plan_typed(p, t0->dtype, s0->dtype, t0->default_kind, s0->default_kind, ndim, my_len, his_len, his_to_mine);
+    });
+    if (rc) return rc;
+    std::vector<const void *> in_v(m);
+    std::vector<const int32_t *> in_s(m);
+    std::vector<void *> out_v(m);
+    std::vector<int32_t *> out_s(m);
+    for (int k = 0; k < m; ++k) {
+      olap_store *t = targets[members[k]];
+      drop_lazy_status(t);
+      in_v[k] = sources[members[k]]->values;
+      in_s[k] = mask_needed(sources[members[k]]);
+      out_v[k] = t->values;
+      out_s[k] = t->status;
+    }
+    rc = plan_run_batch_counted(ref.plan, m, in_v.data(), in_s.data(), out_v.data(), out_s.data(), nullptr, &made);
+    if (rc) return rc;
+    for (int k = 0; k < m; ++k) {  // what order_after_load records for an untracked store
+      olap_store *t = targets[members[k]];
+      t->maybe_nonempty = true;
+      t->hi_index = t->size ? t->size - 1 : 0;
+    }
+  }
+  if (launches) *launches = made;
+  return OLAP_OK;
 }

@@ -4,7 +4,8 @@
 // coalesced 16 B/lane accesses, enough loads in flight per lane, >> 256 workgroups per launch,
 // and reading each input cell exactly once.  No MFMA: there is no contraction here.
 //
-// Instantiated once per cell type in olap_kernels_{f32,f64,i32,u32}.hip.
+// Instantiated once per cell type in olap_kernels_{f32,f64,i32,u32}.hip; the kernels that load between two cell types
+// live in olap_kernels_load_typed.hip.
 #pragma once
 
 #include <cstdlib>
@@ -2327,10 +2328,10 @@ __global__ __launch_bounds__(kBlock) void gather_reduce_batch_kernel(const Batch
 // streamed (every cell is read exactly once), and the index is decoded in 32-bit arithmetic when the other cube has
 // fewer than 2^32 cells (a 64-bit division is a long software sequence on CDNA).
 template <typename T, bool HAS_STATUS, int VEC, typename IDX>
-__global__ __launch_bounds__(kBlock) void load_scatter_kernel(const T *__restrict__ his,
-                                                              const int32_t *__restrict__ his_st,
-                                                              T *__restrict__ mine,
-                                                              int32_t *__restrict__ mine_st, const Remap r) {
+__device__ __forceinline__ void load_scatter_cells(const T *__restrict__ his,
+                                                   const int32_t *__restrict__ his_st,
+                                                   T *__restrict__ mine,
+                                                   int32_t *__restrict__ mine_st, const Remap &r) {
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t >= r.total) return;
   const bool def_nan = r.def_nan != 0, his_nan = r.src_def_nan != 0;
@@ -2382,6 +2383,21 @@ __global__ __launch_bounds__(kBlock) void load_scatter_kernel(const T *__restric
   if (mine_st) store_stream<int32_t, VEC>(mine_st + dst, os);
 }
 
+template <typename T, bool HAS_STATUS, int VEC, typename IDX>
+__global__ __launch_bounds__(kBlock) void load_scatter_kernel(const T *__restrict__ his,
+                                                              const int32_t *__restrict__ his_st,
+                                                              T *__restrict__ mine,
+                                                              int32_t *__restrict__ mine_st, const Remap r) {
+  load_scatter_cells<T, HAS_STATUS, VEC, IDX>(his, his_st, mine, mine_st, r);
+}
+
+// the measures of a cube hydrated from the measures of another one: blockIdx.y picks the (his, mine) pair
+template <typename T, bool HAS_STATUS, int VEC, typename IDX>
+__global__ __launch_bounds__(kBlock) void load_scatter_batch_kernel(const Batch<T> b, const Remap r) {
+  const uint32_t pair = blockIdx.y;
+  load_scatter_cells<T, HAS_STATUS, VEC, IDX>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], r);
+}
+
 // The same when the INNERMOST dimension itself is remapped (his items of the last dimension sit elsewhere in mine):
 // no 16 contiguous bytes on my side, but a lane still reads R consecutive cells of his with one 16-byte streaming load
 // and decodes its index ONCE — the divisions are what bounds the one-cell-per-lane form (~100 instructions per 4 bytes:
@@ -2391,8 +2407,8 @@ __global__ __launch_bounds__(kBlock) void load_scatter_kernel(const T *__restric
 // loads of his: 299 us.  Neither the stores nor the loads are what costs here but the dependent chain index -> table
 // entry -> address -> cell per lane.)
 template <typename T, bool HAS_STATUS, typename IDX>
-__global__ __launch_bounds__(kBlock) void load_scatter_run_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
-                                                                  int32_t *__restrict__ mine_st, const Remap r, const uint64_t n_cells) {
+__device__ __forceinline__ void load_scatter_run_cells(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
+                                                       int32_t *__restrict__ mine_st, const Remap &r, const uint64_t n_cells) {
   constexpr int R = 16 / sizeof(T);
   const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (t * R >= n_cells) return;
@@ -2463,6 +2479,18 @@ __global__ __launch_bounds__(kBlock) void load_scatter_run_kernel(const T *__res
   }
 }
 
+template <typename T, bool HAS_STATUS, typename IDX>
+__global__ __launch_bounds__(kBlock) void load_scatter_run_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
+                                                                  int32_t *__restrict__ mine_st, const Remap r, const uint64_t n_cells) {
+  load_scatter_run_cells<T, HAS_STATUS, IDX>(his, his_st, mine, mine_st, r, n_cells);
+}
+
+template <typename T, bool HAS_STATUS, typename IDX>
+__global__ __launch_bounds__(kBlock) void load_scatter_run_batch_kernel(const Batch<T> b, const Remap r, const uint64_t n_cells) {
+  const uint32_t pair = blockIdx.y;
+  load_scatter_run_cells<T, HAS_STATUS, IDX>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], r, n_cells);
+}
+
 // The innermost dimension's items PERMUTED (the same items in another order — hydrating from a cube whose last
 // dimension lists them differently) and every other dimension left alone: his row r is my row r with its cells
 // rearranged.  A workgroup stages a tile of whole rows: 16-byte streaming loads of HIS cells, every cell written to
@@ -2480,8 +2508,8 @@ struct LoadPermute {
 };
 
 template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(kBlock) void load_permute_rows_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
-                                                                   int32_t *__restrict__ mine_st, const LoadPermute a) {
+__device__ __forceinline__ void load_permute_rows_cells(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
+                                                        int32_t *__restrict__ mine_st, const LoadPermute &a) {
   constexpr uint32_t V = 16 / sizeof(T);
   constexpr uint32_t kCells = kTileBytes / sizeof(T);
   constexpr int NL = kCells / V / kBlock;
@@ -2557,6 +2585,19 @@ __global__ __launch_bounds__(kBlock) void load_permute_rows_kernel(const T *__re
   }
 }
 
+template <typename T, bool HAS_STATUS>
+__global__ __launch_bounds__(kBlock) void load_permute_rows_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
+                                                                   int32_t *__restrict__ mine_st, const LoadPermute a) {
+  load_permute_rows_cells<T, HAS_STATUS>(his, his_st, mine, mine_st, a);
+}
+
+// (every pair of a batch stages its own tile: the LDS layout depends on "mine has a mask", which a batch shares)
+template <typename T, bool HAS_STATUS>
+__global__ __launch_bounds__(kBlock) void load_permute_rows_batch_kernel(const Batch<T> b, const LoadPermute a) {
+  const uint32_t pair = blockIdx.y;
+  load_permute_rows_cells<T, HAS_STATUS>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a);
+}
+
 // ======================================================================= K4: reorder as a brick transpose
 // in-memory.js:178-211.  When the output's fastest dimension is not the input's fastest one a plain
 // gather reads 4 B per cache line.  Here a workgroup owns a BRICK: a small range of every dimension
@@ -2594,10 +2635,10 @@ struct Brick {
 __device__ __forceinline__ uint32_t lds_pad(uint32_t e) { return e + (e >> 5); }
 
 template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(1024) void reorder_brick_kernel(const T *__restrict__ in,
-                                                               const int32_t *__restrict__ st_in,
-                                                               T *__restrict__ out,
-                                                               int32_t *__restrict__ st_out, const Brick b) {
+__device__ __forceinline__ void reorder_brick_cells(const T *__restrict__ in,
+                                                    const int32_t *__restrict__ st_in,
+                                                    T *__restrict__ out,
+                                                    int32_t *__restrict__ st_out, const Brick &b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   T *tile = reinterpret_cast<T *>(lds_raw);
   const size_t tile_bytes = ((size_t)lds_pad(b.elems) * sizeof(T) + 15) & ~(size_t)15;
@@ -2691,6 +2732,21 @@ __global__ __launch_bounds__(1024) void reorder_brick_kernel(const T *__restrict
   }
 }
 
+template <typename T, bool HAS_STATUS>
+__global__ __launch_bounds__(1024) void reorder_brick_kernel(const T *__restrict__ in,
+                                                               const int32_t *__restrict__ st_in,
+                                                               T *__restrict__ out,
+                                                               int32_t *__restrict__ st_out, const Brick b) {
+  reorder_brick_cells<T, HAS_STATUS>(in, st_in, out, st_out, b);
+}
+
+// the measures of a cube reordered together: blockIdx.y picks the pair
+template <typename T, bool HAS_STATUS>
+__global__ __launch_bounds__(1024) void reorder_brick_batch_kernel(const Batch<T> p, const Brick b) {
+  const uint32_t pair = blockIdx.y;
+  reorder_brick_cells<T, HAS_STATUS>(p.in[pair], p.st_in[pair], p.out[pair], p.st_out[pair], b);
+}
+
 // 16-byte form.  Cells 4q..4q+3 of the read order are adjacent in the source (one 16 B load, one
 // 16 B LDS store); a write group is 4 adjacent destination cells whose LDS positions come packed
 // from the table.  LDS position of read-order cell e: e + 4*(e/32) (keeps groups 16 B aligned and
@@ -2698,10 +2754,10 @@ __global__ __launch_bounds__(1024) void reorder_brick_kernel(const T *__restrict
 __device__ __forceinline__ uint32_t lds_pad4(uint32_t e) { return e + ((e >> 5) << 2); }
 
 template <typename T, bool HAS_STATUS, int UB>
-__global__ __launch_bounds__(1024) void reorder_brick4_kernel(const T *__restrict__ in,
-                                                                const int32_t *__restrict__ st_in,
-                                                                T *__restrict__ out,
-                                                                int32_t *__restrict__ st_out, const Brick b) {
+__device__ __forceinline__ void reorder_brick4_cells(const T *__restrict__ in,
+                                                     const int32_t *__restrict__ st_in,
+                                                     T *__restrict__ out,
+                                                     int32_t *__restrict__ st_out, const Brick &b) {
   static_assert(sizeof(T) == 4, "16-byte groups of 4 cells");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   T *tile = reinterpret_cast<T *>(lds_raw);
@@ -2776,6 +2832,20 @@ __global__ __launch_bounds__(1024) void reorder_brick4_kernel(const T *__restric
       }
     }
   }
+}
+
+template <typename T, bool HAS_STATUS, int UB>
+__global__ __launch_bounds__(1024) void reorder_brick4_kernel(const T *__restrict__ in,
+                                                                const int32_t *__restrict__ st_in,
+                                                                T *__restrict__ out,
+                                                                int32_t *__restrict__ st_out, const Brick b) {
+  reorder_brick4_cells<T, HAS_STATUS, UB>(in, st_in, out, st_out, b);
+}
+
+template <typename T, bool HAS_STATUS, int UB>
+__global__ __launch_bounds__(1024) void reorder_brick4_batch_kernel(const Batch<T> p, const Brick b) {
+  const uint32_t pair = blockIdx.y;
+  reorder_brick4_cells<T, HAS_STATUS, UB>(p.in[pair], p.st_in[pair], p.out[pair], p.st_out[pair], b);
 }
 
 // dice of ONE dimension over rows that are not whole 16-byte groups, any row length of at least one
@@ -3975,6 +4045,10 @@ struct Launch {
                                          int use_rounding, uint32_t longest_group, hipStream_t stream);
   static hipError_t drilldown_rows_lines_batch(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
                                                int divide, uint32_t longest_group, hipStream_t stream);
+  // load over nb pairs (his = in, mine = out); the run form needs every `in` / `st_in` on the 16-byte grid
+  static hipError_t reorder_brick_batch(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream);
+  static hipError_t load_scatter_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
+  static hipError_t load_permute_batch(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream);
   static hipError_t canonicalize(T *values, int32_t *status, uint64_t n, int def_nan, int use_status,
                                  hipStream_t stream);
   static hipError_t from_f64(const double *src, T *values, int32_t *status, uint64_t n, int def_nan,
@@ -4001,6 +4075,12 @@ struct Launch {
   static hipError_t set_cell(T *values, int32_t *status, uint64_t index, double value, int is_null, int def_nan,
                              hipStream_t stream);
 };
+
+// load between stores of DIFFERENT cell types (olap_kernels_load_typed.hip: the twelve type pairs live in a translation
+// unit of their own): nb (his, mine) pairs in one launch, blockIdx.y picks the pair.  vec > 1: every lane's 16 bytes of
+// his are contiguous in mine (r.total counts lanes of vec cells); vec == 1: the run form (r.total counts cells).
+hipError_t launch_load_convert(int his_dtype, int my_dtype, bool has_status, int vec, const void *const *his, const int32_t *const *his_st,
+                               void *const *mine, int32_t *const *mine_st, unsigned nb, const Remap &r, hipStream_t stream);
 
 inline size_t lds_pad_host(size_t e) { return e + (e >> 5); }
 inline unsigned grid_for(uint64_t threads) { return (unsigned)((threads + kBlock - 1) / kBlock); }
@@ -4569,28 +4649,38 @@ hipError_t Launch<T>::gather_reduce_batch(int method, bool has_status, int vec, 
                     : gather_reduce_method<T, false>(method, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream);
 }
 
+// p == nullptr: the one pair given by its four pointers; else the nb pairs of *p (blockIdx.y)
 template <typename T>
-hipError_t Launch<T>::reorder_brick(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                    const Brick &b, uint64_t n_bricks, hipStream_t stream) {
+static hipError_t reorder_brick_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *p, unsigned nb,
+                                       const Brick &b, uint64_t n_bricks, hipStream_t stream) {
   if (n_bricks == 0) return hipSuccess;
   if constexpr (sizeof(T) == 4) {
-    const bool aligned = (((uintptr_t)in | (uintptr_t)out | (uintptr_t)st_in | (uintptr_t)st_out) & 15u) == 0;
+    bool aligned = (((uintptr_t)in | (uintptr_t)out | (uintptr_t)st_in | (uintptr_t)st_out) & 15u) == 0;
+    for (unsigned i = 0; p && i < nb; ++i)
+      aligned = aligned && (((uintptr_t)p->in[i] | (uintptr_t)p->out[i] | (uintptr_t)p->st_in[i] | (uintptr_t)p->st_out[i]) & 15u) == 0;
     if (b.quad && aligned) {
       const size_t padded = (size_t)(b.elems + ((b.elems >> 5) << 2)) * 4;
       const size_t lds4 = padded * (has_status ? 2 : 1);
       // above 64 KiB of dynamic LDS the kernel has to be told once (bricks of 10^4 cells with the mask: 90 KiB)
-      static PerDeviceFlag raised;
-      if (!raised.test_and_set()) {
-        hipError_t e1 = hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      static PerDeviceFlag raised, raised_batch;
+      if (!(p ? raised_batch : raised).test_and_set()) {
+        hipError_t e1 = p ? hipFuncSetAttribute((const void *)reorder_brick4_batch_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+                          : hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = p ? hipFuncSetAttribute((const void *)reorder_brick4_batch_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+                          : hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (e1 != hipSuccess) return e1;
         if (e2 != hipSuccess) return e2;
       }
       unsigned threads4 = kBlock;  // measured: 512 and 1024 lanes lose on the [10]^8 reversal, 512 gains 7 % on a 2-D transpose
       if (const char *e = getenv("OLAP_BRICK_THREADS")) threads4 = (unsigned)atoi(e);
       // groups in flight per lane: 2, 4 and 10 measure the same (the 400-byte runs, not latency, set the pace)
-      if (has_status) hipLaunchKernelGGL((reorder_brick4_kernel<T, true, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
-      else hipLaunchKernelGGL((reorder_brick4_kernel<T, false, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
+      if (p) {
+        if (has_status) hipLaunchKernelGGL((reorder_brick4_batch_kernel<T, true, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, *p, b);
+        else hipLaunchKernelGGL((reorder_brick4_batch_kernel<T, false, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, *p, b);
+      } else {
+        if (has_status) hipLaunchKernelGGL((reorder_brick4_kernel<T, true, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
+        else hipLaunchKernelGGL((reorder_brick4_kernel<T, false, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
+      }
       return hipGetLastError();
     }
   }
@@ -4599,42 +4689,72 @@ hipError_t Launch<T>::reorder_brick(bool has_status, const T *in, const int32_t 
   unsigned threads = kBlock;  // larger workgroups for larger bricks bought nothing (tools/sweep.py)
   if (const char *e = getenv("OLAP_BRICK_THREADS")) threads = (unsigned)atoi(e);
   if (lds > 48 * 1024) {  // bricks sized for the 16-byte form, run here because a buffer is not 16 B aligned
-    static PerDeviceFlag raised_scalar;
-    if (!raised_scalar.test_and_set()) {
-      hipError_t e1 = hipFuncSetAttribute((const void *)reorder_brick_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      hipError_t e2 = hipFuncSetAttribute((const void *)reorder_brick_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    static PerDeviceFlag raised_scalar, raised_scalar_batch;
+    if (!(p ? raised_scalar_batch : raised_scalar).test_and_set()) {
+      hipError_t e1 = p ? hipFuncSetAttribute((const void *)reorder_brick_batch_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+                        : hipFuncSetAttribute((const void *)reorder_brick_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      hipError_t e2 = p ? hipFuncSetAttribute((const void *)reorder_brick_batch_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
+                        : hipFuncSetAttribute((const void *)reorder_brick_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       if (e1 != hipSuccess) return e1;
       if (e2 != hipSuccess) return e2;
     }
   }
-  if (has_status) hipLaunchKernelGGL((reorder_brick_kernel<T, true>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
-  else hipLaunchKernelGGL((reorder_brick_kernel<T, false>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
+  if (p) {
+    if (has_status) hipLaunchKernelGGL((reorder_brick_batch_kernel<T, true>), dim3((unsigned)n_bricks, nb), threads, lds, stream, *p, b);
+    else hipLaunchKernelGGL((reorder_brick_batch_kernel<T, false>), dim3((unsigned)n_bricks, nb), threads, lds, stream, *p, b);
+  } else {
+    if (has_status) hipLaunchKernelGGL((reorder_brick_kernel<T, true>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
+    else hipLaunchKernelGGL((reorder_brick_kernel<T, false>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
+  }
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t Launch<T>::load_scatter(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st,
-                                   const Remap &r, hipStream_t stream) {
+hipError_t Launch<T>::reorder_brick(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
+                                    const Brick &b, uint64_t n_bricks, hipStream_t stream) {
+  return reorder_brick_launch<T>(has_status, in, st_in, out, st_out, nullptr, 1, b, n_bricks, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::reorder_brick_batch(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream) {
+  return reorder_brick_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &p, nb, b, n_bricks, stream);
+}
+
+// b == nullptr: the one pair given by its four pointers; else the nb pairs of *b (blockIdx.y)
+template <typename T>
+static hipError_t load_scatter_launch(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const Batch<T> *b,
+                                      unsigned nb, const Remap &r, hipStream_t stream) {
   if (r.total == 0) return hipSuccess;
   const bool idx32 = r.total * (uint64_t)vec < 0xFFFFFFFFull;
-  if (vec == 1 && r.nd >= 1 && (((uintptr_t)his | (uintptr_t)his_st) & 15u) == 0 && !getenv("OLAP_LOAD_NO_RUNS")) {
+  bool his_aligned = (((uintptr_t)his | (uintptr_t)his_st) & 15u) == 0;
+  for (unsigned i = 0; b && i < nb; ++i) his_aligned = his_aligned && (((uintptr_t)b->in[i] | (uintptr_t)b->st_in[i]) & 15u) == 0;
+  if (vec == 1 && r.nd >= 1 && his_aligned && !getenv("OLAP_LOAD_NO_RUNS")) {
     // the innermost dimension is remapped: 16 bytes of HIS per lane, one decode per lane
     const uint64_t lanes = (r.total + 16 / sizeof(T) - 1) / (16 / sizeof(T));
     const unsigned g = grid_for(lanes);
+#define OLAP_LDR(HS, IDX)                                                                                                               \
+  do {                                                                                                                                  \
+    if (b) hipLaunchKernelGGL((load_scatter_run_batch_kernel<T, HS, IDX>), dim3(g, nb), kBlock, 0, stream, *b, r, r.total);             \
+    else hipLaunchKernelGGL((load_scatter_run_kernel<T, HS, IDX>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);      \
+  } while (0)
     if (has_status) {
-      if (idx32) hipLaunchKernelGGL((load_scatter_run_kernel<T, true, uint32_t>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);
-      else hipLaunchKernelGGL((load_scatter_run_kernel<T, true, uint64_t>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);
+      if (idx32) OLAP_LDR(true, uint32_t); else OLAP_LDR(true, uint64_t);
     } else {
-      if (idx32) hipLaunchKernelGGL((load_scatter_run_kernel<T, false, uint32_t>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);
-      else hipLaunchKernelGGL((load_scatter_run_kernel<T, false, uint64_t>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);
+      if (idx32) OLAP_LDR(false, uint32_t); else OLAP_LDR(false, uint64_t);
     }
+#undef OLAP_LDR
     return hipGetLastError();
   }
   const unsigned grid = grid_for(r.total);
-#define OLAP_LD(HS, V)                                                                                                              \
-  do {                                                                                                                              \
-    if (idx32) hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r); \
-    else hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r);       \
+#define OLAP_LD(HS, V)                                                                                                                \
+  do {                                                                                                                                \
+    if (b) {                                                                                                                          \
+      if (idx32) hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);       \
+      else hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);             \
+    } else {                                                                                                                          \
+      if (idx32) hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r); \
+      else hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r);     \
+    }                                                                                                                                 \
   } while (0)
   if (has_status) {
     if (vec == 4) OLAP_LD(true, 4); else if (vec == 2) OLAP_LD(true, 2); else OLAP_LD(true, 1);
@@ -4646,15 +4766,43 @@ hipError_t Launch<T>::load_scatter(bool has_status, int vec, const T *his, const
 }
 
 template <typename T>
-hipError_t Launch<T>::load_permute(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const LoadPermute &a,
-                                   hipStream_t stream) {
+hipError_t Launch<T>::load_scatter(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st,
+                                   const Remap &r, hipStream_t stream) {
+  return load_scatter_launch<T>(has_status, vec, his, his_st, mine, mine_st, nullptr, 1, r, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::load_scatter_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
+  return load_scatter_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, r, stream);
+}
+
+template <typename T>
+static hipError_t load_permute_launch(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const Batch<T> *b,
+                                      unsigned nb, const LoadPermute &a, hipStream_t stream) {
   if (a.n_rows == 0 || a.len == 0) return hipSuccess;
   const uint64_t tiles = (a.n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
   if (tiles >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-  const size_t lds = kTileBytes + (mine_st ? kTileBytes / sizeof(T) * 4 : 0) + (size_t)a.len * 4;
-  if (has_status) hipLaunchKernelGGL((load_permute_rows_kernel<T, true>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
-  else hipLaunchKernelGGL((load_permute_rows_kernel<T, false>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
+  const bool my_mask = b ? b->st_out[0] != nullptr : mine_st != nullptr;
+  const size_t lds = kTileBytes + (my_mask ? kTileBytes / sizeof(T) * 4 : 0) + (size_t)a.len * 4;
+  if (b) {
+    if (has_status) hipLaunchKernelGGL((load_permute_rows_batch_kernel<T, true>), dim3((unsigned)tiles, nb), kBlock, lds, stream, *b, a);
+    else hipLaunchKernelGGL((load_permute_rows_batch_kernel<T, false>), dim3((unsigned)tiles, nb), kBlock, lds, stream, *b, a);
+  } else {
+    if (has_status) hipLaunchKernelGGL((load_permute_rows_kernel<T, true>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
+    else hipLaunchKernelGGL((load_permute_rows_kernel<T, false>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
+  }
   return hipGetLastError();
+}
+
+template <typename T>
+hipError_t Launch<T>::load_permute(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const LoadPermute &a,
+                                   hipStream_t stream) {
+  return load_permute_launch<T>(has_status, his, his_st, mine, mine_st, nullptr, 1, a, stream);
+}
+
+template <typename T>
+hipError_t Launch<T>::load_permute_batch(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream) {
+  return load_permute_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream);
 }
 
 template <typename T>

@@ -231,6 +231,17 @@ class Plan:
                                len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr))
         return cls(h)
 
+    @classmethod
+    def load_typed(cls, my_dtype, his_dtype, my_default, his_default, my_len, his_len, his_to_mine):
+        """load between stores whose cell types may differ (olap_load_plan_typed): `in` of run() holds his_dtype cells"""
+        L = capi.lib()
+        ml, hl = _u32(my_len), _u32(his_len)
+        keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
+        h = C.c_void_p()
+        check(L.olap_load_plan_typed(C.byref(h), DTYPES[my_dtype], DTYPES[his_dtype], _default_kind(my_default), _default_kind(his_default),
+                                     len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr))
+        return cls(h)
+
     @property
     def in_cells(self):
         return int(capi.lib().olap_plan_in_cells(self._h))
@@ -607,3 +618,31 @@ class HipStore:
         keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
         check(self._lib.olap_store_load(self._h, other._h, len(ml), ml.ctypes.data_as(capi._pu32),
                                         hl.ctypes.data_as(capi._pu32), arr))
+
+    @staticmethod
+    def load_many(targets, sources, my_len, his_len, his_to_mine):
+        """targets[i].load(sources[i]) for every pair in one call (olap_store_load_multi); cell types may differ within a
+        pair.  Returns the kernel launches made."""
+        if len(targets) != len(sources):
+            raise ValueError("load_many: %d targets, %d sources" % (len(targets), len(sources)))
+        ml, hl = _u32(my_len), _u32(his_len)
+        keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
+        n = len(targets)
+        ts = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in targets])
+        ss = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in sources])
+        launches = C.c_int(-1)
+        check(capi.lib().olap_store_load_multi(n, ts, ss, len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr,
+                                               C.byref(launches)))
+        return launches.value
+
+    @staticmethod
+    def reorder_many(stores, old_len, perm):
+        """reorder of several measures of a cube in one call (olap_store_reorder_multi): (new stores in order, kernel
+        launches made)"""
+        ol, p = _u32(old_len), _i32(perm)
+        n = len(stores)
+        hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in stores])
+        outs, launches = (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        check(capi.lib().olap_store_reorder_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), p.ctypes.data_as(capi._pi32),
+                                                  C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)

@@ -860,8 +860,10 @@ class Cube {
   reorderDimensions(dimensionIds) {
     if (this.dimensions.every((d, i) => dimensionIds[i] === d.id)) return this;
     const newDimensions = dimensionIds.map((id) => this.dimensions.find((d) => d.id === id));
-    this._materializeStores();
-    return this._derive(newDimensions, (store) => store.reorder(this.dimensions, newDimensions));
+    // (reorderMany dices pending selections together first, as _materializeStores does for the per-measure calls)
+    const reordered = this._together(this.storedMeasureIds, 'reorderMany', (Store, stores) => Store.reorderMany(stores, this.dimensions, newDimensions));
+    if (Object.keys(reordered).length === 0) this._materializeStores();
+    return this._derive(newDimensions, (store, id) => reordered[id] || store.reorder(this.dimensions, newDimensions));
   }
 
   swapDimensions(dim1, dim2) {
@@ -900,10 +902,14 @@ class Cube {
     } catch (_e) {
       return; // no overlap between the cubes: nothing to load
     }
-    for (const id of this.storedMeasureIds) {
-      const source = compatible.storedMeasures[id];
-      if (source) this.storedMeasures[id].load(source, this.dimensions, compatible.dimensions);
+    // the measures both cubes have go to their store class together where it has loadMany (one device call)
+    const ids = this.storedMeasureIds.filter((id) => compatible.storedMeasures[id]);
+    const Store = ids.length >= 1 ? this.storedMeasures[ids[0]].constructor : null;
+    if (Store && typeof Store.loadMany === 'function') {
+      Store.loadMany(ids.map((id) => this.storedMeasures[id]), ids.map((id) => compatible.storedMeasures[id]), this.dimensions, compatible.dimensions);
+      return;
     }
+    for (const id of ids) this.storedMeasures[id].load(compatible.storedMeasures[id], this.dimensions, compatible.dimensions);
   }
 
   compose(otherCube, union = false, fillWith = null) {

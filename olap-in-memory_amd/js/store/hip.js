@@ -177,6 +177,14 @@ function onShards(native, method, args) {
   }
 }
 
+/** his item index -> my item index (-1: an item I do not have), per dimension (in-memory.js:140-150) */
+function loadTables(myDimensions, hisDimensions) {
+  return hisDimensions.map((dim, i) => {
+    const position = myDimensions[i].getItemsToIdx();
+    return Int32Array.from(dim.getItems(), (item) => (position[item] === undefined ? -1 : position[item]));
+  });
+}
+
 class HipStore {
   /**
    * `native` is the addon Store, or — for the result of dice() — a pending selection
@@ -765,22 +773,103 @@ class HipStore {
     return this._wrap(onShards(this._native, 'reorder', [lengthsOf(oldDimensions), perm]));
   }
 
+  /**
+   * reorder of the stored measures of one cube — what Cube.reorderDimensions asks of every stored measure in turn.
+   * Measures held whole on one device and untracked go to the device TOGETHER (addon reorderMulti ->
+   * olap_store_reorder_multi: one launch for up to 8 measures of one cell type and default, except where the reorder
+   * runs as the two-axis transpose); tracked and sharded measures take reorder one by one.  Pending selections are diced
+   * together first (materializeMany, whose launches HipStore.lastBatchLaunches keeps reporting; the reorder's own go to
+   * HipStore.lastReorderLaunches).  Returns the new stores in the order given.
+   */
+  static reorderMany(stores, oldDimensions, newDimensions) {
+    const out = new Array(stores.length);
+    HipStore.materializeMany(stores);
+    HipStore.lastReorderLaunches = null;
+    const together = [];
+    stores.forEach((store, i) => {
+      const native = store._pending ? null : store._nativeStore;
+      if (native && !native.isSharded && !native.orderTracked) together.push(i);
+    });
+    const addon = backend.load();
+    // (an addon built before reorderMulti existed keeps the single-store calls)
+    if (together.length >= 2 && typeof addon.reorderMulti === 'function') {
+      const perm = Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
+      const launchesOut = new Int32Array(1);
+      const natives = addon.reorderMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(oldDimensions), perm, launchesOut);
+      together.forEach((i, j) => {
+        out[i] = stores[i]._wrap(natives[j]);
+      });
+      HipStore.lastReorderLaunches = launchesOut[0];
+    }
+    stores.forEach((store, i) => {
+      if (!out[i]) out[i] = store.reorder(oldDimensions, newDimensions);
+    });
+    return out;
+  }
+
   /** in-memory.js:139-176 — mutates this store */
   load(otherStore, myDimensions, hisDimensions) {
-    const hisToMine = hisDimensions.map((dim, i) => {
-      const position = myDimensions[i].getItemsToIdx();
-      return Int32Array.from(dim.getItems(), (item) => (position[item] === undefined ? -1 : position[item]));
-    });
-    if (otherStore._cells !== this._cells) {
-      // the kernels copy cells of one element type; re-type the source through float64 first
-      const retyped = new HipStore(otherStore._size, this._type, otherStore._defaultValue);
-      retyped.data = otherStore.data;
-      otherStore = retyped;
-    }
+    this._loadWith(otherStore, lengthsOf(myDimensions), lengthsOf(hisDimensions), loadTables(myDimensions, hisDimensions));
+  }
+
+  /** load by ready-made tables (loadTables).  HipStore.lastLoadPath says where the cells travelled. */
+  _loadWith(otherStore, myLen, hisLen, hisToMine) {
     // hydration scatters cells across the whole index space: a sharded measure is gathered for it and
     // stays on one device afterwards
     if (this._native.isSharded) this._nativeStore = this._native.gather();
-    this._writable.load(otherStore._whole, lengthsOf(myDimensions), lengthsOf(hisDimensions), hisToMine);
+    const target = this._writable;
+    HipStore.lastLoadPath = 'device';
+    if (otherStore._cells !== this._cells) {
+      if (!target.orderTracked) {
+        // cells of another element type are converted as they are loaded (addon loadMulti -> olap_store_load_multi)
+        const launchesOut = new Int32Array(1);
+        backend.load().loadMulti([target], [otherStore._whole], myLen, hisLen, hisToMine, launchesOut);
+        HipStore.lastBatchLaunches = launchesOut[0];
+        return;
+      }
+      // A tracked target of another cell type keeps the host path: its key order needs the single-store call, which
+      // copies cells of one element type, so the source is re-typed through float64 first.
+      const retyped = new HipStore(otherStore._size, this._type, otherStore._defaultValue);
+      retyped.data = otherStore.data;
+      otherStore = retyped;
+      HipStore.lastLoadPath = 'host';
+    }
+    target.load(otherStore._whole, myLen, hisLen, hisToMine);
+  }
+
+  /**
+   * targets[i].load(sources[i]) for the measures two cubes share — what Cube.hydrateFromCube asks of every stored measure
+   * in turn.  The tables are computed once; pending selections among the sources are diced together (materializeMany),
+   * sharded sources are gathered as load does; targets held whole on one device and untracked go to the device in ONE
+   * call (addon loadMulti -> olap_store_load_multi: one launch for up to 8 pairs that share both cell types and both
+   * defaults, cells of another type converted on the way); sharded and tracked targets take load one by one.
+   */
+  static loadMany(targets, sources, myDimensions, hisDimensions) {
+    const hisToMine = loadTables(myDimensions, hisDimensions);
+    const myLen = lengthsOf(myDimensions);
+    const hisLen = lengthsOf(hisDimensions);
+    HipStore.materializeMany(sources);
+    let launches = HipStore.lastBatchLaunches;
+    let path = 'device';
+    // a store on both sides, or a target twice: the order of the loads matters, so they stay one by one
+    const distinct = new Set(targets.concat(sources)).size === targets.length + sources.length;
+    const together = [];
+    targets.forEach((target, i) => {
+      const native = target._native;
+      if (distinct && !native.isSharded && !native.orderTracked) together.push(i);
+    });
+    if (together.length >= 1) {
+      const launchesOut = new Int32Array(1);
+      backend.load().loadMulti(together.map((i) => targets[i]._writable), together.map((i) => sources[i]._whole), myLen, hisLen, hisToMine, launchesOut);
+      launches += launchesOut[0];
+    }
+    targets.forEach((target, i) => {
+      if (together.includes(i)) return;
+      target._loadWith(sources[i], myLen, hisLen, hisToMine);
+      if (HipStore.lastLoadPath === 'host') path = 'host';
+    });
+    HipStore.lastBatchLaunches = launches;
+    HipStore.lastLoadPath = path;
   }
 
   /**
@@ -810,8 +899,11 @@ class HipStore {
 
 HipStore.lastSelectPath = null;
 // kernel launches the device reported for the last many-call (diceMany: 0 where every selection stays pending; materializeMany,
-// drillDownMany and the pending selections of drillUpMany: what diceMulti / drillDownMulti / diceDrillUpMulti launched)
+// drillDownMany and the pending selections of drillUpMany: what diceMulti / drillDownMulti / diceDrillUpMulti launched;
+// loadMany and a load between cell types: what loadMulti launched on top)
 HipStore.lastBatchLaunches = null;
+// kernel launches reorderMulti reported for the last reorderMany (null: every measure took reorder one by one)
+HipStore.lastReorderLaunches = null;
 // 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the
 // launches it reported; never reset here
 HipStore.lastTotalsPath = null;
@@ -821,6 +913,10 @@ HipStore.lastTotalsLaunches = null;
 HipStore.lastTotalsCalls = null;
 // 'device' after a copyMeasureData that ran as one device scatter (copySelect / copySelectFormula); never reset here
 HipStore.lastCopyPath = null;
+
+// 'device' after a load / loadMany whose cells stayed on the device, 'host' when a source of another cell type went
+// through the host as float64 (a tracked target); never reset here
+HipStore.lastLoadPath = null;
 
 // what the last Cube.copyToStoredMeasure / convertToStoredMeasure did: 'device' (setFormula: one device call, no host copy)
 // or 'host' (getData, then setData); Cube resets it to null when such a call starts

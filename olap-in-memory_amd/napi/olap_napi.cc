@@ -1104,6 +1104,46 @@ static napi_value DiceMulti(napi_env env, napi_callback_info info) {
   return wrap_new_stores(env, outs);
 }
 
+// reorderMulti(stores: Store[], oldLen, perm: Int32Array, launchesOut?: Int32Array) -> Store[]
+static napi_value ReorderMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "reorderMulti(stores: Store[], oldLen: Uint32Array, perm: Int32Array, launchesOut?: Int32Array)";
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::vector<uint32_t> len, perm;
+  MultiArgs m;
+  bool bad = true;
+  if (argc < 3 || !get_u32_vec(env, argv[1], len) || !get_u32_vec(env, argv[2], perm) || len.size() != perm.size()) return bad_args(env, usage);
+  if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int launches = 0;
+  int rc = olap_store_reorder_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)len.size(), len.data(), (const int32_t *)perm.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 3) set_path(env, argv[3], launches);
+  return wrap_new_stores(env, outs);
+}
+
+// loadMulti(targets: Store[], sources: Store[], myLen, hisLen, hisToMine: Int32Array[], launchesOut?: Int32Array): targets[i].load(sources[i])
+static napi_value LoadMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "loadMulti(targets: Store[], sources: Store[], myLen: Uint32Array, hisLen: Uint32Array, hisToMine: Int32Array[], launchesOut?: Int32Array)";
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs t, o;
+  bool bad = true;
+  if (argc < 5 || !a.decode(env, argv[2], argv[3], argv[4])) return bad_args(env, usage);
+  if (!t.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  if (!o.decode(env, argv[1], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  if (t.stores.size() != o.stores.size()) return bad_args(env, usage);
+  int launches = 0;
+  int rc = olap_store_load_multi((int)t.stores.size(), (olap_store *const *)t.stores.data(), o.stores.data(), (int)a.a_len.size(), a.a_len.data(),
+                                 a.b_len.data(), (const int32_t *const *)a.ptrs.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 5) set_path(env, argv[5], launches);
+  return nullptr;
+}
+
 // diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?) -> Store[]
 static napi_value DiceDrillUpMulti(napi_env env, napi_callback_info info) {
   const char *usage = "diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?: Int32Array)";
@@ -1725,6 +1765,8 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"totalsReport", nullptr, TotalsReport, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillUpMulti", nullptr, DrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"diceMulti", nullptr, DiceMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"reorderMulti", nullptr, ReorderMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"loadMulti", nullptr, LoadMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"diceDrillUpMulti", nullptr, DiceDrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
