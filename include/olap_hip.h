@@ -389,6 +389,27 @@ int olap_totals_report(int n_inputs, const olap_store *const *inputs, int ndim, 
                        const double *consts, const int *out_n_inputs, const int *formula_inputs, double *host_values,
                        int *launches, uint64_t *bytes_read);
 
+/* Cube.scan / Cube.iterateOverDimension (src/cube.js:811-823): what every combination of the scanned dimensions' items
+ * receives, for n stores of one cube (size = prod(lens) cells each; cell types and defaults may differ), in one device
+ * pass.  scanned[d] != 0 marks a scanned dimension, the others are kept.  C = the product of the scanned lengths, B =
+ * the product of the kept ones; c = the row-major index over the scanned dimensions in cube order (the order of the
+ * combinations), b = the row-major index over the kept ones.  host_values[k * size + c * B + b] = what
+ * olap_store_get_data_f64(stores[k]) puts at that cell's flat index (the value as float64, the store's default in an
+ * unset cell): per store, get_data_f64 transposed to [scanned..., kept...].  One device slab, one copy to the host, the
+ * call's only wait.  Two kernels, chosen on the host: the innermost cube dimension kept — rows stay contiguous on both
+ * sides, a converting row gather; the innermost scanned — a padded LDS tile transpose between it and the last kept
+ * dimension, converted on the way out.  Stores that share cell type, default and whether they keep a mask leave in
+ * launches of up to 8; *launches (may be NULL) = the sum of ceil(group / 8) over the groups.
+ * Refused on the host before any device work, with the same codes and messages on a machine without a device, in this
+ * order: a NULL list or n < 0; a NULL entry ("store i of the batch is NULL"); ndim, the length vector and the flags; no
+ * scanned dimension, or B == 0 or C == 0; a store whose size is not prod(lens) (OLAP_ERR_LENGTH_MISMATCH); stores on
+ * two devices; a tracked store ("ordered: ..."); n * size * 8 above OLAP_BLOCKS_MAX_BYTES ("blocks: ...": the caller
+ * goes combination by combination; the environment variable OLAP_BLOCKS_MAX_BYTES lowers the cap, for tests).  Sharded
+ * stores have no such call.  DESIGN.md §3 K11. */
+#define OLAP_BLOCKS_MAX_BYTES (1ull << 30)
+int olap_store_blocks_report(int n, const olap_store *const *stores, int ndim, const uint32_t *lens,
+                             const uint8_t *scanned /* ndim flags */, double *host_values, int *launches);
+
 /* Filtered totals and copies over a cartesian selection given as nlev LEVELS in nesting order, the first outermost
  * (getCombinations, src/cube.js:19-32: the filter's keys in their own order, then the unfiltered dimensions in cube
  * order).  axis[l] is a cube dimension (each exactly once) or -1 for a filter key that is not a dimension (it only

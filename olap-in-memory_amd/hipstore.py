@@ -646,3 +646,23 @@ class HipStore:
         check(capi.lib().olap_store_reorder_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), p.ctypes.data_as(capi._pi32),
                                                   C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
+
+
+def blocks_report(stores, lens, scanned):
+    """Cube.scan / iterateOverDimension for several measures of one cube in one device pass (olap_store_blocks_report):
+    `scanned` flags the scanned dimensions (one per dimension).  Returns ((n, C, B) float64 array, kernel launches made):
+    [k, c] holds the cells combination c of the scanned dimensions' items receives of store k, as get_data_f64 reads them
+    (the default in unset cells), row-major over the kept dimensions."""
+    lv = _u32(lens)
+    flags = np.ascontiguousarray(np.asarray(scanned, dtype=np.uint8).ravel())
+    if len(flags) != len(lv):
+        raise ValueError("blocks_report: one flag per dimension")
+    n = len(stores)
+    combos = int(np.prod([int(l) for l, f in zip(lv, flags) if f], dtype=np.uint64)) if len(lv) else 1
+    kept = int(np.prod([int(l) for l, f in zip(lv, flags) if not f], dtype=np.uint64)) if len(lv) else 1
+    hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in stores])
+    out = np.zeros((n, combos, kept), np.float64)
+    launches = C.c_int(-1)
+    check(capi.lib().olap_store_blocks_report(n, hs, len(lv), lv.ctypes.data_as(capi._pu32), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              out.ctypes.data_as(capi._pdbl), C.byref(launches)))
+    return out, launches.value

@@ -808,10 +808,51 @@ class Cube {
     return this._derive(newDimensions, (store, id) => diced[id] || store.dice(this.dimensions, newDimensions), rules, wanted);
   }
 
+  /**
+   * src/cube.js:811-823.  What every combination receives is a permutation of cells that are already on the device, so
+   * the stored measures are regrouped by ONE device call (HipStore.blocksMany, DESIGN.md §3 K11) and every callback gets
+   * a cube whose measures are host-resident stores over its block: the same dimension objects, rules and computed
+   * measures as diceByDimensionItems(combination) builds.  _scanPerCombination is the reference's loop; it serves a single
+   * combination, cubes without stored measures, measures the device call does not take (tracked, sharded, another store
+   * class, above its byte cap) and — from the first callback that writes to this cube — the combinations that remain.
+   */
   scan(dimensionIds, cb) {
+    HipStore.lastBlocksCalls = 0;
+    const pass = this._blocksPass(this.getDimensionItemsMap(dimensionIds));
+    if (pass === null) {
+      this._scanPerCombination(dimensionIds, cb);
+      return;
+    }
+    const diced = this._lazyDice();
+    pass.each((combination, blocks) => {
+      const newDimensions = this.dimensions.slice();
+      for (const [dimensionId, item] of Object.entries(combination)) {
+        const index = this.getDimensionIndex(dimensionId);
+        newDimensions[index] = diced(index, item);
+        // (a dice that does not come down to the one item: the general path decides what the cube looks like)
+        if (newDimensions[index].numItems !== 1) return false;
+      }
+      const cube = new Cube(newDimensions);
+      Object.assign(cube.computedMeasures, this.computedMeasures);
+      for (const id of pass.ids) {
+        cube.storedMeasuresRules[id] = deepCopy(this.storedMeasuresRules[id]);
+        cube.storedMeasures[id] = blocks[id];
+      }
+      cb(cube, combination);
+      return true;
+    }, (combination) => cb(this.diceByDimensionItems(combination), combination));
+  }
+
+  _scanPerCombination(dimensionIds, cb) {
     for (const combination of cartesian(this.getDimensionItemsMap(dimensionIds))) cb(this.diceByDimensionItems(combination), combination);
   }
 
+  /**
+   * src/cube.js:815-823.  Every slice(id, 'all', 'all') of aggregateByDimensions rolls up groups of exactly one member,
+   * and the seven rules leave a lone value and its set / unset state as they are (in-memory.js:298-331): each callback's
+   * cube holds row `c` of the one device pass scan() describes.  Another rule name takes the reference's loop, which
+   * throws its message.
+   */
   iterateOverDimension(dimension, cb) {
     const others = this.dimensionIds.filter((id) => id !== dimension);
     if (others.length === this.dimensionIds.length) throw new Error(`Cube has no ${dimension} dimension. Dimensions: ${this.dimensionIds}`);
@@ -819,7 +860,104 @@ class Cube {
       cb(this, {});
       return;
     }
-    this.scan(others, (diced, items) => cb(diced.aggregateByDimensions([dimension]), items));
+    HipStore.lastBlocksCalls = 0;
+    const known = ['sum', 'average', 'highest', 'lowest', 'first', 'last', 'product'];
+    const rulesKnown = this.storedMeasureIds.every((id) => others.every((other) => {
+      const rule = (this.storedMeasuresRules[id] || {})[other];
+      return rule === undefined || known.includes(rule);
+    }));
+    const pass = rulesKnown ? this._blocksPass(this.getDimensionItemsMap(others)) : null;
+    if (pass === null) {
+      this._iterateOverDimensionPerCombination(dimension, cb);
+      return;
+    }
+    const kept = this.getDimension(dimension);
+    const diced = this._lazyDice();
+    const perCombination = (combination) => cb(this.diceByDimensionItems(combination).aggregateByDimensions([dimension]), combination);
+    pass.each((combination, blocks) => {
+      // the dimension objects are not handed out, but their dice() may throw: at the same combination as in the loop
+      for (const [dimensionId, item] of Object.entries(combination)) if (diced(this.getDimensionIndex(dimensionId), item).numItems !== 1) return false;
+      const cube = new Cube([kept]);
+      Object.assign(cube.computedMeasures, this.computedMeasures);
+      for (const id of pass.ids) {
+        const rules = deepCopy(this.storedMeasuresRules[id]);
+        if (rules) for (const other of others) delete rules[other];
+        cube.storedMeasuresRules[id] = rules;
+        cube.storedMeasures[id] = blocks[id];
+      }
+      cb(cube, combination);
+      return true;
+    }, perCombination);
+  }
+
+  _iterateOverDimensionPerCombination(dimension, cb) {
+    const others = this.dimensionIds.filter((id) => id !== dimension);
+    if (others.length === this.dimensionIds.length) throw new Error(`Cube has no ${dimension} dimension. Dimensions: ${this.dimensionIds}`);
+    if (others.length === 0) {
+      cb(this, {});
+      return;
+    }
+    this._scanPerCombination(others, (diced, items) => cb(diced.aggregateByDimensions([dimension]), items));
+  }
+
+  /** dimension.dice(attribute, [item]) as diceByDimensionItems calls it for one item, made on first use and kept per (dimension, item). */
+  _lazyDice() {
+    const made = this.dimensions.map(() => new Map());
+    return (index, item) => {
+      let dimension = made[index].get(item);
+      if (dimension === undefined) {
+        // a dimension literally called 'time' is diced at the periodicity of the given slot (src/cube.js:600-603)
+        const attribute = this.dimensions[index].id === 'time' ? TimeSlot.fromValue(item).periodicity : this.dimensions[index].rootAttribute;
+        dimension = this.dimensions[index].dice(attribute, [item], false);
+        made[index].set(item, dimension);
+      }
+      return dimension;
+    };
+  }
+
+  /**
+   * The one device pass behind scan / iterateOverDimension over the dimensions of `itemsMap` (in cube order, as
+   * getDimensionItemsMap lists them), or null where it does not apply: fewer than 2 combinations, no stored measure, more
+   * cells per combination than HipStore.blocksMaxBlockCells, a measure that is no HipStore, or HipStore.blocksMany declining.  `each(onBlock, onCombination)` walks the combinations
+   * in the order of cartesian(): onBlock(combination, { id: host-resident store over the combination's cells }) while
+   * the source cube is as it was when the pass ran (the same store objects, none handed out for writing since; onBlock
+   * may return false to decline), onCombination(combination) from then on.
+   */
+  _blocksPass(itemsMap) {
+    const combinations = cartesian(itemsMap);
+    const ids = this.storedMeasureIds;
+    if (combinations.length < 2 || ids.length === 0) return null;
+    // few combinations of very large blocks gain nothing from the one pass (HipStore.blocksMaxBlockCells says on which measurement)
+    if (this.storeSize / combinations.length > HipStore.blocksMaxBlockCells) return null;
+    const stores = ids.map((id) => this.storedMeasures[id]);
+    if (!stores.every((store) => store instanceof HipStore)) return null;
+    const flags = this.dimensions.map((d) => itemsMap[d.id] !== undefined);
+    const values = HipStore.blocksMany(stores, this.dimensions, flags);
+    if (values === null) return null;
+    const writes = stores.map((store) => store._writes);
+    const rows = this.storeSize / combinations.length;
+    const unchanged = () => {
+      const now = this.storedMeasureIds;
+      return now.length === ids.length && ids.every((id, k) => now[k] === id && this.storedMeasures[id] === stores[k] && stores[k]._writes === writes[k]);
+    };
+    return {
+      ids,
+      each: (onBlock, onCombination) => {
+        let onePass = true;
+        combinations.forEach((combination, c) => {
+          onePass = onePass && unchanged();
+          if (onePass) {
+            const blocks = {};
+            ids.forEach((id, k) => {
+              const source = stores[k];
+              blocks[id] = new HipStore(rows, source._type, source._defaultValue, { host: values[k].subarray(c * rows, (c + 1) * rows), cells: source._cells });
+            });
+            if (onBlock(combination, blocks) !== false) return;
+          }
+          onCombination(combination);
+        });
+      },
+    };
   }
 
   // ------------------------------------------------------------------ dimension list changes

@@ -71,28 +71,51 @@ class CellMapView {
   }
 
   get size() {
+    const host = this._store._hostCells;
+    if (host) {
+      let n = 0;
+      for (let i = 0; i < host.length; ++i) if (this._store._hostIsSet(i)) ++n;
+      return n;
+    }
     return this._store._whole.countSet();
   }
 
   has(index) {
+    if (this._store._hostHolds(index)) return this._store._hostIsSet(index);
     return this._store._native.getValue(index) !== undefined;
   }
 
   get(index) {
+    if (this._store._hostHolds(index)) return this._store._hostIsSet(index) ? this._store._hostCells[index] : undefined;
     return this._store._native.getValue(index);
   }
 
   *keys() {
+    const host = this._store._hostCells;
+    if (host) {
+      // (an untracked store lists its set cells in ascending index order)
+      for (let i = 0; i < host.length; ++i) if (this._store._hostIsSet(i)) yield i;
+      return;
+    }
     for (const k of this._store._whole.getKeys()) yield k;
   }
 
   *values() {
+    if (this._store._hostCells) {
+      for (const [, v] of this.entries()) yield v;
+      return;
+    }
     const whole = this._store._whole;
     const data = whole.getDataF64();
     for (const k of whole.getKeys()) yield data[k];
   }
 
   *entries() {
+    const host = this._store._hostCells;
+    if (host) {
+      for (let i = 0; i < host.length; ++i) if (this._store._hostIsSet(i)) yield [i, host[i]];
+      return;
+    }
     const whole = this._store._whole;
     const data = whole.getDataF64();
     for (const k of whole.getKeys()) yield [k, data[k]];
@@ -190,7 +213,10 @@ class HipStore {
    * `native` is the addon Store, or — for the result of dice() — a pending selection
    * `{ source, oldLen, sel }` that is only materialised when cells are actually needed: a drillUp
    * that follows (slice, removeDimension, drillUp after dice) runs fused and never writes the diced
-   * intermediate cube (K5, DESIGN.md §3).
+   * intermediate cube (K5, DESIGN.md §3).  Or — for the cubes Cube.scan / iterateOverDimension hand out — host-resident
+   * cells `{ host: Float64Array, cells }`: the `size` cells with the default in unset ones, as blocksMany brought them back,
+   * of a source whose device cells are of type `cells`.  Reads answer from the array; the first operation that needs the
+   * device creates the store (the _native getter) and the measure is an ordinary one from then on (K11, DESIGN.md §3).
    */
   constructor(size, type = 'float32', defaultValue = Number.NaN, native = undefined, lengths = undefined) {
     // same checks, order and messages as in-memory.js:56-60
@@ -201,7 +227,14 @@ class HipStore {
     this._defaultValue = defaultValue;
     this._pending = null;
     this._lent = false; // a pending dice elsewhere still reads this store's device buffer
-    if (native && native.source) {
+    this._host = null;
+    this._writes = 0; // bumped whenever this store is handed out for writing (_writable): Cube.scan watches it
+    if (native && native.host) {
+      if (native.host.length !== size) throw new Error(`value length is invalid: ${size} !== ${native.host.length}`);
+      this._host = native.host;
+      this._nativeStore = null;
+      this._cells = native.cells;
+    } else if (native && native.source) {
       this._pending = native;
       this._nativeStore = null;
       this._cells = TYPE_NAME[native.source.dtype];
@@ -230,14 +263,39 @@ class HipStore {
     return world >= 2 && !!lengths && lengths.length >= 1 && lengths[0] >= world;
   }
 
-  /** The device store (one device, or sharded); a pending dice is executed on first use. */
+  /**
+   * The device store (one device, or sharded); a pending dice is executed on first use, and host-resident cells are
+   * uploaded into a new store of the source's cell type and default — the store the per-combination path would have made.
+   */
   get _native() {
     if (!this._nativeStore) {
+      if (this._host) {
+        const native = new (backend.load().Store)(this._size, TYPE_CODE[this._cells], Number.isNaN(this._defaultValue) ? 1 : 0);
+        native.setData(this._host);
+        this._nativeStore = native;
+        this._host = null;
+        return native;
+      }
       const p = this._pending;
       this._nativeStore = onShards(p.source, 'dice', [p.oldLen, p.midLen, p.sel]);
       this._pending = null;
     }
     return this._nativeStore;
+  }
+
+  /** The host-resident cells while no device store exists yet (null otherwise). */
+  get _hostCells() {
+    return this._nativeStore ? null : this._host;
+  }
+
+  _hostHolds(index) {
+    return this._hostCells !== null && Number.isInteger(index) && index >= 0 && index < this._size;
+  }
+
+  /** What the `data` setter would make of host cell `index`: set iff its value is not the default. */
+  _hostIsSet(index) {
+    const v = this._host[index];
+    return Number.isNaN(this._defaultValue) ? !Number.isNaN(v) : v !== 0;
   }
 
   /**
@@ -270,6 +328,7 @@ class HipStore {
    * copy and leaves the lent one to its readers (copy-on-write, at most once per lending).
    */
   get _writable() {
+    ++this._writes;
     const native = this._native;
     if (this._lent) {
       this._nativeStore = native.clone();
@@ -296,6 +355,7 @@ class HipStore {
 
   /** Dense plain Array, default value in unset cells (in-memory.js:30-37). */
   get data() {
+    if (this._hostCells) return toPlainArray(this._host);
     return toPlainArray(this._native.getDataF64());
   }
 
@@ -318,6 +378,7 @@ class HipStore {
   }
 
   getValue(index) {
+    if (this._hostHolds(index)) return this._host[index];
     const v = this._native.getValue(index);
     return v === undefined ? this._defaultValue : v;
   }
@@ -873,6 +934,42 @@ class HipStore {
   }
 
   /**
+   * What every combination of the scanned dimensions' items receives, for the stored measures of one cube, in ONE device
+   * call (addon blocksReport -> olap_store_blocks_report): `scannedFlags[d]` marks the scanned dimensions.  Returns one
+   * Float64Array per store — views of the one result, laid out [combination][kept cells], the default in unset cells — or
+   * null when the call does not apply: a sharded or tracked measure, an addon without the call, or a result above the
+   * call's byte cap (OLAP_BLOCKS_MAX_BYTES).  The caller then goes combination by combination.  Pending dices are
+   * materialised together first, as reorderMany does.  Sets HipStore.lastBlocksCalls and HipStore.lastBatchLaunches.
+   */
+  static blocksMany(stores, dimensions, scannedFlags) {
+    const addon = backend.load();
+    if (typeof addon.blocksReport !== 'function') return null;
+    for (const store of stores) {
+      const native = store._pending ? store._pending.source : store._nativeStore;
+      if (native && (native.isSharded || native.orderTracked)) return null;
+    }
+    HipStore.materializeMany(stores);
+    let launches = HipStore.lastBatchLaunches;
+    const natives = stores.map((store) => store._native);
+    if (natives.some((native) => native.isSharded || native.orderTracked)) return null;
+    const lens = lengthsOf(dimensions);
+    const size = lens.reduce((n, l) => n * l, 1);
+    if (stores.length * size * 8 > HipStore.blocksMaxBytes) return null;
+    const launchesOut = new Int32Array(1);
+    let values;
+    try {
+      values = addon.blocksReport(natives, lens, Uint8Array.from(scannedFlags, (f) => (f ? 1 : 0)), launchesOut);
+    } catch (e) {
+      if (!/^blocks:/.test(e.message)) throw e;
+      return null; // the cap (lowered by the environment)
+    }
+    launches += launchesOut[0];
+    HipStore.lastBlocksCalls += 1;
+    HipStore.lastBatchLaunches = launches;
+    return stores.map((_, k) => values.subarray(k * size, (k + 1) * size));
+  }
+
+  /**
    * Same blob as the reference (in-memory.js:75-101): the set cells in sparse form.  The compaction
    * (set cells -> ascending index / value lists) runs on the device.
    */
@@ -898,6 +995,15 @@ class HipStore {
 }
 
 HipStore.lastSelectPath = null;
+// the blocksReport calls the last Cube.scan / iterateOverDimension made: 1 when every combination was served from one device
+// pass, 0 when it went combination by combination; Cube resets it when such a call starts
+HipStore.lastBlocksCalls = 0;
+// OLAP_BLOCKS_MAX_BYTES (include/olap_hip.h): the float64 result one blocksReport call may bring back
+HipStore.blocksMaxBytes = 2 ** 30;
+// Cube.scan / iterateOverDimension go combination by combination when one combination receives more cells than this: at 10^6
+// cells per combination the one pass measured 0.9 - 1.2 of the loop's time while holding every block on the host at once, at
+// 10^5 it is 1.2 - 1.5 times faster (profiles/scan_blocks_r36.txt; nothing was measured in between)
+HipStore.blocksMaxBlockCells = 500000;
 // kernel launches the device reported for the last many-call (diceMany: 0 where every selection stays pending; materializeMany,
 // drillDownMany and the pending selections of drillUpMany: what diceMulti / drillDownMulti / diceDrillUpMulti launched;
 // loadMany and a load between cell types: what loadMulti launched on top)

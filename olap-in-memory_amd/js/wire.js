@@ -44,7 +44,10 @@ class Sink {
 
   f32(value) {
     this.reserve(4);
-    this.view.setFloat32(this.length, value, true);
+    // NaN (a measure's default) is written as 0x7FC00000 explicitly: DataView.setFloat32 wrote 0xFFFFFFFF for the same NaN in
+    // one call of a process and 0x7FC00000 in the others (Node 12), so equal stores gave blobs that differed in these four bytes
+    if (value !== value) this.view.setUint32(this.length, 0x7fc00000, true);
+    else this.view.setFloat32(this.length, value, true);
     this.length += 4;
   }
 

@@ -7,6 +7,8 @@
 // Handles are freed by the GC finalizer (the reference API has no explicit free).
 #include <node_api.h>
 
+#include <algorithm>
+
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -1144,6 +1146,46 @@ static napi_value LoadMulti(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// blocksReport(stores: Store[], lens: Uint32Array, scanned: Uint8Array, launchesOut?: Int32Array)
+//   -> Float64Array of stores.length results, one after the other, each [scanned..., kept...] (olap_store_blocks_report)
+static napi_value BlocksReport(napi_env env, napi_callback_info info) {
+  const char *usage = "blocksReport(stores: Store[], lens: Uint32Array, scanned: Uint8Array, launchesOut?: Int32Array)";
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::vector<uint32_t> lens;
+  MultiArgs m;
+  bool bad = true;
+  napi_typedarray_type ft;
+  size_t n_flags = 0;
+  void *flags = nullptr;
+  if (argc < 3 || !get_u32_vec(env, argv[1], lens) || napi_get_typedarray_info(env, argv[2], &ft, &n_flags, &flags, nullptr, nullptr) != napi_ok ||
+      ft != napi_uint8_array || n_flags != lens.size())
+    return bad_args(env, usage);
+  if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  // the byte cap of olap_store_blocks_report, before the result is allocated
+  double cells = 1;
+  for (uint32_t l : lens) cells *= (double)l;
+  double cap = (double)OLAP_BLOCKS_MAX_BYTES;
+  if (const char *e = getenv("OLAP_BLOCKS_MAX_BYTES")) cap = std::min(cap, strtod(e, nullptr));
+  if ((double)m.stores.size() * cells * 8.0 > cap) {
+    napi_throw_range_error(env, nullptr, "blocks: the result is larger than one call may bring back");
+    return nullptr;
+  }
+  void *data;
+  napi_value ta = make_ta(env, napi_float64_array, 8, (size_t)((double)m.stores.size() * cells), &data);
+  if (!ta) return nullptr;
+  static const uint32_t none = 0;
+  static const uint8_t no_flag = 0;
+  static double no_cell = 0;
+  int launches = 0;
+  int rc = olap_store_blocks_report((int)m.stores.size(), m.stores.data(), (int)lens.size(), lens.empty() ? &none : lens.data(),
+                                    flags ? (const uint8_t *)flags : &no_flag, data ? (double *)data : &no_cell, &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 3) set_path(env, argv[3], launches);
+  return ta;
+}
+
 // diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?) -> Store[]
 static napi_value DiceDrillUpMulti(napi_env env, napi_callback_info info) {
   const char *usage = "diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?: Int32Array)";
@@ -1767,6 +1809,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"diceMulti", nullptr, DiceMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reorderMulti", nullptr, ReorderMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"loadMulti", nullptr, LoadMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"blocksReport", nullptr, BlocksReport, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"diceDrillUpMulti", nullptr, DiceDrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
