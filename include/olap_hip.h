@@ -164,6 +164,12 @@ int olap_load_plan(olap_plan **plan, int dtype, int my_default_kind, int his_def
 int olap_load_plan_typed(olap_plan **plan, int my_dtype, int his_dtype, int my_default_kind, int his_default_kind,
                          int ndim, const uint32_t *my_len, const uint32_t *his_len,
                          const int32_t *const *his_to_mine);
+/* The plan olap_store_compose_multi runs for stores of this cell type and default (below): a gather over MY cells with
+ * the item maps inverted on the host.  `in` of olap_plan_run is the other store, `out` a store of my_len cells of which
+ * EVERY cell is written (no fill: cells without a cell of his end unset).  olap_plan_kernel_name tells the form:
+ * "compose_gather (16-byte lanes)" or "compose_gather (16-byte runs of this store)". */
+int olap_compose_plan(olap_plan **plan, int dtype, int default_kind, int ndim, const uint32_t *my_len,
+                      const uint32_t *his_len, const int32_t *const *his_to_mine);
 
 uint64_t olap_plan_in_cells(const olap_plan *plan);
 uint64_t olap_plan_out_cells(const olap_plan *plan);
@@ -517,6 +523,26 @@ int olap_store_load(olap_store *store, const olap_store *other, int ndim, const 
 int olap_store_load_multi(int n, olap_store *const *targets, const olap_store *const *sources, int ndim,
                           const uint32_t *my_len, const uint32_t *his_len,
                           const int32_t *const *his_to_mine, int *launches);
+/* The stored measures of ONE source cube brought onto the dimensions of a composed cube (Cube.compose): out[i] is a new
+ * store of prod(my_len) cells with sources[i]'s cell type and default that ends, bit for bit in values and mask, as
+ *   olap_store_create; olap_store_fill(fill[i]) where has_fill && has_fill[i]; olap_store_load(sources[i], same lengths and maps)
+ * would leave it — in one pass that writes every cell of the new store exactly once: nothing is cleared or filled
+ * first, and a cell takes the cell of his that maps onto it, or the fill, or stays unset.  his_to_mine is load's (-1: an
+ * item I do not have); it is inverted on the host, per dimension, the LAST of his items that name one item of mine
+ * winning, as the last write of a load does.  The fill value is converted, and kept or dropped, as olap_store_fill does
+ * it (NaN under a NaN default and 0 under a 0 default leave the cells unset).  fill / has_fill may be NULL.  n == 0 or a
+ * target of 0 cells launches nothing; ndim == 0 is a single cell.  Sources that share (cell type, default, device)
+ * share one plan (olap_compose_plan), kept by the plan cache, and leave in launches of up to 8: *launches (may be NULL)
+ * is the sum of ceil(group size / 8) over the groups.  A mask is read and written only where it is primary (integer
+ * cells under a NaN default): a Float32 measure moves 4 bytes in and 4 bytes out per cell of the new store.
+ * Checked on the host before any device work, with the same codes and messages on a machine without a device, in this
+ * order: a NULL list or n < 0; a NULL entry ("store i of the batch is NULL"); ndim, the length vectors and the map
+ * entries (as olap_store_load_multi); a source whose size is not the product of his_len (OLAP_ERR_LENGTH_MISMATCH);
+ * sources on two devices; a tracked source ("ordered: ...": the key order of fill + load is not a gather's); a NULL
+ * `out`.  On an error no store is created and out[] is untouched.  The sources are only read. */
+int olap_store_compose_multi(int n, const olap_store *const *sources, const double *fill, const uint8_t *has_fill,
+                             olap_store **out, int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                             const int32_t *const *his_to_mine, int *launches);
 /* olap_store_reorder of n stores — all stored measures of one cube (Cube.reorderDimensions) — with the checks, the
  * grouping and the results of the *_multi calls above.  Reorders that run as a gather or through bricks leave in
  * launches of up to 8; the two-axis transpose runs pair by pair behind the call. */

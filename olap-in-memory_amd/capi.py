@@ -58,6 +58,7 @@ SIGNATURES = {
     "olap_reorder_plan": (_i32, [_pvp, _i32, _i32, _i32, _pu32, _pi32]),
     "olap_load_plan": (_i32, [_pvp, _i32, _i32, _i32, _i32, _pu32, _pu32, _ppi32]),
     "olap_load_plan_typed": (_i32, [_pvp, _i32, _i32, _i32, _i32, _i32, _pu32, _pu32, _ppi32]),
+    "olap_compose_plan": (_i32, [_pvp, _i32, _i32, _i32, _pu32, _pu32, _ppi32]),
     "olap_plan_in_cells": (_u64, [_vp]),
     "olap_plan_out_cells": (_u64, [_vp]),
     "olap_plan_kernel_name": (C.c_char_p, [_vp]),
@@ -115,6 +116,7 @@ SIGNATURES = {
     "olap_store_load": (_i32, [_vp, _vp, _i32, _pu32, _pu32, _ppi32]),
     "olap_store_load_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _pu32, _ppi32, C.POINTER(C.c_int)]),
     "olap_store_reorder_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _pi32, C.POINTER(C.c_int)]),
+    "olap_store_compose_multi": (_i32, [_i32, _pvp, _pdbl, C.POINTER(C.c_uint8), _pvp, _i32, _pu32, _pu32, _ppi32, C.POINTER(C.c_int)]),
     "olap_store_blocks_report": (_i32, [_i32, _pvp, _i32, _pu32, C.POINTER(C.c_uint8), _pdbl, C.POINTER(C.c_int)]),
     "olap_store_select_total": (_i32, [_vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
     "olap_store_copy_select": (_i32, [_vp, _vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),

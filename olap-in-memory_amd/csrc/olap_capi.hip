@@ -228,7 +228,7 @@ extern "C" int olap_device_synchronize(void) {
 }
 
 // ------------------------------------------------------------------ plans
-enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE };
+enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE };
 
 struct olap_plan {
   PlanKind kind;
@@ -1480,6 +1480,61 @@ static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_def
   return OLAP_OK;
 }
 
+// ---- compose --------------------------------------------------------------------------------
+// create [+ fill] + load as one gather over MY cells (olap_kernels_compose.hip): the item maps are inverted here, per
+// dimension, the LAST of his items that name one of mine winning — the cell a load writes last, because the
+// lexicographically last of the cells of his that land on one cell of mine is the per-dimension last one.
+extern "C" int olap_compose_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *my_len, const uint32_t *his_len,
+                                 const int32_t *const *his_to_mine) {
+  if (!out) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan out-pointer is NULL");
+  *out = nullptr;
+  int rc;
+  if ((rc = check_dtype(dtype)) || (rc = check_default(default_kind))) return rc;
+  if ((rc = check_load_maps(ndim, my_len, his_len, his_to_mine))) return rc;
+  if ((rc = require_device())) return rc;
+  olap_plan *p = new (std::nothrow) olap_plan();
+  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
+  p->kind = PLAN_COMPOSE;
+  p->dtype = p->his_dtype = dtype;
+  p->def_nan = p->his_def_nan = default_kind == OLAP_DEFAULT_NAN;
+  p->in_cells = product(his_len, ndim);
+  p->out_cells = product(my_len, ndim);
+  std::vector<RemapDim> dims(ndim);
+  uint64_t stride = 1;  // of his
+  const bool nothing = p->in_cells == 0;  // his store has no cell: every table says so
+  for (int d = ndim - 1; d >= 0; --d) {
+    RemapDim &rd = dims[d];
+    rd.len = my_len[d];
+    rd.stride = stride;
+    bool ident = his_len[d] == my_len[d] && !nothing;
+    for (uint32_t j = 0; ident && j < his_len[d]; ++j) ident = his_to_mine[d][j] == (int32_t)j;
+    rd.arithmetic = ident;
+    if (!ident) {
+      rd.table.assign(my_len[d], -1);
+      for (uint32_t j = 0; j < his_len[d] && !nothing; ++j)
+        if (his_to_mine[d][j] >= 0) rd.table[his_to_mine[d][j]] = (int64_t)j * (int64_t)stride;
+    }
+    stride *= his_len[d];
+  }
+  if (dims.empty()) {  // one cell: the kernels decode at least one dimension
+    RemapDim one{};
+    one.len = 1, one.arithmetic = true, one.stride = 1;
+    dims.push_back(one);
+  }
+  if ((rc = finish_remap(p, dims, p->out_cells, true))) {
+    olap_plan_destroy(p);
+    return rc;
+  }
+  // lanes only of 16 bytes: an innermost run that is no whole number of them takes the per-cell form
+  if (p->vec != (int)(16 / olap_dtype_size(dtype))) {
+    p->remap.total *= (uint64_t)p->vec;
+    p->vec = 1;
+  }
+  p->kernel_name = p->vec > 1 ? "compose_gather (16-byte lanes)" : "compose_gather (16-byte runs of this store)";
+  *out = p;
+  return OLAP_OK;
+}
+
 // ---- drillDown ------------------------------------------------------------------------------
 extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind, int method, int ndim,
                                    const uint32_t *old_len, const uint32_t *new_len,
@@ -1780,6 +1835,12 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_BRICK:
       e = Launch<T>::reorder_brick(hs, in, in_s, out, out_s, p->brick, p->n_bricks, stream);
       break;
+    case PLAN_COMPOSE: {  // a batch of one without a fill
+      Remap r = p->remap;
+      const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
+      e = launch_compose(p->dtype, hs, vec, &in_v, &in_s, &out_v, &out_s, nullptr, nullptr, 1, r, stream);
+      break;
+    }
     case PLAN_GATHER_REDUCE: {
       GatherReduce g = p->gr;
       const int vec = remap_for_launch(g.r, p->vec, all_aligned16(in, in_s, out, out_s));
@@ -3576,5 +3637,148 @@ extern "C" int olap_store_load_multi(int n, olap_store *const *targets, const ol
     }
   }
   if (launches) *launches = made;
+  return OLAP_OK;
+}
+
+// ---- compose: the measures of one source cube on the dimensions of a composed cube (Cube.compose) ----------------
+static PlanKey compose_key(const olap_store *s, int ndim, const uint32_t *my_len, const uint32_t *his_len, const int32_t *const *his_to_mine) {
+  PlanKey key;
+  if (bad_dims(ndim, my_len, his_len) || !tables_readable(ndim, his_len, his_to_mine, his_to_mine)) return key;
+  key.i32('C');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim);
+  key.u32s(my_len, ndim), key.u32s(his_len, ndim);
+  key.tables((const uint32_t *const *)his_to_mine, his_len, ndim);
+  return key;
+}
+
+// The arguments of olap_store_compose_multi, refused on the host before any device work (so also without a device), in
+// the order the header lists them.
+static int check_compose_multi(int n, const olap_store *const *sources, olap_store **out, int ndim, const uint32_t *my_len,
+                               const uint32_t *his_len, const int32_t *const *his_to_mine) {
+  if (n < 0 || (n > 0 && !sources)) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
+  for (int i = 0; i < n; ++i)
+    if (!sources[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  int rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  if (rc) return rc;
+  const uint64_t his = product(his_len, ndim);
+  for (int i = 0; i < n; ++i)
+    if (sources[i]->size != his) return fail(OLAP_ERR_LENGTH_MISMATCH, "compose: store sizes do not match the dimensions");
+  for (int i = 1; i < n; ++i)
+    if (sources[i]->device != sources[0]->device)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "compose: the stores live on different devices (%d and %d)", sources[0]->device, sources[i]->device);
+  for (int i = 0; i < n; ++i)
+    if (sources[i]->track_order)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use create, fill and load", i);
+  if (n > 0 && !out) return fail(OLAP_ERR_INVALID_ARGUMENT, "out is NULL");
+  return OLAP_OK;
+}
+
+// ToUint32 of the host (js_to_uint32 of olap_device.hpp)
+static uint32_t host_js_to_uint32(double d) {
+  if (!(std::fabs(d) < 1.7976931348623157e308)) return 0u;
+  double m = std::fmod(std::trunc(d), 4294967296.0);
+  if (m < 0) m += 4294967296.0;
+  return (uint32_t)m;
+}
+
+// The cell olap_store_fill(value) broadcasts into a store of this type and default (from_f64_kernel over one cell:
+// setValue on the number, the typed conversion, then the store invariant), as a float64, and whether it is set.
+static void fill_cell(int dtype, bool def_nan, double value, double *cell, int32_t *set) {
+  *cell = 0.0;
+  *set = 0;
+  if (def_nan ? value != value : value == 0.0) return;
+  switch (dtype) {
+    case OLAP_FLOAT32: {
+      const float f = (float)value;
+      if (def_nan ? f != f : f == 0.0f) return;
+      *cell = (double)f;
+      break;
+    }
+    case OLAP_INT32: {
+      const int32_t v = (int32_t)host_js_to_uint32(value);
+      if (!def_nan && v == 0) return;
+      *cell = (double)v;
+      break;
+    }
+    case OLAP_UINT32: {
+      const uint32_t v = host_js_to_uint32(value);
+      if (!def_nan && v == 0u) return;
+      *cell = (double)v;
+      break;
+    }
+    default: *cell = value; break;
+  }
+  *set = OLAP_STATUS_SET;
+}
+
+// out[i] = what olap_store_create + olap_store_fill(fill[i]) (where has_fill[i]) + olap_store_load(sources[i]) leave, in
+// one pass over the new store's cells.  Sources that share (cell type, default, device) share one cached plan and leave
+// in launches of up to 8; nothing is waited for (see run_to_new_store).
+extern "C" int olap_store_compose_multi(int n, const olap_store *const *sources, const double *fill, const uint8_t *has_fill, olap_store **out,
+                                        int ndim, const uint32_t *my_len, const uint32_t *his_len, const int32_t *const *his_to_mine,
+                                        int *launches) {
+  if (launches) *launches = 0;
+  int rc = check_compose_multi(n, sources, out, ndim, my_len, his_len, his_to_mine);
+  if (rc) return rc;
+  if (n == 0) return OLAP_OK;
+  if ((rc = require_device())) return rc;
+  if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
+  const uint64_t cells = product(my_len, ndim);
+  OnStoreDevice on_device__(sources[0]);
+  std::vector<olap_store *> made(n, nullptr);
+  auto drop = [&](int code) {
+    for (olap_store *s : made)
+      if (s) olap_store_destroy(s);
+    return code;
+  };
+  for (int i = 0; i < n; ++i)
+    if ((rc = store_alloc(&made[i], cells, sources[i]->dtype, sources[i]->default_kind))) return drop(rc);
+  int count = 0;
+  std::vector<char> done(n, 0);
+  for (int i = 0; i < n && cells > 0; ++i) {
+    if (done[i]) continue;
+    const olap_store *s0 = sources[i];
+    std::vector<int> members;
+    for (int j = i; j < n; ++j)
+      if (!done[j] && sources[j]->dtype == s0->dtype && sources[j]->default_kind == s0->default_kind && sources[j]->device == s0->device) {
+        members.push_back(j);
+        done[j] = 1;
+      }
+    PlanRef ref;
+    rc = ref.acquire(compose_key(s0, ndim, my_len, his_len, his_to_mine),
+                     [&](olap_plan **p) { return olap_compose_plan(p, s0->dtype, s0->default_kind, ndim, my_len, his_len, his_to_mine); });
+    if (rc) return drop(rc);
+    olap_plan *p = ref.plan;
+    int cur;
+    if (!begin_run(p, nullptr, &cur)) return drop(foreign_device(p, cur));
+    const bool def_nan = s0->default_kind == OLAP_DEFAULT_NAN;
+    for (size_t first = 0; first < members.size(); first += kMaxBatch) {
+      const unsigned nb = (unsigned)std::min<size_t>(members.size() - first, (size_t)kMaxBatch);
+      const void *in_v[kMaxBatch];
+      const int32_t *in_s[kMaxBatch];
+      void *out_v[kMaxBatch];
+      int32_t *out_s[kMaxBatch];
+      double fill_cells[kMaxBatch];
+      int32_t fill_set[kMaxBatch];
+      bool aligned = true;
+      for (unsigned k = 0; k < nb; ++k) {
+        const int at = members[first + k];
+        in_v[k] = sources[at]->values;
+        in_s[k] = mask_needed(sources[at]);
+        out_v[k] = made[at]->values;
+        out_s[k] = made[at]->status;
+        fill_cells[k] = 0.0, fill_set[k] = 0;
+        if (fill && has_fill && has_fill[at]) fill_cell(s0->dtype, def_nan, fill[at], &fill_cells[k], &fill_set[k]);
+        aligned = aligned && all_aligned16(in_v[k], in_s[k], out_v[k], out_s[k]);
+      }
+      Remap r = p->remap;
+      const int vec = remap_for_launch(r, p->vec, aligned);
+      const hipError_t e = launch_compose(p->dtype, in_s[0] != nullptr, vec, in_v, in_s, out_v, out_s, fill_cells, fill_set, nb, r, nullptr);
+      if (e != hipSuccess) return drop(hip_fail(e, p->kernel_name.c_str()));
+      ++count;
+    }
+  }
+  for (int i = 0; i < n; ++i) out[i] = made[i];
+  if (launches) *launches = count;
   return OLAP_OK;
 }

@@ -4082,6 +4082,14 @@ struct Launch {
 hipError_t launch_load_convert(int his_dtype, int my_dtype, bool has_status, int vec, const void *const *his, const int32_t *const *his_st,
                                void *const *mine, int32_t *const *mine_st, unsigned nb, const Remap &r, hipStream_t stream);
 
+// compose (olap_kernels_compose.hip): nb (his, mine) pairs of one cell type and default in one launch, a gather indexed
+// by MINE — `r` walks my dimensions and yields offsets in his.  vec == 16 / cell size: every lane's 16 bytes of mine are
+// 16 contiguous bytes of his (r.total counts lanes); vec == 1: the per-cell form (r.total counts cells).  fill_set[i] != 0:
+// my cells without a cell of his take fill_cells[i] (the converted cell as a float64) and are set; NULL: no fills.
+hipError_t launch_compose(int dtype, bool has_status, int vec, const void *const *his, const int32_t *const *his_st, void *const *mine,
+                          int32_t *const *mine_st, const double *fill_cells, const int32_t *fill_set, unsigned nb, const Remap &r,
+                          hipStream_t stream);
+
 inline size_t lds_pad_host(size_t e) { return e + (e >> 5); }
 inline unsigned grid_for(uint64_t threads) { return (unsigned)((threads + kBlock - 1) / kBlock); }
 inline unsigned grid_stride_for(uint64_t n) {

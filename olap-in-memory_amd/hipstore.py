@@ -242,6 +242,17 @@ class Plan:
                                      len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr))
         return cls(h)
 
+    @classmethod
+    def compose(cls, dtype, default, my_len, his_len, his_to_mine):
+        """the gather olap_store_compose_multi runs for stores of this cell type and default (olap_compose_plan)"""
+        L = capi.lib()
+        ml, hl = _u32(my_len), _u32(his_len)
+        keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
+        h = C.c_void_p()
+        check(L.olap_compose_plan(C.byref(h), DTYPES[dtype], _default_kind(default), len(ml), ml.ctypes.data_as(capi._pu32),
+                                  hl.ctypes.data_as(capi._pu32), arr))
+        return cls(h)
+
     @property
     def in_cells(self):
         return int(capi.lib().olap_plan_in_cells(self._h))
@@ -645,6 +656,26 @@ class HipStore:
         outs, launches = (C.c_void_p * max(n, 1))(), C.c_int(-1)
         check(capi.lib().olap_store_reorder_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), p.ctypes.data_as(capi._pi32),
                                                   C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
+    @staticmethod
+    def compose_many(sources, my_len, his_len, his_to_mine, fills=None):
+        """The measures of one cube on the dimensions of a composed one (olap_store_compose_multi): new stores of
+        prod(my_len) cells that end as create [+ fill(fills[i]) where fills[i] is not None] + load(sources[i]) leave them,
+        in one pass per group of up to 8.  Returns (new stores in order, kernel launches made)."""
+        ml, hl = _u32(my_len), _u32(his_len)
+        keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
+        n = len(sources)
+        hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in sources])
+        outs, launches = (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        values = has = None
+        if fills is not None:
+            if len(fills) != n:
+                raise ValueError("compose_many: %d sources, %d fills" % (n, len(fills)))
+            values = (C.c_double * max(n, 1))(*[0.0 if f is None else float(f) for f in fills])
+            has = (C.c_uint8 * max(n, 1))(*[0 if f is None else 1 for f in fills])
+        check(capi.lib().olap_store_compose_multi(n, hs, values, has, outs, len(ml), ml.ctypes.data_as(capi._pu32),
+                                                  hl.ctypes.data_as(capi._pu32), arr, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
 

@@ -1050,13 +1050,87 @@ class Cube {
     for (const id of ids) this.storedMeasures[id].load(compatible.storedMeasures[id], this.dimensions, compatible.dimensions);
   }
 
-  compose(otherCube, union = false, fillWith = null) {
+  /** The dimensions both cubes have, each the union or the intersection of the two (src/cube.js:1045-1054). */
+  _composedDimensions(otherCube, union) {
     const newDimensions = [];
     for (const dimension of this.dimensions) {
       const other = otherCube.getDimension(dimension.id);
       if (other) newDimensions.push(union ? dimension.union(other) : dimension.intersect(other));
     }
-    const cube = new Cube(newDimensions);
+    return newDimensions;
+  }
+
+  /**
+   * src/cube.js:1040-1080.  The reference creates, fills and hydrates measure by measure (_composePerMeasure); a repeated
+   * load changes nothing, and a load into a new (or newly filled) store of the same type and default is a gather, so each
+   * source cube is reshaped ONCE and its measures leave in one device call that writes every cell of the new stores once
+   * (HipStore.composeMany, DESIGN.md §3 K12).  Tracked (`first` / `last`) and sharded measures, measures of another store
+   * class and everything under an addon without the call keep create + fill + load, loaded once per source.
+   * HipStore.lastComposeCalls counts the composeMany calls, HipStore.lastBatchLaunches the launches of both kinds.
+   */
+  compose(otherCube, union = false, fillWith = null) {
+    HipStore.lastComposeCalls = 0;
+    const cube = new Cube(this._composedDimensions(otherCube, union));
+    let launches = 0;
+    for (const source of [this, otherCube]) launches += cube._composeFrom(source, fillWith);
+    HipStore.lastBatchLaunches = launches;
+    Object.assign(cube.computedMeasures, this.computedMeasures, otherCube.computedMeasures);
+    return cube;
+  }
+
+  /** The stored measures of `source` as measures of this (new) cube; returns the launches the many-calls reported. */
+  _composeFrom(source, fillWith) {
+    const ids = source.storedMeasureIds;
+    const fillOf = (id) => (fillWith && fillWith[id] ? fillWith[id] : undefined);
+    const stores = {};
+    const create = (id) => {
+      const store = source.storedMeasures[id];
+      stores[id] = this._newStore(store._type, store._defaultValue, source.storedMeasuresRules[id]);
+      if (fillOf(id) !== undefined) stores[id].fill(fillOf(id));
+    };
+    // the measures that may leave in the one pass are not created here: the pass returns their finished stores
+    const ordered = (id) => Object.values(source.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last');
+    const onePass = HipStore.composesMany() && !HipStore.splits(this.dimensions.map((d) => d.numItems));
+    const direct = [];
+    for (const id of ids) {
+      this._checkNewMeasure(id);
+      if (onePass && !ordered(id) && source.storedMeasures[id] instanceof HipStore) direct.push(id);
+      else create(id);
+    }
+    let compatible = null;
+    try {
+      compatible = source.reshape(this.dimensions);
+    } catch (_e) {
+      // no overlap between the cubes: the measures exist, filled, and nothing is loaded
+    }
+    let launches = 0;
+    const together = compatible ? direct.filter((id) => HipStore.composable(compatible.storedMeasures[id])) : [];
+    if (together.length > 0) {
+      const made = HipStore.composeMany(together.map((id) => compatible.storedMeasures[id]), this.dimensions, compatible.dimensions, together.map(fillOf));
+      together.forEach((id, i) => {
+        stores[id] = made[i];
+      });
+      launches += HipStore.lastBatchLaunches;
+    }
+    for (const id of direct) if (!stores[id]) create(id);
+    const rest = compatible ? ids.filter((id) => !together.includes(id) && compatible.storedMeasures[id]) : [];
+    const Store = rest.length >= 1 ? stores[rest[0]].constructor : null;
+    if (Store && typeof Store.loadMany === 'function') {
+      Store.loadMany(rest.map((id) => stores[id]), rest.map((id) => compatible.storedMeasures[id]), this.dimensions, compatible.dimensions);
+      launches += HipStore.lastBatchLaunches;
+    } else {
+      for (const id of rest) stores[id].load(compatible.storedMeasures[id], this.dimensions, compatible.dimensions);
+    }
+    for (const id of ids) {
+      this.storedMeasures[id] = stores[id];
+      this.storedMeasuresRules[id] = source.storedMeasuresRules[id];
+    }
+    return launches;
+  }
+
+  /** compose as the reference orders its calls: one hydrateFromCube per measure (the comparison path of compose). */
+  _composePerMeasure(otherCube, union = false, fillWith = null) {
+    const cube = new Cube(this._composedDimensions(otherCube, union));
     for (const source of [this, otherCube]) {
       for (const id of source.storedMeasureIds) {
         const store = source.storedMeasures[id];
@@ -1065,6 +1139,7 @@ class Cube {
         cube.hydrateFromCube(source);
       }
     }
+    Object.assign(cube.computedMeasures, this.computedMeasures, otherCube.computedMeasures);
     return cube;
   }
 

@@ -933,6 +933,46 @@ class HipStore {
     HipStore.lastLoadPath = path;
   }
 
+  /** Whether composeMany can run: the addon has the call (one built before it existed keeps create + fill + load). */
+  static composesMany() {
+    return typeof backend.load().composeMulti === 'function';
+  }
+
+  /** Whether `store` may be a source of composeMany: held whole on one device, untracked, cells of its declared type. */
+  static composable(store) {
+    if (!(store instanceof HipStore) || store._cells !== cellTypeOf(store._type)) return false;
+    const native = store._pending ? store._pending.source : store._native;
+    return !native.isSharded && !native.orderTracked;
+  }
+
+  /**
+   * The stored measures of ONE source cube on the dimensions of a composed cube — what Cube.compose asked of every
+   * measure in turn as createStoredMeasure + fillData + hydrateFromCube: new stores over `myDimensions` of the sources'
+   * declared type and default that end, values and mask, as `new HipStore; fill(fills[i]); load(sources[i])` leaves them,
+   * in ONE device call (addon composeMulti -> olap_store_compose_multi: a gather that writes every cell of the new
+   * stores once, one launch for up to 8 measures of one cell type and default; DESIGN.md §3 K12).  `fills[i]` undefined
+   * or null: no fill.  The tables are loadTables'; pending selections among the sources are diced together first
+   * (materializeMany).  Every source must be composable().  Sets HipStore.lastBatchLaunches, counts in lastComposeCalls.
+   */
+  static composeMany(sources, myDimensions, hisDimensions, fills = []) {
+    const hisToMine = loadTables(myDimensions, hisDimensions);
+    HipStore.materializeMany(sources);
+    let launches = HipStore.lastBatchLaunches;
+    const values = new Float64Array(sources.length);
+    const hasFill = new Uint8Array(sources.length);
+    sources.forEach((_, i) => {
+      if (fills[i] === undefined || fills[i] === null) return;
+      values[i] = fills[i];
+      hasFill[i] = 1;
+    });
+    const launchesOut = new Int32Array(1);
+    const natives = backend.load().composeMulti(sources.map((store) => store._whole), lengthsOf(myDimensions), lengthsOf(hisDimensions), hisToMine, values, hasFill, launchesOut);
+    launches += launchesOut[0];
+    HipStore.lastComposeCalls += 1;
+    HipStore.lastBatchLaunches = launches;
+    return sources.map((store, i) => store._wrap(natives[i]));
+  }
+
   /**
    * What every combination of the scanned dimensions' items receives, for the stored measures of one cube, in ONE device
    * call (addon blocksReport -> olap_store_blocks_report): `scannedFlags[d]` marks the scanned dimensions.  Returns one
@@ -1008,6 +1048,9 @@ HipStore.blocksMaxBlockCells = 500000;
 // drillDownMany and the pending selections of drillUpMany: what diceMulti / drillDownMulti / diceDrillUpMulti launched;
 // loadMany and a load between cell types: what loadMulti launched on top)
 HipStore.lastBatchLaunches = null;
+// the composeMulti calls the last Cube.compose made: one per source cube that had a measure for it, 0 when every measure
+// took create + fill + load; Cube resets it when compose starts
+HipStore.lastComposeCalls = 0;
 // kernel launches reorderMulti reported for the last reorderMany (null: every measure took reorder one by one)
 HipStore.lastReorderLaunches = null;
 // 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the

@@ -1146,6 +1146,38 @@ static napi_value LoadMulti(napi_env env, napi_callback_info info) {
   return nullptr;
 }
 
+// composeMulti(sources: Store[], myLen, hisLen, hisToMine: Int32Array[], fills: Float64Array, hasFill: Uint8Array, launchesOut?: Int32Array)
+//   -> Store[]: new stores that end as create [+ fill(fills[i]) where hasFill[i]] + load(sources[i]) (olap_store_compose_multi)
+static napi_value ComposeMulti(napi_env env, napi_callback_info info) {
+  const char *usage =
+      "composeMulti(sources: Store[], myLen: Uint32Array, hisLen: Uint32Array, hisToMine: Int32Array[], fills: Float64Array, hasFill: Uint8Array, "
+      "launchesOut?: Int32Array)";
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs m;
+  bool bad = true;
+  if (argc < 6 || !a.decode(env, argv[1], argv[2], argv[3])) return bad_args(env, usage);
+  for (size_t d = 0; d < a.tables.size(); ++d)
+    if (a.tables[d].size() != a.b_len[d]) return bad_args(env, usage);  // one entry per item of his
+  if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  napi_typedarray_type vt, ft;
+  size_t n_values = 0, n_flags = 0;
+  void *values = nullptr, *flags = nullptr;
+  if (napi_get_typedarray_info(env, argv[4], &vt, &n_values, &values, nullptr, nullptr) != napi_ok || vt != napi_float64_array ||
+      napi_get_typedarray_info(env, argv[5], &ft, &n_flags, &flags, nullptr, nullptr) != napi_ok || ft != napi_uint8_array ||
+      n_values != m.stores.size() || n_flags != m.stores.size())
+    return bad_args(env, usage);
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int launches = 0;
+  int rc = olap_store_compose_multi((int)m.stores.size(), m.stores.data(), (const double *)values, (const uint8_t *)flags, outs.data(),
+                                    (int)a.a_len.size(), a.a_len.data(), a.b_len.data(), (const int32_t *const *)a.ptrs.data(), &launches);
+  if (rc) return throw_olap(env, rc);
+  if (argc > 6) set_path(env, argv[6], launches);
+  return wrap_new_stores(env, outs);
+}
+
 // blocksReport(stores: Store[], lens: Uint32Array, scanned: Uint8Array, launchesOut?: Int32Array)
 //   -> Float64Array of stores.length results, one after the other, each [scanned..., kept...] (olap_store_blocks_report)
 static napi_value BlocksReport(napi_env env, napi_callback_info info) {
@@ -1809,6 +1841,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"diceMulti", nullptr, DiceMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"reorderMulti", nullptr, ReorderMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"loadMulti", nullptr, LoadMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"composeMulti", nullptr, ComposeMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"blocksReport", nullptr, BlocksReport, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"diceDrillUpMulti", nullptr, DiceDrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
