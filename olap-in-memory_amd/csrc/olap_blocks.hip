@@ -252,9 +252,9 @@ uint64_t blocks_byte_cap() {
 // The arguments, refused on the host before any device work, in the order the header lists them.
 int check_blocks(int n, const olap_store *const *stores, int ndim, const uint32_t *lens, const uint8_t *scanned, const double *host_values,
                  uint64_t *size, uint64_t *kept_cells) {
-  if (n < 0 || (n > 0 && (!stores || !host_values))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
-  for (int i = 0; i < n; ++i)
-    if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  int rc = check_list(n, stores && host_values, "store list is NULL");
+  if (!rc) rc = check_entries(n, stores);
+  if (rc) return rc;
   if (ndim < 0 || ndim > OLAP_MAX_DIMS) return fail(OLAP_ERR_INVALID_ARGUMENT, "ndim %d out of range [0, %d]", ndim, OLAP_MAX_DIMS);
   if (ndim > 0 && !lens) return fail(OLAP_ERR_INVALID_ARGUMENT, "dimension length vectors must not be NULL");
   if (ndim > 0 && !scanned) return fail(OLAP_ERR_INVALID_ARGUMENT, "scanned flags are NULL");
@@ -264,16 +264,11 @@ int check_blocks(int n, const olap_store *const *stores, int ndim, const uint32_
   const uint64_t combos = product_of(ndim, lens, scanned, true), kept = product_of(ndim, lens, scanned, false);
   if (combos == 0 || kept == 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "blocks: a dimension has no items");
   const uint64_t cells = product_of(ndim, lens, nullptr, true);
-  for (int i = 0; i < n; ++i)
-    if (stores[i]->size != cells)
-      return fail(OLAP_ERR_LENGTH_MISMATCH, "store holds %llu cells but the dimensions describe %llu", (unsigned long long)stores[i]->size,
-                  (unsigned long long)cells);
+  if ((rc = check_cells(n, stores, cells))) return rc;
   for (int i = 1; i < n; ++i)
     if (stores[i]->device != stores[0]->device)
       return fail(OLAP_ERR_INVALID_ARGUMENT, "blocks: the stores live on different devices (%d and %d)", stores[0]->device, stores[i]->device);
-  for (int i = 0; i < n; ++i)
-    if (stores[i]->track_order)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use the single-store call", i);
+  if ((rc = check_untracked(n, stores, "use the single-store call"))) return rc;
   const uint64_t cap = blocks_byte_cap();
   if (n > 0 && cells > cap / 8 / (uint64_t)n)
     return fail(OLAP_ERR_INVALID_ARGUMENT, "blocks: %d stores of %llu cells are more than the %llu bytes of one call", n, (unsigned long long)cells,
@@ -293,14 +288,10 @@ int run_group(const BlocksPlan &p, const olap_store *const *stores, const std::v
     const unsigned nb = (unsigned)std::min<size_t>(members.size() - first, (size_t)kMaxBatch);
     Batch<T> b{};
     BlockSlots o{};
-    bool aligned16 = true;
-    for (unsigned i = 0; i < nb; ++i) {
+    const bool aligned16 = fill_chunk((int)nb, b.in, b.st_in, o.out, (int32_t **)nullptr, [&](int i) {
       const olap_store *s = stores[members[first + i]];
-      b.in[i] = (const T *)s->values;
-      b.st_in[i] = has_status ? s->status : nullptr;
-      o.out[i] = slab + (uint64_t)members[first + i] * size;
-      aligned16 = aligned16 && (((uintptr_t)b.in[i] | (uintptr_t)b.st_in[i] | (uintptr_t)o.out[i]) & 15u) == 0;
-    }
+      return PairBuffers{s->values, has_status ? s->status : nullptr, slab + (uint64_t)members[first + i] * size, nullptr};
+    });
     const hipError_t e = launch_blocks<T>(p, has_status, b, o, nb, size, aligned16, def_nan);
     if (e != hipSuccess) return hip_fail(e, "blocks_report");
     ++*made;
@@ -323,18 +314,11 @@ extern "C" int olap_store_blocks_report(int n, const olap_store *const *stores, 
   double *slab = nullptr;
   HIP_TRY(dev_alloc((void **)&slab, (uint64_t)n * size * sizeof(double)));
   int made = 0;
-  std::vector<char> done(n, 0);
-  for (int i = 0; i < n && !rc; ++i) {
-    if (done[i]) continue;
-    const olap_store *s0 = stores[i];
-    std::vector<int> members;  // cell type and default decide whether a store keeps a mask
-    for (int j = i; j < n; ++j)
-      if (!done[j] && stores[j]->dtype == s0->dtype && stores[j]->default_kind == s0->default_kind) {
-        members.push_back(j);
-        done[j] = 1;
-      }
-    DISPATCH_DTYPE(s0->dtype, T, rc = run_group<T>(plan, stores, members, slab, size, &made));
-  }
+  rc = for_each_group(  // cell type and default decide whether a store keeps a mask
+      n, [&](int i, int j) { return same_cells(stores[j], stores[i]); },
+      [&](const std::vector<int> &members) {
+        DISPATCH_DTYPE(stores[members[0]]->dtype, T, return run_group<T>(plan, stores, members, slab, size, &made));
+      });
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpy(host_values, slab, (uint64_t)n * size * sizeof(double), hipMemcpyDeviceToHost);  // the call's only wait
   else (void)hipStreamSynchronize(nullptr);  // launches already made still write the slab

@@ -1736,11 +1736,6 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
 }
 
 // ---- run ------------------------------------------------------------------------------------
-// every buffer of a launch starts on a 16-byte boundary (a buffer the launch does not have is passed as nullptr)
-static bool all_aligned16(const void *in, const void *in_s, const void *out, const void *out_s) {
-  return (((uintptr_t)in | (uintptr_t)in_s | (uintptr_t)out | (uintptr_t)out_s) & 15u) == 0;
-}
-
 // What a launch over p->axis runs with: buffers off the 16-byte grid take one cell per lane.  The drillDown row
 // kernels read neither `total` nor `xcd_order`, and the mixed-rule launcher declines unaligned buffers before it
 // looks at the lane width, so one preparation serves all four launches.
@@ -1924,15 +1919,10 @@ struct Pairs {
 template <typename T>
 static Batch<T> fill_batch(const Pairs &q, int first, int nb, const int *methods, bool *aligned) {
   Batch<T> b{};
-  *aligned = true;
-  for (int i = 0; i < nb; ++i) {
-    b.in[i] = (const T *)q.in_v[first + i];
-    b.st_in[i] = q.masks() ? q.in_s[first + i] : nullptr;
-    b.out[i] = (T *)q.out_v[first + i];
-    b.st_out[i] = q.out_s ? q.out_s[first + i] : nullptr;
-    if (methods) b.method[i] = methods[first + i];
-    *aligned = *aligned && all_aligned16(b.in[i], b.st_in[i], b.out[i], b.st_out[i]);
-  }
+  *aligned = fill_chunk(nb, b.in, b.st_in, b.out, b.st_out, [&](int i) {
+    return PairBuffers{q.in_v[first + i], q.masks() ? q.in_s[first + i] : nullptr, q.out_v[first + i], q.out_s ? q.out_s[first + i] : nullptr};
+  });
+  for (int i = 0; methods && i < nb; ++i) b.method[i] = methods[first + i];
   return b;
 }
 
@@ -3072,9 +3062,28 @@ static int run_to_new_store(olap_plan *plan, const olap_store *in, olap_store **
   return OLAP_OK;
 }
 
-static int check_store_cells(const olap_store *s, const olap_plan *plan) {
-  if (s->size != olap_plan_in_cells(plan))
-    return fail(OLAP_ERR_LENGTH_MISMATCH, "store holds %llu cells but the dimensions describe %llu", (unsigned long long)s->size, (unsigned long long)olap_plan_in_cells(plan));
+// ---- the refusals of a list of stores (olap_internal.hpp)
+int check_list(int n, bool there, const char *what) { return n < 0 || (n > 0 && !there) ? fail(OLAP_ERR_INVALID_ARGUMENT, "%s", what) : OLAP_OK; }
+int check_entry(const olap_store *s, int i) { return s ? OLAP_OK : fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i); }
+
+int check_entries(int n, const olap_store *const *stores) {
+  int rc = OLAP_OK;
+  for (int i = 0; i < n && !rc; ++i) rc = check_entry(stores[i], i);
+  return rc;
+}
+
+int check_untracked(int n, const olap_store *const *stores, const char *advice) {
+  for (int i = 0; i < n; ++i)
+    if (stores[i]->track_order) return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; %s", i, advice);
+  return OLAP_OK;
+}
+
+int check_cells(int n, const olap_store *const *stores, uint64_t cells, const char *what) {
+  for (int i = 0; i < n; ++i) {
+    if (stores[i]->size == cells) continue;
+    if (what) return fail(OLAP_ERR_LENGTH_MISMATCH, "%s", what);
+    return fail(OLAP_ERR_LENGTH_MISMATCH, "store holds %llu cells but the dimensions describe %llu", (unsigned long long)stores[i]->size, (unsigned long long)cells);
+  }
   return OLAP_OK;
 }
 
@@ -3181,7 +3190,7 @@ template <typename Build>
 static int run_cached(const olap_store *s, olap_store **out, const PlanKey &key, Build build, bool (*keep)(const olap_plan *) = nullptr) {
   PlanRef ref;
   int rc = ref.acquire(key, build, keep);
-  if (!rc) rc = check_store_cells(s, ref.plan);
+  if (!rc) rc = check_cells(1, &s, olap_plan_in_cells(ref.plan));
   if (!rc) rc = run_to_new_store(ref.plan, s, out);
   return rc;
 }
@@ -3205,8 +3214,7 @@ int store_drillup_plain(const olap_store *s, olap_store **out, int ndim, const u
 static bool same_shape(int n, const olap_store *const *stores) {
   bool same = n > 1;
   for (int i = 0; i < n && same; ++i)
-    same = stores[i]->dtype == stores[0]->dtype && stores[i]->default_kind == stores[0]->default_kind && stores[i]->size == stores[0]->size &&
-           stores[i]->device == stores[0]->device && !stores[i]->track_order;
+    same = same_cells(stores[i], stores[0]) && stores[i]->size == stores[0]->size && stores[i]->device == stores[0]->device && !stores[i]->track_order;
   return same;
 }
 
@@ -3220,74 +3228,88 @@ static int drop_results(int n, olap_store **out, int rc) {
 }
 
 namespace {
-// The buffers of a batch of n over one plan: allocates the results and lists every pair's pointers.
+// The buffers of a batch of m pairs over one plan, listed as the run entry points take them.  Pair k is member
+// at[k] of the caller's lists (at == nullptr: member k).
 struct BatchBuffers {
   std::vector<const void *> in_v;
   std::vector<const int32_t *> in_s;
   std::vector<void *> out_v;
   std::vector<int32_t *> out_s;
-  explicit BatchBuffers(int n) : in_v(n), in_s(n), out_v(n), out_s(n) {}
-  int alloc(const olap_plan *plan, const olap_store *const *stores, olap_store **out) {
-    for (int i = 0; i < (int)in_v.size(); ++i) {
-      const int rc = store_alloc(&out[i], olap_plan_out_cells(plan), stores[0]->dtype, stores[0]->default_kind);
-      if (rc) return rc;
-      in_v[i] = stores[i]->values;
-      in_s[i] = mask_needed(stores[i]);
-      out_v[i] = out[i]->values;
-      out_s[i] = out[i]->status;
+  explicit BatchBuffers(int m) : in_v(m), in_s(m), out_v(m), out_s(m) {}
+  // pairs that exist: from[i] into to[i]
+  void list(const int *at, const olap_store *const *from, olap_store *const *to) {
+    for (int k = 0; k < (int)in_v.size(); ++k) {
+      const int i = at ? at[k] : k;
+      in_v[k] = from[i]->values;
+      in_s[k] = mask_needed(from[i]);
+      out_v[k] = to[i]->values;
+      out_s[k] = to[i]->status;
     }
+  }
+  // allocates the results first: stores like `like` of as many cells as the plan writes
+  int alloc(const olap_plan *plan, const olap_store *like, const int *at, const olap_store *const *stores, olap_store **out) {
+    for (int k = 0; k < (int)in_v.size(); ++k) {
+      const int rc = store_alloc(&out[at ? at[k] : k], olap_plan_out_cells(plan), like->dtype, like->default_kind);
+      if (rc) return rc;
+    }
+    list(at, stores, out);
     return OLAP_OK;
   }
   Pairs pairs() const { return Pairs{(int)in_v.size(), in_v.data(), in_s.data(), out_v.data(), out_s.data()}; }
 };
 }  // namespace
 
+// The m members at[0..m) of `stores` (at == nullptr: 0..m) — one group: same cell type, default, size and device —
+// through one (cached) plan into freshly allocated stores out[at[k]].  key() is written on the group's device (a key
+// names it); unkeyed != 0: returned, with nothing done, when the key stays empty.  run(plan, pairs) launches; on any
+// failure none of the group's results stays.
+template <typename Key, typename Build, typename Run>
+static int run_group(int m, const int *at, const olap_store *const *stores, olap_store **out, Key key, int unkeyed, Build build,
+                     bool (*keep)(const olap_plan *), Run run) {
+  const olap_store *s0 = stores[at ? at[0] : 0];
+  OnStoreDevice on_device__(s0);
+  const PlanKey k = key();
+  if (unkeyed && k.empty()) return unkeyed;
+  PlanRef ref;
+  int rc = ref.acquire(k, build, keep);
+  BatchBuffers b(m);
+  if (!rc) rc = check_cells(1, &s0, olap_plan_in_cells(ref.plan));
+  if (!rc) rc = b.alloc(ref.plan, s0, at, stores, out);
+  if (!rc) rc = run(ref.plan, b.pairs());
+  for (int i = 0; rc && i < m; ++i) drop_results(1, &out[at ? at[i] : i], rc);
+  return rc;
+}
+
 // Cube.drillUp over several stored measures that share cell type, default and rule (src/cube.js:1012-1020 calls the
 // store once per measure): one plan, one launch (olap_plan_run_batch).  Stores that differ in type or default, or that
 // track their insertion order, take the single-store path one by one — same results, n launches.
 extern "C" int olap_store_drillup_batch(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *old_len,
                                         const uint32_t *new_len, const uint32_t *const *maps, int method) {
-  if (n < 0 || (n > 0 && (!stores || !out))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
+  int rc = check_list(n, stores && out, "store list is NULL");
+  if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
-  for (int i = 0; i < n; ++i)
-    if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  if ((rc = check_entries(n, stores))) return rc;
   if (!same_shape(n, stores) || bad_dims(ndim, old_len, new_len) || (ndim > 0 && !maps)) {
-    for (int i = 0; i < n; ++i) {
-      const int rc = olap_store_drillup(stores[i], &out[i], ndim, old_len, new_len, maps, method);
-      if (rc) return drop_results(n, out, rc);
-    }
-    return OLAP_OK;
+    for (int i = 0; i < n && !rc; ++i) rc = olap_store_drillup(stores[i], &out[i], ndim, old_len, new_len, maps, method);
+    return rc ? drop_results(n, out, rc) : OLAP_OK;
   }
   const olap_store *s0 = stores[0];
-  OnStoreDevice on_device__(s0);
-  PlanRef ref;
-  int rc = ref.acquire(drillup_key(s0, method, ndim, old_len, new_len, maps),
-                       [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, method, ndim, old_len, new_len, maps); });
-  if (rc) return rc;
-  BatchBuffers b(n);
-  rc = check_store_cells(s0, ref.plan);
-  if (!rc) rc = b.alloc(ref.plan, stores, out);
-  if (!rc) rc = olap_plan_run_batch(ref.plan, n, b.in_v.data(), b.in_s.data(), b.out_v.data(), b.out_s.data(), nullptr);
-  return rc ? drop_results(n, out, rc) : OLAP_OK;
+  return run_group(
+      n, nullptr, stores, out, [&] { return drillup_key(s0, method, ndim, old_len, new_len, maps); }, 0,
+      [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, method, ndim, old_len, new_len, maps); }, nullptr,
+      [](olap_plan *plan, const Pairs &q) { return olap_plan_run_batch(plan, q.n, q.in_v, q.in_s, q.out_v, q.out_s, nullptr); });
 }
 
 // The measures of one shape with a rule each, as mixed-rule launches over the plan of the first rule (a drillUp plan's
 // tables do not depend on the rule).  OLAP_MIXED_NOT_APPLICABLE: the caller goes rule by rule, which also reports
-// arguments that are not there to read.  The caller drops the results on any failure.
+// arguments that are not there to read.
 static int drillup_mixed(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim, const uint32_t *old_len,
                          const uint32_t *new_len, const uint32_t *const *maps) {
   const olap_store *s0 = stores[0];
-  OnStoreDevice on_device__(s0);
-  const PlanKey key = drillup_key(s0, methods[0], ndim, old_len, new_len, maps);
-  if (key.empty()) return OLAP_MIXED_NOT_APPLICABLE;
-  PlanRef ref;
-  int rc = ref.acquire(key, [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, methods[0], ndim, old_len, new_len, maps); });
-  if (rc) return rc;
-  BatchBuffers b(n);
-  rc = check_store_cells(s0, ref.plan);
-  if (!rc) rc = b.alloc(ref.plan, stores, out);
-  if (!rc) rc = plan_run_mixed(ref.plan, b.pairs(), methods, nullptr);
-  return rc;
+  return run_group(
+      n, nullptr, stores, out, [&] { return drillup_key(s0, methods[0], ndim, old_len, new_len, maps); }, OLAP_MIXED_NOT_APPLICABLE,
+      [&](olap_plan **p) { return olap_drillup_plan(p, s0->dtype, s0->default_kind, methods[0], ndim, old_len, new_len, maps); }, nullptr,
+      [&](olap_plan *plan, const Pairs &q) { return plan_run_mixed(plan, q, methods, nullptr); });
 }
 
 // Cube.drillUp over ALL stored measures of a cube, each with its own rule for the rolled-up dimension (methods[i]):
@@ -3295,39 +3317,31 @@ static int drillup_mixed(int n, const olap_store *const *stores, const int *meth
 // the row regime (drillup_rows_mixed_kernel), one launch per rule otherwise — the rest one by one.
 extern "C" int olap_store_drillup_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
                                         const uint32_t *old_len, const uint32_t *new_len, const uint32_t *const *maps) {
-  if (n < 0 || (n > 0 && (!stores || !out || !methods))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store / method list is NULL");
+  int rc = check_list(n, stores && out && methods, "store / method list is NULL");
+  if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   for (int i = 0; i < n; ++i) {
-    if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+    if ((rc = check_entry(stores[i], i))) return rc;
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
   }
   bool one_rule = true;
   for (int i = 0; i < n; ++i) one_rule = one_rule && methods[i] == methods[0];
   if (same_shape(n, stores) && !one_rule) {
-    const int rc = drillup_mixed(n, stores, methods, out, ndim, old_len, new_len, maps);
-    if (rc == OLAP_OK) return OLAP_OK;
-    drop_results(n, out, rc);
+    rc = drillup_mixed(n, stores, methods, out, ndim, old_len, new_len, maps);
     if (rc != OLAP_MIXED_NOT_APPLICABLE) return rc;
   }
   // rule by rule: the measures of one rule together (olap_store_drillup_batch groups further by cell type)
-  std::vector<char> done(n, 0);
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    std::vector<int> members;
-    for (int j = i; j < n; ++j)
-      if (!done[j] && methods[j] == methods[i] && stores[j]->dtype == stores[i]->dtype && stores[j]->default_kind == stores[i]->default_kind &&
-          stores[j]->size == stores[i]->size) {
-        members.push_back(j);
-        done[j] = 1;
-      }
-    std::vector<const olap_store *> in(members.size());
-    std::vector<olap_store *> res(members.size(), nullptr);
-    for (size_t k = 0; k < members.size(); ++k) in[k] = stores[members[k]];
-    const int rc = olap_store_drillup_batch((int)members.size(), in.data(), res.data(), ndim, old_len, new_len, maps, methods[i]);
-    if (rc) return drop_results(n, out, rc);
-    for (size_t k = 0; k < members.size(); ++k) out[members[k]] = res[k];
-  }
-  return OLAP_OK;
+  rc = for_each_group(
+      n, [&](int i, int j) { return methods[j] == methods[i] && same_cells(stores[j], stores[i]) && stores[j]->size == stores[i]->size; },
+      [&](const std::vector<int> &members) {
+        std::vector<const olap_store *> in(members.size());
+        std::vector<olap_store *> res(members.size(), nullptr);
+        for (size_t k = 0; k < members.size(); ++k) in[k] = stores[members[k]];
+        const int rc = olap_store_drillup_batch((int)members.size(), in.data(), res.data(), ndim, old_len, new_len, maps, methods[members[0]]);
+        for (size_t k = 0; k < members.size() && !rc; ++k) out[members[k]] = res[k];
+        return rc;
+      });
+  return rc ? drop_results(n, out, rc) : OLAP_OK;
 }
 
 static int store_drilldown_plain(const olap_store *s, olap_store **out, int ndim, const uint32_t *old_len,
@@ -3400,24 +3414,17 @@ extern "C" int olap_store_dice_drillup(const olap_store *s, olap_store **out, in
 // launches of up to 8 (olap_plan_run_batch); a measure alone in its group runs as the single-store call does.
 static int check_multi(int n, const olap_store *const *stores, const int *methods, bool need_methods, int method_mask, olap_store **out, int ndim,
                        const uint32_t *old_len, const uint32_t *new_len) {
-  if (n < 0 || (n > 0 && (!stores || !out || (need_methods && !methods)))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store / method list is NULL");
+  int rc = check_list(n, stores && out && (!need_methods || methods), "store / method list is NULL");
+  if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
-  for (int i = 0; i < n; ++i)
-    if (!stores[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
+  if ((rc = check_entries(n, stores))) return rc;
   // the lists, the rules and the lengths first: refused without looking into a store
   for (int i = 0; i < n && need_methods; ++i)
     if ((methods[i] & ~method_mask) < OLAP_SUM || (methods[i] & ~method_mask) > OLAP_PRODUCT)
       return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
-  const int rc = check_dims(ndim, old_len, new_len);
-  if (rc) return rc;
-  for (int i = 0; i < n; ++i)
-    if (stores[i]->track_order)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use the single-store call", i);
-  const uint64_t cells = product(old_len, ndim);
-  for (int i = 0; i < n; ++i)
-    if (stores[i]->size != cells)
-      return fail(OLAP_ERR_LENGTH_MISMATCH, "store holds %llu cells but the dimensions describe %llu", (unsigned long long)stores[i]->size, (unsigned long long)cells);
-  return OLAP_OK;
+  if ((rc = check_dims(ndim, old_len, new_len))) return rc;
+  if ((rc = check_untracked(n, stores, "use the single-store call"))) return rc;
+  return check_cells(n, stores, product(old_len, ndim));
 }
 
 // key(store, rule) / build(&plan, store, rule): the operation's plan for a group, named by its first member
@@ -3425,35 +3432,16 @@ template <typename Key, typename Build>
 static int run_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int *launches, Key key, Build build,
                      bool (*keep)(const olap_plan *) = nullptr) {
   int made = 0;
-  std::vector<char> done(n, 0);
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    const olap_store *s0 = stores[i];
-    const int rule = methods ? methods[i] : 0;
-    std::vector<int> members;
-    for (int j = i; j < n; ++j)
-      if (!done[j] && (!methods || methods[j] == rule) && stores[j]->dtype == s0->dtype && stores[j]->default_kind == s0->default_kind &&
-          stores[j]->device == s0->device) {
-        members.push_back(j);
-        done[j] = 1;
-      }
-    const int m = (int)members.size();
-    std::vector<const olap_store *> in(m);
-    std::vector<olap_store *> res(m, nullptr);
-    for (int k = 0; k < m; ++k) in[k] = stores[members[k]];
-    OnStoreDevice on_device__(s0);
-    PlanRef ref;
-    int rc = ref.acquire(key(s0, rule), [&](olap_plan **p) { return build(p, s0, rule); }, keep);
-    BatchBuffers b(m);
-    if (!rc) rc = check_store_cells(s0, ref.plan);
-    if (!rc) rc = b.alloc(ref.plan, in.data(), res.data());
-    if (!rc) rc = plan_run_batch_counted(ref.plan, m, b.in_v.data(), b.in_s.data(), b.out_v.data(), b.out_s.data(), nullptr, &made);
-    if (rc) {
-      drop_results(m, res.data(), rc);
-      return drop_results(n, out, rc);
-    }
-    for (int k = 0; k < m; ++k) out[members[k]] = res[k];
-  }
+  const int rc = for_each_group(
+      n, [&](int i, int j) { return (!methods || methods[j] == methods[i]) && same_cells(stores[j], stores[i]) && stores[j]->device == stores[i]->device; },
+      [&](const std::vector<int> &members) {
+        const olap_store *s0 = stores[members[0]];
+        const int rule = methods ? methods[members[0]] : 0;
+        return run_group(
+            (int)members.size(), members.data(), stores, out, [&] { return key(s0, rule); }, 0, [&](olap_plan **p) { return build(p, s0, rule); }, keep,
+            [&](olap_plan *plan, const Pairs &q) { return plan_run_batch_counted(plan, q.n, q.in_v, q.in_s, q.out_v, q.out_s, nullptr, &made); });
+      });
+  if (rc) return drop_results(n, out, rc);
   if (launches) *launches = made;
   return OLAP_OK;
 }
@@ -3568,20 +3556,18 @@ static PlanKey load_key(const olap_store *mine, const olap_store *his, int ndim,
 // the order the header lists them.
 static int check_load_multi(int n, olap_store *const *targets, const olap_store *const *sources, int ndim, const uint32_t *my_len,
                             const uint32_t *his_len, const int32_t *const *his_to_mine) {
-  if (n < 0 || (n > 0 && (!targets || !sources))) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
-  for (int i = 0; i < n; ++i)
-    if (!targets[i] || !sources[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
-  int rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  int rc = check_list(n, targets && sources, "store list is NULL");
+  for (int i = 0; i < n && !rc; ++i)
+    if (!(rc = check_entry(targets[i], i))) rc = check_entry(sources[i], i);
+  if (!rc) rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  // (one wording for both sides: which of the two loops finds the mismatch does not show)
+  if (!rc) rc = check_cells(n, sources, product(his_len, ndim), "load: store sizes do not match the dimensions");
+  if (!rc) rc = check_cells(n, targets, product(my_len, ndim), "load: store sizes do not match the dimensions");
   if (rc) return rc;
-  const uint64_t mine = product(my_len, ndim), his = product(his_len, ndim);
-  for (int i = 0; i < n; ++i)
-    if (sources[i]->size != his || targets[i]->size != mine) return fail(OLAP_ERR_LENGTH_MISMATCH, "load: store sizes do not match the dimensions");
   for (int i = 0; i < n; ++i)
     if (targets[i]->device != sources[i]->device)
       return fail(OLAP_ERR_INVALID_ARGUMENT, "load: the stores live on different devices (%d and %d)", targets[i]->device, sources[i]->device);
-  for (int i = 0; i < n; ++i)
-    if (targets[i]->track_order)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use the single-store call", i);
+  if ((rc = check_untracked(n, targets, "use the single-store call"))) return rc;
   for (int i = 0; i < n; ++i)
     for (int j = 0; j < n; ++j)
       if ((j > i && targets[j] == targets[i]) || sources[j] == targets[i])
@@ -3597,45 +3583,29 @@ extern "C" int olap_store_load_multi(int n, olap_store *const *targets, const ol
   int rc = check_load_multi(n, targets, sources, ndim, my_len, his_len, his_to_mine);
   if (rc) return rc;
   int made = 0;
-  std::vector<char> done(n > 0 ? n : 1, 0);
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    olap_store *t0 = targets[i];
-    const olap_store *s0 = sources[i];
-    std::vector<int> members;
-    for (int j = i; j < n; ++j)
-      if (!done[j] && targets[j]->dtype == t0->dtype && sources[j]->dtype == s0->dtype && targets[j]->default_kind == t0->default_kind &&
-          sources[j]->default_kind == s0->default_kind && targets[j]->device == t0->device) {
-        members.push_back(j);
-        done[j] = 1;
-      }
-    const int m = (int)members.size();
-    OnStoreDevice on_device__(t0);
-    PlanRef ref;
-    rc = ref.acquire(load_key(t0, s0, ndim, my_len, his_len, his_to_mine), [&](olap_plan **p) {
-      return olap_load_plan_typed(p, t0->dtype, s0->dtype, t0->default_kind, s0->default_kind, ndim, my_len, his_len, his_to_mine);
-    });
-    if (rc) return rc;
-    std::vector<const void *> in_v(m);
-    std::vector<const int32_t *> in_s(m);
-    std::vector<void *> out_v(m);
-    std::vector<int32_t *> out_s(m);
-    for (int k = 0; k < m; ++k) {
-      olap_store *t = targets[members[k]];
-      drop_lazy_status(t);
-      in_v[k] = sources[members[k]]->values;
-      in_s[k] = mask_needed(sources[members[k]]);
-      out_v[k] = t->values;
-      out_s[k] = t->status;
-    }
-    rc = plan_run_batch_counted(ref.plan, m, in_v.data(), in_s.data(), out_v.data(), out_s.data(), nullptr, &made);
-    if (rc) return rc;
-    for (int k = 0; k < m; ++k) {  // what order_after_load records for an untracked store
-      olap_store *t = targets[members[k]];
-      t->maybe_nonempty = true;
-      t->hi_index = t->size ? t->size - 1 : 0;
-    }
-  }
+  rc = for_each_group(
+      n, [&](int i, int j) { return same_cells(targets[j], targets[i]) && same_cells(sources[j], sources[i]) && targets[j]->device == targets[i]->device; },
+      [&](const std::vector<int> &members) {
+        olap_store *t0 = targets[members[0]];
+        const olap_store *s0 = sources[members[0]];
+        OnStoreDevice on_device__(t0);
+        PlanRef ref;
+        int rc = ref.acquire(load_key(t0, s0, ndim, my_len, his_len, his_to_mine), [&](olap_plan **p) {
+          return olap_load_plan_typed(p, t0->dtype, s0->dtype, t0->default_kind, s0->default_kind, ndim, my_len, his_len, his_to_mine);
+        });
+        if (rc) return rc;
+        for (int at : members) drop_lazy_status(targets[at]);
+        BatchBuffers b((int)members.size());
+        b.list(members.data(), sources, targets);
+        const Pairs q = b.pairs();
+        if ((rc = plan_run_batch_counted(ref.plan, q.n, q.in_v, q.in_s, q.out_v, q.out_s, nullptr, &made))) return rc;
+        for (int at : members) {  // what order_after_load records for an untracked store
+          targets[at]->maybe_nonempty = true;
+          targets[at]->hi_index = targets[at]->size ? targets[at]->size - 1 : 0;
+        }
+        return rc;
+      });
+  if (rc) return rc;
   if (launches) *launches = made;
   return OLAP_OK;
 }
@@ -3655,22 +3625,16 @@ static PlanKey compose_key(const olap_store *s, int ndim, const uint32_t *my_len
 // the order the header lists them.
 static int check_compose_multi(int n, const olap_store *const *sources, olap_store **out, int ndim, const uint32_t *my_len,
                                const uint32_t *his_len, const int32_t *const *his_to_mine) {
-  if (n < 0 || (n > 0 && !sources)) return fail(OLAP_ERR_INVALID_ARGUMENT, "store list is NULL");
-  for (int i = 0; i < n; ++i)
-    if (!sources[i]) return fail(OLAP_ERR_INVALID_ARGUMENT, "store %d of the batch is NULL", i);
-  int rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  int rc = check_list(n, sources, "store list is NULL");
+  if (!rc) rc = check_entries(n, sources);
+  if (!rc) rc = check_load_maps(ndim, my_len, his_len, his_to_mine);
+  if (!rc) rc = check_cells(n, sources, product(his_len, ndim), "compose: store sizes do not match the dimensions");
   if (rc) return rc;
-  const uint64_t his = product(his_len, ndim);
-  for (int i = 0; i < n; ++i)
-    if (sources[i]->size != his) return fail(OLAP_ERR_LENGTH_MISMATCH, "compose: store sizes do not match the dimensions");
   for (int i = 1; i < n; ++i)
     if (sources[i]->device != sources[0]->device)
       return fail(OLAP_ERR_INVALID_ARGUMENT, "compose: the stores live on different devices (%d and %d)", sources[0]->device, sources[i]->device);
-  for (int i = 0; i < n; ++i)
-    if (sources[i]->track_order)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "ordered: store %d of the batch tracks its insertion order; use create, fill and load", i);
-  if (n > 0 && !out) return fail(OLAP_ERR_INVALID_ARGUMENT, "out is NULL");
-  return OLAP_OK;
+  if ((rc = check_untracked(n, sources, "use create, fill and load"))) return rc;
+  return check_list(n, out, "out is NULL");
 }
 
 // ToUint32 of the host (js_to_uint32 of olap_device.hpp)
@@ -3734,50 +3698,41 @@ extern "C" int olap_store_compose_multi(int n, const olap_store *const *sources,
   for (int i = 0; i < n; ++i)
     if ((rc = store_alloc(&made[i], cells, sources[i]->dtype, sources[i]->default_kind))) return drop(rc);
   int count = 0;
-  std::vector<char> done(n, 0);
-  for (int i = 0; i < n && cells > 0; ++i) {
-    if (done[i]) continue;
-    const olap_store *s0 = sources[i];
-    std::vector<int> members;
-    for (int j = i; j < n; ++j)
-      if (!done[j] && sources[j]->dtype == s0->dtype && sources[j]->default_kind == s0->default_kind && sources[j]->device == s0->device) {
-        members.push_back(j);
-        done[j] = 1;
-      }
-    PlanRef ref;
-    rc = ref.acquire(compose_key(s0, ndim, my_len, his_len, his_to_mine),
-                     [&](olap_plan **p) { return olap_compose_plan(p, s0->dtype, s0->default_kind, ndim, my_len, his_len, his_to_mine); });
-    if (rc) return drop(rc);
-    olap_plan *p = ref.plan;
-    int cur;
-    if (!begin_run(p, nullptr, &cur)) return drop(foreign_device(p, cur));
-    const bool def_nan = s0->default_kind == OLAP_DEFAULT_NAN;
-    for (size_t first = 0; first < members.size(); first += kMaxBatch) {
-      const unsigned nb = (unsigned)std::min<size_t>(members.size() - first, (size_t)kMaxBatch);
-      const void *in_v[kMaxBatch];
-      const int32_t *in_s[kMaxBatch];
-      void *out_v[kMaxBatch];
-      int32_t *out_s[kMaxBatch];
-      double fill_cells[kMaxBatch];
-      int32_t fill_set[kMaxBatch];
-      bool aligned = true;
-      for (unsigned k = 0; k < nb; ++k) {
-        const int at = members[first + k];
-        in_v[k] = sources[at]->values;
-        in_s[k] = mask_needed(sources[at]);
-        out_v[k] = made[at]->values;
-        out_s[k] = made[at]->status;
-        fill_cells[k] = 0.0, fill_set[k] = 0;
-        if (fill && has_fill && has_fill[at]) fill_cell(s0->dtype, def_nan, fill[at], &fill_cells[k], &fill_set[k]);
-        aligned = aligned && all_aligned16(in_v[k], in_s[k], out_v[k], out_s[k]);
-      }
-      Remap r = p->remap;
-      const int vec = remap_for_launch(r, p->vec, aligned);
-      const hipError_t e = launch_compose(p->dtype, in_s[0] != nullptr, vec, in_v, in_s, out_v, out_s, fill_cells, fill_set, nb, r, nullptr);
-      if (e != hipSuccess) return drop(hip_fail(e, p->kernel_name.c_str()));
-      ++count;
-    }
-  }
+  rc = for_each_group(
+      cells > 0 ? n : 0, [&](int i, int j) { return same_cells(sources[j], sources[i]) && sources[j]->device == sources[i]->device; },
+      [&](const std::vector<int> &members) {
+        const olap_store *s0 = sources[members[0]];
+        PlanRef ref;
+        const int rc = ref.acquire(compose_key(s0, ndim, my_len, his_len, his_to_mine),
+                                   [&](olap_plan **p) { return olap_compose_plan(p, s0->dtype, s0->default_kind, ndim, my_len, his_len, his_to_mine); });
+        if (rc) return rc;
+        olap_plan *p = ref.plan;
+        int cur;
+        if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
+        const bool def_nan = s0->default_kind == OLAP_DEFAULT_NAN;
+        for (size_t first = 0; first < members.size(); first += kMaxBatch) {
+          const unsigned nb = (unsigned)std::min<size_t>(members.size() - first, (size_t)kMaxBatch);
+          const void *in_v[kMaxBatch];
+          const int32_t *in_s[kMaxBatch];
+          void *out_v[kMaxBatch];
+          int32_t *out_s[kMaxBatch];
+          double fill_cells[kMaxBatch];
+          int32_t fill_set[kMaxBatch];
+          const bool aligned = fill_chunk((int)nb, in_v, in_s, out_v, out_s, [&](int k) {
+            const int at = members[first + k];
+            fill_cells[k] = 0.0, fill_set[k] = 0;
+            if (fill && has_fill && has_fill[at]) fill_cell(s0->dtype, def_nan, fill[at], &fill_cells[k], &fill_set[k]);
+            return PairBuffers{sources[at]->values, mask_needed(sources[at]), made[at]->values, made[at]->status};
+          });
+          Remap r = p->remap;
+          const int vec = remap_for_launch(r, p->vec, aligned);
+          const hipError_t e = launch_compose(p->dtype, in_s[0] != nullptr, vec, in_v, in_s, out_v, out_s, fill_cells, fill_set, nb, r, nullptr);
+          if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+          ++count;
+        }
+        return rc;
+      });
+  if (rc) return drop(rc);
   for (int i = 0; i < n; ++i) out[i] = made[i];
   if (launches) *launches = count;
   return OLAP_OK;

@@ -89,6 +89,65 @@ OLAP_INTERNAL int store_alloc(olap_store **out, uint64_t size, int dtype, int de
 OLAP_INTERNAL int ensure_status(const olap_store *s);
 OLAP_INTERNAL void drop_lazy_status(olap_store *s);
 
+// ---- lists of stores: what the entry points over several stores share (olap_capi.hip, olap_blocks.hip) -------------
+// The refusals, each written once; an entry point composes them in the order it reports them, with its own wording
+// (`what`, `advice`) where entry points differ.
+OLAP_INTERNAL int check_list(int n, bool there, const char *what);  // n < 0, or a list that is not `there`
+OLAP_INTERNAL int check_entry(const olap_store *s, int i);          // entry i of a list is NULL
+OLAP_INTERNAL int check_entries(int n, const olap_store *const *stores);
+OLAP_INTERNAL int check_untracked(int n, const olap_store *const *stores, const char *advice);  // no member tracks its order
+// every member holds `cells` cells (`what`: instead of the message that names the two counts)
+OLAP_INTERNAL int check_cells(int n, const olap_store *const *stores, uint64_t cells, const char *what = nullptr);
+
+inline bool same_cells(const olap_store *a, const olap_store *b) { return a->dtype == b->dtype && a->default_kind == b->default_kind; }
+
+// Partitions 0..n-1 (nothing for n <= 0) by same(i, j), i the group's first member.  Groups come in the order of their
+// first member, members ascending: launch counts and "the first error wins" follow from this.  fn(members) -> rc; the
+// first non-zero rc ends the walk and is returned.
+template <typename Same, typename Fn>
+int for_each_group(int n, Same same, Fn fn) {
+  if (n <= 0) return 0;
+  std::vector<char> done(n, 0);
+  std::vector<int> members;
+  for (int i = 0; i < n; ++i) {
+    if (done[i]) continue;
+    members.clear();
+    for (int j = i; j < n; ++j)
+      if (!done[j] && same(i, j)) {
+        members.push_back(j);
+        done[j] = 1;
+      }
+    const int rc = fn(members);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// every buffer of a launch starts on a 16-byte boundary (a buffer the launch does not have is passed as nullptr)
+inline bool all_aligned16(const void *in, const void *in_s, const void *out, const void *out_s) {
+  return (((uintptr_t)in | (uintptr_t)in_s | (uintptr_t)out | (uintptr_t)out_s) & 15u) == 0;
+}
+
+// Fills the pointer slots of one chunk of nb <= kMaxBatch pairs as a kernel takes them (st_out == nullptr: it takes no
+// result masks) from pair(k), the buffers of the chunk's k-th member.  Returns all_aligned16 of the whole chunk.
+struct PairBuffers {
+  const void *in;
+  const int32_t *st_in;
+  void *out;
+  int32_t *st_out;
+};
+template <typename In, typename Out, typename Pair>
+bool fill_chunk(int nb, const In **in, const int32_t **st_in, Out **out, int32_t **st_out, Pair pair) {
+  bool aligned = true;
+  for (int k = 0; k < nb; ++k) {
+    const PairBuffers p = pair(k);
+    in[k] = (const In *)p.in, st_in[k] = p.st_in, out[k] = (Out *)p.out;
+    if (st_out) st_out[k] = p.st_out;
+    aligned = aligned && all_aligned16(p.in, p.st_in, p.out, p.st_out);
+  }
+  return aligned;
+}
+
 // ---- reorder of 4-byte cells as a two-axis LDS transpose (olap_transpose.hip) ---------------------
 constexpr int kTransposeMaxAxis = 4;    // dimensions merged into the X (source-contiguous) or Y (destination-contiguous) axis
 constexpr int kTransposeMaxBatch = 12;  // remaining dimensions: one coordinate per workgroup

@@ -41,11 +41,19 @@ def _levels(lens, levels):
     return lv, ax, n, keep, arr
 
 
+def _handles(stores):  # a None entry stays NULL: the C ABI refuses it by its index
+    return (C.c_void_p * max(len(stores), 1))(*[s._h.value if s is not None else None for s in stores])
+
+
+def _new_stores(n):  # (the array a call writes n new handles into, the int it writes its launch count into)
+    return (C.c_void_p * max(n, 1))(), C.c_int(-1)
+
+
 def _formula(code, consts, inputs):
     """(code, n_code, consts, n_consts, n_inputs, input table, keepalive) of a formula over stores"""
     c = np.ascontiguousarray(code, dtype=np.int32).reshape(-1)
     k = np.ascontiguousarray(consts if len(consts) else [0.0], dtype=np.float64).reshape(-1)
-    table = (C.c_void_p * max(len(inputs), 1))(*[s._h.value if s is not None else None for s in inputs])
+    table = _handles(inputs)
     return (c.ctypes.data_as(capi._pi32), len(c), k.ctypes.data_as(capi._pdbl), len(consts), len(inputs), table, (c, k))
 
 
@@ -88,7 +96,7 @@ def totals_report(inputs, lens, methods, outputs):
     if len(flat) != len(inputs) * len(lv):
         raise ValueError("totals_report: one rule per input and dimension")
     m = (C.c_int * max(len(flat), 1))(*flat)
-    table = (C.c_void_p * max(len(inputs), 1))(*[s._h.value if s is not None else None for s in inputs])
+    table = _handles(inputs)
     stored, n_code, n_consts, n_in, code, consts, picks = [], [], [], [], [], [], []
     for out in outputs:
         if isinstance(out, (int, np.integer)):
@@ -274,12 +282,7 @@ class Plan:
         """The same plan over several buffer pairs in one call (one launch where the plan allows it): lists of device
         addresses; in_status / out_status may be None (no masks) or lists with 0 / None entries."""
         n = len(in_values)
-
-        def ptrs(xs):
-            if xs is None:
-                return None
-            return (C.c_void_p * n)(*[x or None for x in xs])
-
+        ptrs = lambda xs: None if xs is None else (C.c_void_p * n)(*[x or None for x in xs])
         check(capi.lib().olap_plan_run_batch(self._h, n, ptrs(in_values), ptrs(in_status), ptrs(out_values), ptrs(out_status),
                                              stream or None))
 
@@ -287,12 +290,7 @@ class Plan:
         """A drillUp plan over several buffer pairs with a rule each (names or codes): one mixed-rule launch where the
         plan allows it (olap_plan_run_batch_rules)."""
         n = len(in_values)
-
-        def ptrs(xs):
-            if xs is None:
-                return None
-            return (C.c_void_p * n)(*[x or None for x in xs])
-
+        ptrs = lambda xs: None if xs is None else (C.c_void_p * n)(*[x or None for x in xs])
         codes = (C.c_int * n)(*[m if isinstance(m, int) else _method_code(m) for m in methods])
         check(capi.lib().olap_plan_run_batch_rules(self._h, n, codes, ptrs(in_values), ptrs(in_status), ptrs(out_values), ptrs(out_status),
                                                    stream or None))
@@ -484,11 +482,10 @@ class HipStore:
         ol, nl = _u32(old_len), _u32(new_len)
         keep, arr = _tables(maps, np.uint32, C.c_uint32)
         n = len(stores)
-        hs = (C.c_void_p * n)(*[s._h for s in stores])
-        outs = (C.c_void_p * n)()
-        check(capi.lib().olap_store_drillup_batch(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
+        outs, _ = _new_stores(n)
+        check(capi.lib().olap_store_drillup_batch(n, _handles(stores), outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
                                                   _method_code(method)))
-        return [HipStore(0, _handle=C.c_void_p(outs[i])) for i in range(n)]
+        return HipStore._multi_result(n, outs)
 
     @staticmethod
     def drill_up_multi(stores, methods, old_len, new_len, maps):
@@ -497,11 +494,10 @@ class HipStore:
         ol, nl = _u32(old_len), _u32(new_len)
         keep, arr = _tables(maps, np.uint32, C.c_uint32)
         n = len(stores)
-        hs = (C.c_void_p * n)(*[s._h for s in stores])
-        codes = (C.c_int * n)(*[_method_code(m) for m in methods])
-        outs = (C.c_void_p * n)()
-        check(capi.lib().olap_store_drillup_multi(n, hs, codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr))
-        return [HipStore(0, _handle=C.c_void_p(outs[i])) for i in range(n)]
+        codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
+        outs, _ = _new_stores(n)
+        check(capi.lib().olap_store_drillup_multi(n, _handles(stores), codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr))
+        return HipStore._multi_result(n, outs)
 
     def drill_down(self, old_len, new_len, maps, method="sum", distributions=None, integer_measure=False):
         """in-memory.js:336-430.  `integer_measure`: the measure is DECLARED int32 / uint32 but held in float64 cells (what
@@ -544,15 +540,16 @@ class HipStore:
 
     # ---- all stored measures of a cube in one call (olap_store_*_multi): (new stores in order, kernel launches made)
     @staticmethod
-    def _multi_result(n, outs, launches):
-        return [HipStore(0, _handle=C.c_void_p(outs[i])) for i in range(n)], launches.value
+    def _multi_result(n, outs, launches=None):
+        stores = [HipStore(0, _handle=C.c_void_p(outs[i])) for i in range(n)]
+        return stores if launches is None else (stores, launches.value)
 
     @staticmethod
     def dice_multi(stores, old_len, new_len, sel):
         ol, nl = _u32(old_len), _u32(new_len)
         keep, arr = _tables(sel, np.int32, C.c_int32)
         n = len(stores)
-        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        hs, (outs, launches) = _handles(stores), _new_stores(n)
         check(capi.lib().olap_store_dice_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
                                                C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
@@ -563,7 +560,7 @@ class HipStore:
         keep_s, arr_s = _tables(sel, np.int32, C.c_int32)
         keep_m, arr_m = _tables(maps, np.uint32, C.c_uint32)
         n = len(stores)
-        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        hs, (outs, launches) = _handles(stores), _new_stores(n)
         codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
         check(capi.lib().olap_store_dice_drillup_multi(n, hs, codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), ml.ctypes.data_as(capi._pu32),
                                                        nl.ctypes.data_as(capi._pu32), arr_s, arr_m, C.byref(launches)))
@@ -575,7 +572,7 @@ class HipStore:
         ol, nl = _u32(old_len), _u32(new_len)
         keep, arr = _tables(maps, np.uint32, C.c_uint32)
         n = len(stores)
-        hs, outs, launches = (C.c_void_p * max(n, 1))(*[s._h for s in stores]), (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        hs, (outs, launches) = _handles(stores), _new_stores(n)
         flags = integer_measures or [False] * n
         codes = (C.c_int * max(n, 1))(*[_method_code(m) | (capi.DRILLDOWN_INTEGER_MEASURE if f else 0) for m, f in zip(methods, flags)])
         check(capi.lib().olap_store_drilldown_multi(n, hs, codes, outs, len(ol), ol.ctypes.data_as(capi._pu32), nl.ctypes.data_as(capi._pu32), arr,
@@ -639,10 +636,8 @@ class HipStore:
         ml, hl = _u32(my_len), _u32(his_len)
         keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
         n = len(targets)
-        ts = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in targets])
-        ss = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in sources])
         launches = C.c_int(-1)
-        check(capi.lib().olap_store_load_multi(n, ts, ss, len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr,
+        check(capi.lib().olap_store_load_multi(n, _handles(targets), _handles(sources), len(ml), ml.ctypes.data_as(capi._pu32), hl.ctypes.data_as(capi._pu32), arr,
                                                C.byref(launches)))
         return launches.value
 
@@ -652,9 +647,8 @@ class HipStore:
         launches made)"""
         ol, p = _u32(old_len), _i32(perm)
         n = len(stores)
-        hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in stores])
-        outs, launches = (C.c_void_p * max(n, 1))(), C.c_int(-1)
-        check(capi.lib().olap_store_reorder_multi(n, hs, outs, len(ol), ol.ctypes.data_as(capi._pu32), p.ctypes.data_as(capi._pi32),
+        outs, launches = _new_stores(n)
+        check(capi.lib().olap_store_reorder_multi(n, _handles(stores), outs, len(ol), ol.ctypes.data_as(capi._pu32), p.ctypes.data_as(capi._pi32),
                                                   C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
@@ -666,15 +660,14 @@ class HipStore:
         ml, hl = _u32(my_len), _u32(his_len)
         keep, arr = _tables(his_to_mine, np.int32, C.c_int32)
         n = len(sources)
-        hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in sources])
-        outs, launches = (C.c_void_p * max(n, 1))(), C.c_int(-1)
+        outs, launches = _new_stores(n)
         values = has = None
         if fills is not None:
             if len(fills) != n:
                 raise ValueError("compose_many: %d sources, %d fills" % (n, len(fills)))
             values = (C.c_double * max(n, 1))(*[0.0 if f is None else float(f) for f in fills])
             has = (C.c_uint8 * max(n, 1))(*[0 if f is None else 1 for f in fills])
-        check(capi.lib().olap_store_compose_multi(n, hs, values, has, outs, len(ml), ml.ctypes.data_as(capi._pu32),
+        check(capi.lib().olap_store_compose_multi(n, _handles(sources), values, has, outs, len(ml), ml.ctypes.data_as(capi._pu32),
                                                   hl.ctypes.data_as(capi._pu32), arr, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
@@ -691,9 +684,8 @@ def blocks_report(stores, lens, scanned):
     n = len(stores)
     combos = int(np.prod([int(l) for l, f in zip(lv, flags) if f], dtype=np.uint64)) if len(lv) else 1
     kept = int(np.prod([int(l) for l, f in zip(lv, flags) if not f], dtype=np.uint64)) if len(lv) else 1
-    hs = (C.c_void_p * max(n, 1))(*[s._h.value if s is not None else None for s in stores])
     out = np.zeros((n, combos, kept), np.float64)
     launches = C.c_int(-1)
-    check(capi.lib().olap_store_blocks_report(n, hs, len(lv), lv.ctypes.data_as(capi._pu32), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+    check(capi.lib().olap_store_blocks_report(n, _handles(stores), len(lv), lv.ctypes.data_as(capi._pu32), flags.ctypes.data_as(C.POINTER(C.c_uint8)),
                                               out.ctypes.data_as(capi._pdbl), C.byref(launches)))
     return out, launches.value

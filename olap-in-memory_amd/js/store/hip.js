@@ -176,7 +176,7 @@ function pendingGroups(stores, eligible = () => true) {
   const groups = new Map();
   stores.forEach((store, i) => {
     const p = store._pending;
-    if (!p || p.source.isSharded || p.source.orderTracked || !eligible(store)) return;
+    if (!p || !wholeUntracked(p.source) || !eligible(store)) return;
     const group = groups.get(p.sel);
     if (group === undefined) groups.set(p.sel, [i]);
     else if (stores[group[0]]._pending.oldLen === p.oldLen && stores[group[0]]._pending.midLen === p.midLen) group.push(i);
@@ -207,6 +207,58 @@ function loadTables(myDimensions, hisDimensions) {
     return Int32Array.from(dim.getItems(), (item) => (position[item] === undefined ? -1 : position[item]));
   });
 }
+
+/** Whether an addon store is held whole on one device and untracked: what the calls over several measures take. */
+const wholeUntracked = (native) => !!native && !native.isSharded && !native.orderTracked;
+/**
+ * The addon store that decides it for a HipStore.  heldStore: after materializeMany — a selection that is still pending
+ * (alone in its group, or over a sharded source) gives null, like cells still on the host, and the measure goes one by
+ * one.  sourceStore: before it — a pending selection answers for its source.
+ */
+const heldStore = (store) => (store._pending ? null : store._nativeStore);
+const sourceStore = (store) => (store._pending ? store._pending.source : store._nativeStore);
+
+/**
+ * The last step of drillUpMany, drillDownMany and reorderMany: the measures without a result in `out` that are held whole
+ * and untracked (and `eligible(i)`) go to the device together when there are two or more — `call(addon stores)` gives the
+ * new addon stores, wrapped back in place — and the rest one by one through `single(store, i)`.
+ */
+function togetherThenSingly(stores, out, eligible, call, single) {
+  const together = [];
+  stores.forEach((store, i) => {
+    if (!out[i] && wholeUntracked(heldStore(store)) && eligible(i)) together.push(i);
+  });
+  if (together.length >= 2) {
+    const natives = call(together.map((i) => stores[i]._nativeStore), together);
+    together.forEach((i, j) => {
+      out[i] = stores[i]._wrap(natives[j]);
+    });
+  }
+  stores.forEach((store, i) => {
+    if (!out[i]) out[i] = single(store, i);
+  });
+  return out;
+}
+
+/** old item -> new item per dimension of a roll-up, and how many dimensions such maps actually roll up */
+const drillUpMaps = (oldDimensions, newDimensions) => newDimensions.map((dim, i) => asU32(oldDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
+const rolledUp = (maps, newDimensions) => maps.filter((map, i) => map.length !== newDimensions[i].numItems || map.some((g, k) => g !== k)).length;
+
+/** A roll-up over the dimensions the cube sees (`at`: visibleDims) on those of the pending selection `p`: the ones the cube has dropped keep their single item */
+function rollUpOfPending(p, at, newDimensions, maps) {
+  const newLen = Uint32Array.from(p.midLen, () => 1);
+  const allMaps = Array.from(p.midLen, () => Uint32Array.of(0));
+  at.forEach((d, v) => {
+    newLen[d] = newDimensions[v].numItems;
+    allMaps[d] = maps[v];
+  });
+  return { newLen, allMaps };
+}
+
+/** the code Store.drillDown takes: sum or a copy, and the remainder rule of the DECLARED type (in-memory.js:343), whatever the cells are (OLAP_DRILLDOWN_INTEGER_MEASURE) */
+const drillDownCode = (store, method) => (method === undefined || method === 'sum' ? 0 : 4) | (store._type === 'int32' || store._type === 'uint32' ? 0x100 : 0);
+
+const reorderPerm = (oldDimensions, newDimensions) => Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
 
 class HipStore {
   /**
@@ -427,23 +479,17 @@ class HipStore {
   /** in-memory.js:265-334 */
   drillUp(oldDimensions, newDimensions, method = 'sum') {
     const code = backend.load().methodFromName(method); // throws 'Unsupported aggregation method: <m>'
-    const maps = newDimensions.map((dim, i) => asU32(oldDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
+    const maps = drillUpMaps(oldDimensions, newDimensions);
     const at = this._pending && !this._pending.source.isSharded ? visibleDims(this._pending, lengthsOf(oldDimensions)) : null;
     if (at) {
-      const rolled = maps.filter((map, i) => map.length !== newDimensions[i].numItems || map.some((g, k) => g !== k)).length;
+      const rolled = rolledUp(maps, newDimensions);
       const p = this._pending;
       // every group has exactly its own single member (e.g. the roll-up to 'all' of a dimension that
       // a slice diced down to one item): the cells do not change, the selection stays pending and
       // keeps composing — slice(...).dice(...).drillUp(...) becomes ONE launch over the source cube
       if (rolled === 0) return new HipStore(this._size, this._type, this._defaultValue, { source: p.source, oldLen: p.oldLen, midLen: p.midLen, sel: p.sel });
       if (rolled <= 1) {
-        // dimensions the cube has dropped keep their single item
-        const newLen = Uint32Array.from(p.midLen, () => 1);
-        const allMaps = Array.from(p.midLen, () => Uint32Array.of(0));
-        at.forEach((d, v) => {
-          newLen[d] = newDimensions[v].numItems;
-          allMaps[d] = maps[v];
-        });
+        const { newLen, allMaps } = rollUpOfPending(p, at, newDimensions, maps);
         return this._wrap(p.source.diceDrillUp(p.oldLen, p.midLen, newLen, p.sel, allMaps, code));
       }
     }
@@ -467,17 +513,11 @@ class HipStore {
     const fusable = pendingGroups(stores, (store) => visibleDims(store._pending, lengths) !== null);
     if (fusable.length > 0) {
       const addon = backend.load();
-      const maps = newDimensions.map((dim, i) => asU32(oldDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
-      const rolled = maps.filter((map, i) => map.length !== newDimensions[i].numItems || map.some((g, k) => g !== k)).length;
+      const maps = drillUpMaps(oldDimensions, newDimensions);
+      const rolled = rolledUp(maps, newDimensions);
       for (const group of rolled === 1 ? fusable : []) {
         const p = stores[group[0]]._pending;
-        const at = visibleDims(p, lengths);
-        const newLen = Uint32Array.from(p.midLen, () => 1); // dimensions the cube has dropped keep their single item
-        const allMaps = Array.from(p.midLen, () => Uint32Array.of(0));
-        at.forEach((d, v) => {
-          newLen[d] = newDimensions[v].numItems;
-          allMaps[d] = maps[v];
-        });
+        const { newLen, allMaps } = rollUpOfPending(p, visibleDims(p, lengths), newDimensions, maps);
         const codes = Int32Array.from(group, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
         const launchesOut = new Int32Array(1);
         const natives = addon.diceDrillUpMulti(group.map((i) => stores[i]._pending.source), codes, p.oldLen, p.midLen, newLen, p.sel, allMaps, launchesOut);
@@ -499,33 +539,18 @@ class HipStore {
       launches += HipStore.lastBatchLaunches;
     }
     HipStore.lastBatchLaunches = launches;
-    const together = [];
-    stores.forEach((store, i) => {
-      const native = store._pending || out[i] ? null : store._nativeStore;
-      if (native && !native.isSharded && !native.orderTracked) together.push(i);
-    });
-    if (together.length >= 2) {
+    return togetherThenSingly(stores, out, () => true, (natives, together) => {
       const addon = backend.load();
       const codes = Int32Array.from(together, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
-      const maps = newDimensions.map((dim, i) => asU32(oldDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
-      const natives = addon.drillUpMulti(together.map((i) => stores[i]._nativeStore), codes, lengthsOf(oldDimensions), lengthsOf(newDimensions), maps);
-      together.forEach((i, j) => {
-        out[i] = stores[i]._wrap(natives[j]);
-      });
-    }
-    stores.forEach((store, i) => {
-      if (!out[i]) out[i] = store.drillUp(oldDimensions, newDimensions, methods[i]);
-    });
-    return out;
+      return addon.drillUpMulti(natives, codes, lengthsOf(oldDimensions), lengthsOf(newDimensions), drillUpMaps(oldDimensions, newDimensions));
+    }, (store, i) => store.drillUp(oldDimensions, newDimensions, methods[i]));
   }
 
   /** in-memory.js:336-430 — any method other than 'sum' copies the parent value (:421-423) */
   drillDown(oldDimensions, newDimensions, method = 'sum', distributions = null) {
     const maps = oldDimensions.map((dim, i) => asU32(newDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
     const weights = distributions ? toFloat64(distributions, Number.NaN) : null;
-    // the remainder rule goes by the DECLARED type (:343), whatever the cells are (OLAP_DRILLDOWN_INTEGER_MEASURE)
-    const integerMeasure = this._type === 'int32' || this._type === 'uint32' ? 0x100 : 0;
-    return this._wrap(onShards(this._native, 'drillDown', [lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, (method === 'sum' ? 0 : 4) | integerMeasure, weights]));
+    return this._wrap(onShards(this._native, 'drillDown', [lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, drillDownCode(this, method), weights]));
   }
 
   /**
@@ -537,30 +562,15 @@ class HipStore {
    */
   static drillDownMany(stores, oldDimensions, newDimensions, methods, distributionsPerStore = []) {
     const out = new Array(stores.length);
-    HipStore.materializeMany(stores);
-    let launches = HipStore.lastBatchLaunches;
-    const together = [];
-    stores.forEach((store, i) => {
-      const native = store._pending ? null : store._nativeStore;
-      if (native && !native.isSharded && !native.orderTracked && !distributionsPerStore[i]) together.push(i);
-    });
-    if (together.length >= 2) {
+    HipStore.materializeMany(stores); // (leaves its launches in HipStore.lastBatchLaunches)
+    return togetherThenSingly(stores, out, (i) => !distributionsPerStore[i], (natives, together) => {
       const maps = oldDimensions.map((dim, i) => asU32(newDimensions[i].getGroupIndexFromRootIndexMap(dim.rootAttribute)));
-      // the codes drillDown() hands over: sum or a copy, and the remainder rule of the DECLARED type
-      const codes = Int32Array.from(together, (i) => (methods[i] === undefined || methods[i] === 'sum' ? 0 : 4) |
-        (stores[i]._type === 'int32' || stores[i]._type === 'uint32' ? 0x100 : 0));
+      const codes = Int32Array.from(together, (i) => drillDownCode(stores[i], methods[i]));
       const launchesOut = new Int32Array(1);
-      const natives = backend.load().drillDownMulti(together.map((i) => stores[i]._nativeStore), codes, lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, launchesOut);
-      together.forEach((i, j) => {
-        out[i] = stores[i]._wrap(natives[j]);
-      });
-      launches += launchesOut[0];
-    }
-    HipStore.lastBatchLaunches = launches;
-    stores.forEach((store, i) => {
-      if (!out[i]) out[i] = store.drillDown(oldDimensions, newDimensions, methods[i], distributionsPerStore[i]);
-    });
-    return out;
+      const made = backend.load().drillDownMulti(natives, codes, lengthsOf(oldDimensions), lengthsOf(newDimensions), maps, launchesOut);
+      HipStore.lastBatchLaunches += launchesOut[0];
+      return made;
+    }, (store, i) => store.drillDown(oldDimensions, newDimensions, methods[i], distributionsPerStore[i]));
   }
 
   /** in-memory.js:213-263 — the new dimensions' item ORDER decides where cells land */
@@ -830,8 +840,7 @@ class HipStore {
 
   /** in-memory.js:178-211 */
   reorder(oldDimensions, newDimensions) {
-    const perm = Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
-    return this._wrap(onShards(this._native, 'reorder', [lengthsOf(oldDimensions), perm]));
+    return this._wrap(onShards(this._native, 'reorder', [lengthsOf(oldDimensions), reorderPerm(oldDimensions, newDimensions)]));
   }
 
   /**
@@ -846,26 +855,14 @@ class HipStore {
     const out = new Array(stores.length);
     HipStore.materializeMany(stores);
     HipStore.lastReorderLaunches = null;
-    const together = [];
-    stores.forEach((store, i) => {
-      const native = store._pending ? null : store._nativeStore;
-      if (native && !native.isSharded && !native.orderTracked) together.push(i);
-    });
     const addon = backend.load();
     // (an addon built before reorderMulti existed keeps the single-store calls)
-    if (together.length >= 2 && typeof addon.reorderMulti === 'function') {
-      const perm = Int32Array.from(newDimensions, (dim) => oldDimensions.indexOf(dim));
+    return togetherThenSingly(stores, out, () => typeof addon.reorderMulti === 'function', (natives) => {
       const launchesOut = new Int32Array(1);
-      const natives = addon.reorderMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(oldDimensions), perm, launchesOut);
-      together.forEach((i, j) => {
-        out[i] = stores[i]._wrap(natives[j]);
-      });
+      const made = addon.reorderMulti(natives, lengthsOf(oldDimensions), reorderPerm(oldDimensions, newDimensions), launchesOut);
       HipStore.lastReorderLaunches = launchesOut[0];
-    }
-    stores.forEach((store, i) => {
-      if (!out[i]) out[i] = store.reorder(oldDimensions, newDimensions);
-    });
-    return out;
+      return made;
+    }, (store) => store.reorder(oldDimensions, newDimensions));
   }
 
   /** in-memory.js:139-176 — mutates this store */
@@ -916,8 +913,7 @@ class HipStore {
     const distinct = new Set(targets.concat(sources)).size === targets.length + sources.length;
     const together = [];
     targets.forEach((target, i) => {
-      const native = target._native;
-      if (distinct && !native.isSharded && !native.orderTracked) together.push(i);
+      if (distinct && wholeUntracked(target._native)) together.push(i);
     });
     if (together.length >= 1) {
       const launchesOut = new Int32Array(1);
@@ -941,8 +937,7 @@ class HipStore {
   /** Whether `store` may be a source of composeMany: held whole on one device, untracked, cells of its declared type. */
   static composable(store) {
     if (!(store instanceof HipStore) || store._cells !== cellTypeOf(store._type)) return false;
-    const native = store._pending ? store._pending.source : store._native;
-    return !native.isSharded && !native.orderTracked;
+    return wholeUntracked(sourceStore(store) || store._native); // (cells still on the host are uploaded)
   }
 
   /**
@@ -984,14 +979,11 @@ class HipStore {
   static blocksMany(stores, dimensions, scannedFlags) {
     const addon = backend.load();
     if (typeof addon.blocksReport !== 'function') return null;
-    for (const store of stores) {
-      const native = store._pending ? store._pending.source : store._nativeStore;
-      if (native && (native.isSharded || native.orderTracked)) return null;
-    }
+    if (stores.some((store) => sourceStore(store) && !wholeUntracked(sourceStore(store)))) return null;
     HipStore.materializeMany(stores);
     let launches = HipStore.lastBatchLaunches;
     const natives = stores.map((store) => store._native);
-    if (natives.some((native) => native.isSharded || native.orderTracked)) return null;
+    if (!natives.every(wholeUntracked)) return null;
     const lens = lengthsOf(dimensions);
     const size = lens.reduce((n, l) => n * l, 1);
     if (stores.length * size * 8 > HipStore.blocksMaxBytes) return null;

@@ -990,56 +990,13 @@ static napi_value StoreCopySelectFormula(napi_env env, napi_callback_info info) 
   return nullptr;
 }
 
-// drillUpMulti(stores: Store[], methods: Int32Array, oldLen, newLen, maps) -> Store[]
-// Every stored measure of a cube with its own rule for the rolled-up dimension (olap_store_drillup_multi): one
-// mixed-rule launch where the roll-up allows it, one launch per rule otherwise.
-static napi_value DrillUpMulti(napi_env env, napi_callback_info info) {
-  size_t argc = 5;
-  napi_value argv[5];
-  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  OpArgs a;
-  bool is_arr = false;
-  if (argc >= 1) napi_is_array(env, argv[0], &is_arr);
-  napi_typedarray_type mt;
-  size_t n_methods = 0;
-  void *mdata = nullptr;
-  if (argc < 5 || !is_arr || napi_get_typedarray_info(env, argv[1], &mt, &n_methods, &mdata, nullptr, nullptr) != napi_ok || mt != napi_int32_array ||
-      !a.decode(env, argv[2], argv[3], argv[4]))
-    return bad_args(env, "drillUpMulti(stores: Store[], methods: Int32Array, oldLen: Uint32Array, newLen: Uint32Array, maps: Uint32Array[])");
-  uint32_t n = 0;
-  napi_get_array_length(env, argv[0], &n);
-  if (n_methods != n) return bad_args(env, "drillUpMulti: one method per store");
-  std::vector<const olap_store *> stores(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    napi_value e;
-    NAPI_OK(napi_get_element(env, argv[0], i, &e));
-    stores[i] = unwrap(env, e);
-    if (!stores[i]) return nullptr;
-  }
-  std::vector<olap_store *> outs(n, nullptr);
-  static const int none = 0;
-  int rc = olap_store_drillup_multi((int)n, stores.data(), n ? (const int *)mdata : &none, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
-                                    a.ptrs.data());
-  if (rc) return throw_olap(env, rc);
-  napi_value arr;
-  NAPI_OK(napi_create_array_with_length(env, n, &arr));
-  for (uint32_t i = 0; i < n; ++i) {
-    napi_value w = wrap_new_store(env, outs[i]);
-    if (!w) {
-      for (uint32_t j = i + 1; j < n; ++j) olap_store_destroy(outs[j]);
-      return nullptr;
-    }
-    napi_set_element(env, arr, i, w);
-  }
-  return arr;
-}
-
 // ---- diceMulti / diceDrillUpMulti / drillDownMulti: ALL stored measures of a cube behind one call (olap_store_*_multi)
 namespace {
 // the Store[] and (where the operation has rules) the Int32Array with a rule per store
 struct MultiArgs {
   std::vector<const olap_store *> stores;
   const int *methods = nullptr;
+  bool miscounted = false;  // the rules are an Int32Array, but not one per store
   // false with an exception pending, or — *usage_error — arguments of the wrong shape
   bool decode(napi_env env, napi_value list, const napi_value *rules, bool *usage_error) {
     *usage_error = true;
@@ -1053,8 +1010,9 @@ struct MultiArgs {
       void *mdata = nullptr;
       bool is_ta = false;
       if (napi_is_typedarray(env, *rules, &is_ta) != napi_ok || !is_ta || napi_get_typedarray_info(env, *rules, &mt, &n_methods, &mdata, nullptr, nullptr) != napi_ok ||
-          mt != napi_int32_array || n_methods != n)
+          mt != napi_int32_array)
         return false;
+      if ((miscounted = n_methods != n)) return false;
       static const int none = 0;
       methods = n ? (const int *)mdata : &none;
     }
@@ -1086,6 +1044,36 @@ static napi_value wrap_new_stores(napi_env env, std::vector<olap_store *> &outs)
   return arr;
 }
 
+// The common end of the *Multi calls: the C ABI's refusal thrown, else the launch count into the optional Int32Array
+// at argv[launches_at].  false: an exception is pending.
+static bool multi_done(napi_env env, int rc, size_t argc, const napi_value *argv, size_t launches_at, int launches) {
+  if (rc) {
+    throw_olap(env, rc);
+    return false;
+  }
+  if (argc > launches_at) set_path(env, argv[launches_at], launches);
+  return true;
+}
+
+// drillUpMulti(stores: Store[], methods: Int32Array, oldLen, newLen, maps) -> Store[]
+// Every stored measure of a cube with its own rule for the rolled-up dimension (olap_store_drillup_multi): one
+// mixed-rule launch where the roll-up allows it, one launch per rule otherwise.
+static napi_value DrillUpMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "drillUpMulti(stores: Store[], methods: Int32Array, oldLen: Uint32Array, newLen: Uint32Array, maps: Uint32Array[])";
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  OpArgs a;
+  MultiArgs m;
+  bool bad = true;
+  if (argc < 5 || !a.decode(env, argv[2], argv[3], argv[4])) return bad_args(env, usage);
+  if (!m.decode(env, argv[0], &argv[1], &bad)) return m.miscounted ? bad_args(env, "drillUpMulti: one method per store") : bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  int rc = olap_store_drillup_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
+                                    a.ptrs.data());
+  return multi_done(env, rc, 0, nullptr, 0, 0) ? wrap_new_stores(env, outs) : nullptr;
+}
+
 // diceMulti(stores: Store[], oldLen, newLen, sel: Int32Array[], launchesOut?: Int32Array) -> Store[]
 static napi_value DiceMulti(napi_env env, napi_callback_info info) {
   const char *usage = "diceMulti(stores: Store[], oldLen: Uint32Array, newLen: Uint32Array, sel: Int32Array[], launchesOut?: Int32Array)";
@@ -1101,9 +1089,7 @@ static napi_value DiceMulti(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_dice_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
                                  (const int32_t *const *)a.ptrs.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 4) set_path(env, argv[4], launches);
-  return wrap_new_stores(env, outs);
+  return multi_done(env, rc, argc, argv, 4, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
 // reorderMulti(stores: Store[], oldLen, perm: Int32Array, launchesOut?: Int32Array) -> Store[]
@@ -1120,9 +1106,7 @@ static napi_value ReorderMulti(napi_env env, napi_callback_info info) {
   std::vector<olap_store *> outs(m.stores.size(), nullptr);
   int launches = 0;
   int rc = olap_store_reorder_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)len.size(), len.data(), (const int32_t *)perm.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 3) set_path(env, argv[3], launches);
-  return wrap_new_stores(env, outs);
+  return multi_done(env, rc, argc, argv, 3, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
 // loadMulti(targets: Store[], sources: Store[], myLen, hisLen, hisToMine: Int32Array[], launchesOut?: Int32Array): targets[i].load(sources[i])
@@ -1141,8 +1125,7 @@ static napi_value LoadMulti(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_load_multi((int)t.stores.size(), (olap_store *const *)t.stores.data(), o.stores.data(), (int)a.a_len.size(), a.a_len.data(),
                                  a.b_len.data(), (const int32_t *const *)a.ptrs.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 5) set_path(env, argv[5], launches);
+  multi_done(env, rc, argc, argv, 5, launches);
   return nullptr;
 }
 
@@ -1173,9 +1156,7 @@ static napi_value ComposeMulti(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_compose_multi((int)m.stores.size(), m.stores.data(), (const double *)values, (const uint8_t *)flags, outs.data(),
                                     (int)a.a_len.size(), a.a_len.data(), a.b_len.data(), (const int32_t *const *)a.ptrs.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 6) set_path(env, argv[6], launches);
-  return wrap_new_stores(env, outs);
+  return multi_done(env, rc, argc, argv, 6, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
 // blocksReport(stores: Store[], lens: Uint32Array, scanned: Uint8Array, launchesOut?: Int32Array)
@@ -1213,9 +1194,7 @@ static napi_value BlocksReport(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_blocks_report((int)m.stores.size(), m.stores.data(), (int)lens.size(), lens.empty() ? &none : lens.data(),
                                     flags ? (const uint8_t *)flags : &no_flag, data ? (double *)data : &no_cell, &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 3) set_path(env, argv[3], launches);
-  return ta;
+  return multi_done(env, rc, argc, argv, 3, launches) ? ta : nullptr;
 }
 
 // diceDrillUpMulti(stores: Store[], methods: Int32Array, oldLen, midLen, newLen, sel: Int32Array[], maps: Uint32Array[], launchesOut?) -> Store[]
@@ -1239,9 +1218,7 @@ static napi_value DiceDrillUpMulti(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_dice_drillup_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
                                          new_len.data(), (const int32_t *const *)a.ptrs.data(), map_ptrs.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 7) set_path(env, argv[7], launches);
-  return wrap_new_stores(env, outs);
+  return multi_done(env, rc, argc, argv, 7, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
 // drillDownMulti(stores: Store[], methods: Int32Array, oldLen, newLen, maps: Uint32Array[], launchesOut?) -> Store[]
@@ -1260,9 +1237,7 @@ static napi_value DrillDownMulti(napi_env env, napi_callback_info info) {
   int launches = 0;
   int rc = olap_store_drilldown_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)a.a_len.size(), a.a_len.data(), a.b_len.data(),
                                       a.ptrs.data(), &launches);
-  if (rc) return throw_olap(env, rc);
-  if (argc > 5) set_path(env, argv[5], launches);
-  return wrap_new_stores(env, outs);
+  return multi_done(env, rc, argc, argv, 5, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
 // ---- ShardedStore: a measure split along dimension 0 over the devices of setDevices() -----------

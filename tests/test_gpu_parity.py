@@ -1714,6 +1714,48 @@ def test_drillup_multi_mixed_stores_and_plan_level():
             assert np.array_equal(sts[i][off:off + n_out].cpu().numpy(), want[i].get_status()), (off, rules[i])
 
 
+def _small_store_and_oracle(rng, type_name, default, cells):
+    """small positive integers (every rule's result is exact in every cell type), about a third of the cells unset"""
+    dense = np.where(rng.random(cells) < 0.3, default, rng.integers(1, 7, size=cells).astype(np.float64))
+    g = pkg.HipStore(cells, type_name, default)
+    g.set_data_f64(dense)
+    o = OracleStore(cells, type_name, default)
+    o.set_data(dense)
+    return g, o
+
+
+def _equals_oracle(store, o):
+    ev, es = o.typed()
+    return store.type == o.type and np.array_equal(store.get_status(), es) and same_typed(store.get_data(), ev)
+
+
+def test_drillup_batch_and_multi_interleaved_groups_and_a_second_chunk():
+    """[4, 6] rolled to [4, 2].  A list whose (cell type, default) groups — and, for olap_store_drillup_multi, rules — are
+    interleaved: every result sits at its store's index and equals the oracle's.  Nine measures of one group make a
+    second chunk: the ninth is right too."""
+    lens, new = [4, 6], [4, 2]
+    maps = [np.arange(4, dtype=np.uint32), np.array([0, 0, 0, 1, 1, 1], np.uint32)]
+    kinds = [("float32", 0.0), ("float64", float("nan")), ("float32", 0.0), ("int32", 0.0), ("float64", float("nan")), ("float32", float("nan")),
+             ("float32", 0.0)]
+    rng = np.random.default_rng(91)
+    pairs = [_small_store_and_oracle(rng, t, d, 24) for t, d in kinds]
+    outs = pkg.HipStore.drill_up_batch([g for g, _ in pairs], lens, new, maps, "sum")
+    for i, ((_, o), out) in enumerate(zip(pairs, outs)):
+        assert _equals_oracle(out, o.drill_up(lens, new, maps, "sum")), ("batch", i)
+    rules = ["sum", "highest", "sum", "sum", "highest", "sum", "highest"]
+    outs = pkg.HipStore.drill_up_multi([g for g, _ in pairs], rules, lens, new, maps)
+    for i, ((_, o), rule, out) in enumerate(zip(pairs, rules, outs)):
+        assert _equals_oracle(out, o.drill_up(lens, new, maps, rule)), ("multi", i, rule)
+    nine = [_small_store_and_oracle(rng, "float32", 0.0, 24) for _ in range(9)]
+    outs = pkg.HipStore.drill_up_batch([g for g, _ in nine], lens, new, maps, "sum")
+    for i, ((_, o), out) in enumerate(zip(nine, outs)):
+        assert _equals_oracle(out, o.drill_up(lens, new, maps, "sum")), ("batch of nine", i)
+    for rules in (["highest"] * 9, ["sum", "highest", "last"] * 3):  # one rule: rule by rule; several: the mixed-rule path
+        outs = pkg.HipStore.drill_up_multi([g for g, _ in nine], rules, lens, new, maps)
+        for i, ((_, o), rule, out) in enumerate(zip(nine, rules, outs)):
+            assert _equals_oracle(out, o.drill_up(lens, new, maps, rule)), ("multi of nine", i, rule)
+
+
 @pytest.mark.parametrize("method", ["sum", "average", "highest", "first", "last", "product"])
 @pytest.mark.parametrize("type_name,default", [("float32", 0.0), ("float32", float("nan")), ("int32", 0.0), ("uint32", float("nan")), ("float64", 0.0)])
 @pytest.mark.parametrize("lens,axis,kind", [([3000, 132], 0, "all"), ([2, 1500, 256], 1, "all"), ([2600, 200], 0, "halves"), ([3, 900, 516], 1, "interleaved"),

@@ -6,6 +6,7 @@ import pytest
 
 from conftest import load_package
 from golden_util import same_typed
+from oracle.oracle import OracleStore
 
 pytestmark = pytest.mark.gpu
 
@@ -155,3 +156,45 @@ def test_mixed_reorder_group_and_no_stores():
         assert (o.type, o.default_is_nan) == (s.type, s.default_is_nan) and same_store(o, s.reorder(old_len, perm))
     assert pkg.HipStore.reorder_many([], old_len, perm) == ([], 0)
     assert pkg.HipStore.load_many([], [], old_len, old_len, [np.arange(l, dtype=np.int32) for l in old_len]) == 0
+
+
+# four groups of (cell type, default), interleaved in the list
+INTERLEAVED = [("float32", 0.0), ("float64", NAN), ("float32", 0.0), ("int32", 0.0), ("float64", NAN), ("float32", NAN)]
+
+
+def small_dense(rng, n, default, low):
+    return np.where(rng.random(n) < 0.4, default, rng.integers(low, low + 9, size=n).astype(np.float64))
+
+
+def oracle_store(type_name, default, dense):
+    o = OracleStore(len(dense), type_name, default)
+    o.set_data(dense)
+    return o
+
+
+def equals_oracle(store, o):
+    values, status = o.typed()
+    return store.type == o.type and np.array_equal(store.get_status(), status) and same_typed(store.get_data(), values)
+
+
+def test_interleaved_groups_land_at_their_own_index_as_the_oracle_has_them():
+    """load [3, 4] <- [2, 4] and reorder [2, 3, 4] over a list whose groups are interleaved: every result sits at its own
+    index and equals the oracle's; the launches are the number of groups."""
+    rng = np.random.default_rng(4700)
+    my_len, his_len, maps = [3, 4], [2, 4], [np.array([2, 0], np.int32), np.arange(4, dtype=np.int32)]
+    mine = [small_dense(rng, 12, d, 1) for _, d in INTERLEAVED]
+    his = [small_dense(rng, 8, d, 50) for _, d in INTERLEAVED]
+    targets = [store(t, d, v) for (t, d), v in zip(INTERLEAVED, mine)]
+    sources = [store(t, d, v) for (t, d), v in zip(INTERLEAVED, his)]
+    assert pkg.HipStore.load_many(targets, sources, my_len, his_len, maps) == 4
+    for i, (t, d) in enumerate(INTERLEAVED):
+        want = oracle_store(t, d, mine[i])
+        want.load(oracle_store(t, d, his[i]), my_len, his_len, maps)
+        assert equals_oracle(targets[i], want), i
+    old_len, perm = [2, 3, 4], [2, 0, 1]
+    dense = [small_dense(rng, 24, d, 1) for _, d in INTERLEAVED]
+    stores = [store(t, d, v) for (t, d), v in zip(INTERLEAVED, dense)]
+    outs, launches = pkg.HipStore.reorder_many(stores, old_len, perm)
+    assert launches == 4
+    for i, (t, d) in enumerate(INTERLEAVED):
+        assert equals_oracle(outs[i], oracle_store(t, d, dense[i]).reorder(old_len, perm)), i

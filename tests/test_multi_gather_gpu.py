@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import load_package
+from golden_util import same_typed
 from oracle.oracle import OracleStore
 
 pytestmark = pytest.mark.gpu
@@ -284,3 +285,67 @@ def test_plan_batch_off_the_16_byte_grid_falls_back_pair_by_pair():
     plan.run_batch([s.values_ptr for s in shifted], None, [s.values_ptr for s in aligned], None)
     for b, a in zip(batch, aligned):
         assert b.get_data()[1:1 + n_out].tobytes() == a.get_data()[:n_out].tobytes()
+
+
+# ------------------------------------------------------- interleaved groups and a second chunk, against the oracle
+# four groups of (cell type, default), interleaved in the list
+INTERLEAVED = [("float32", 0.0), ("float64", NAN), ("float32", 0.0), ("int32", 0.0), ("float64", NAN), ("float32", NAN)]
+
+
+def small_stores(rng, kinds, size):
+    out = []
+    for dtype, default in kinds:
+        vals = rng.integers(1, 7, size=size).astype(np.float64)
+        vals[rng.random(size) < 0.33] = default
+        s = HipStore(size, dtype, default)
+        s.set_data_f64(vals)
+        out.append(s)
+    return out
+
+
+def equals_oracle(store, o):
+    ev, es = o.typed()
+    return store.type == o.type and np.array_equal(store.get_status(), es) and same_typed(store.get_data(), ev)
+
+
+def test_interleaved_groups_land_at_their_own_index():
+    """Every result of a list whose groups are interleaved sits at its store's index and equals the oracle's; the launches
+    are the number of groups (groups in the order of their first member, members ascending)."""
+    rng = np.random.default_rng(16)
+    # dice [3, 4] -> [2, 4]
+    old, new, sel = [3, 4], [2, 4], [[2, 0], ident(4)]
+    stores = small_stores(rng, INTERLEAVED, 12)
+    got, launches = HipStore.dice_multi(stores, old, new, sel)
+    for i, (s, g) in enumerate(zip(stores, got)):
+        assert equals_oracle(g, oracle_of(s).dice(old, new, sel)), ("dice", i)
+    assert launches == 4
+    # the fused dice -> drillUp [3, 4] -> [2, 4] -> [2, 2] with two rules interleaved as well: float32/0 sum (0, 2),
+    # float64/NaN highest (1, 4), int32/0 sum, float32/NaN sum, float32/0 highest
+    mid, rolled, maps = [2, 4], [2, 2], [ident(2), [0, 0, 1, 1]]
+    kinds = INTERLEAVED + [("float32", 0.0)]
+    rules = ["sum", "highest", "sum", "sum", "highest", "sum", "highest"]
+    stores = small_stores(rng, kinds, 12)
+    got, launches = HipStore.dice_drillup_multi(stores, rules, old, mid, rolled, sel, maps)
+    for i, (s, rule, g) in enumerate(zip(stores, rules, got)):
+        assert equals_oracle(g, oracle_of(s).dice(old, mid, sel).drill_up(mid, rolled, maps, rule)), ("fused", i, rule)
+    assert launches == 5
+    # drillDown [3, 516] -> [5, 516] in the row form (the form that batches), `sum` and a copying rule interleaved
+    k, parents = groups_of([2, 1, 2])
+    old, new, maps = [3, 516], [k, 516], [parents, ident(516)]
+    rules = ["sum", "average", "sum", "sum", "average", "sum", "average"]
+    for (dtype, default), rule in zip(kinds, rules):
+        assert "drilldown_rows" in Plan.drilldown(dtype, default, rule, old, new, maps).kernel_name
+    stores = small_stores(rng, kinds, 3 * 516)
+    got, launches = HipStore.drill_down_multi(stores, rules, old, new, maps)
+    for i, (s, rule, g) in enumerate(zip(stores, rules, got)):
+        assert equals_oracle(g, oracle_of(s).drill_down(old, new, maps, rule)), ("drillDown", i, rule)
+    assert launches == 5
+
+
+def test_nine_of_one_group_make_a_second_chunk_of_the_fused_call():
+    old, mid, new, sel, maps = [3, 4], [2, 4], [2, 2], [[2, 0], ident(4)], [ident(2), [0, 0, 1, 1]]
+    stores = small_stores(np.random.default_rng(17), [("float32", 0.0)] * 9, 12)
+    got, launches = HipStore.dice_drillup_multi(stores, ["sum"] * 9, old, mid, new, sel, maps)
+    assert launches == 2
+    for i, (s, g) in enumerate(zip(stores, got)):
+        assert equals_oracle(g, oracle_of(s).dice(old, mid, sel).drill_up(mid, new, maps, "sum")), i
