@@ -1768,6 +1768,66 @@ static bool drilldown_takes_lines(const olap_plan *p, const DrillUpAxis &a, int 
   return !spread && a.aligned16 && (a.inner * sizeof(T)) % 128 != 0 && (*whole_groups || a.inner * sizeof(T) >= 2048) && !getenv("OLAP_DD_NO_LINES");
 }
 
+// The gather family (K7 extended): dice and the other remapped copies, the fused dice -> drillUp, the row forms of
+// drillDown and load (every form, between cell types too: `in` is the other store, `out` this one) put up to kMaxBatch
+// pairs behind one launch, and so do the brick forms of reorder.  What stays pair by pair: the two-axis transpose of a reorder
+// without masks, the two-pass drillDown (its quotients live in ONE buffer of the plan), drillDown with distributions
+// and the per-cell drilldown_kernel.
+static bool gather_family_batches(const olap_plan *p, bool masks) {
+  switch (p->kind) {
+    case PLAN_GATHER: return !(p->xy_ok && !masks);
+    case PLAN_GATHER_REDUCE: return true;
+    case PLAN_DRILLDOWN: return p->dd_rows;
+    case PLAN_LOAD: return true;
+    case PLAN_BRICK: return !(p->xy_ok && !masks);
+    default: return false;
+  }
+}
+
+// Which form of the family the plan takes over the nb pairs of `b`, and its launch.  olap_plan_run comes here with
+// Batch<T>::one(...), a batch call with a chunk.  `aligned`: every buffer of every pair is on the 16-byte grid (else a
+// lane moves one cell); `out_aligned`: the outputs are, which is all dice_direct asks for.
+template <typename T>
+static hipError_t launch_gather_family(const olap_plan *p, bool hs, const Batch<T> &b, unsigned nb, bool aligned, bool out_aligned,
+                                       hipStream_t stream) {
+  switch (p->kind) {
+    case PLAN_GATHER: {
+      if (p->dice_direct && out_aligned) return Launch<T>::dice_direct(hs, b, nb, p->dice_rows, stream);
+      Remap r = p->remap;
+      const int vec = remap_for_launch(r, p->vec, aligned);
+      return Launch<T>::gather(hs, vec, b, nb, r, stream);
+    }
+    case PLAN_LOAD: {
+      if (p->his_dtype == p->dtype && p->lperm.perm) return Launch<T>::load_permute(hs, b, nb, p->lperm, stream);
+      Remap r = p->remap;
+      const int vec = remap_for_launch(r, p->vec, aligned);
+      if (p->his_dtype == p->dtype) return Launch<T>::load_scatter(hs, vec, b, nb, r, stream);
+      const void *his[kMaxBatch];  // between cell types: b.in holds the other store's cells, whatever their type
+      void *mine[kMaxBatch];
+      for (unsigned i = 0; i < nb; ++i) his[i] = b.in[i], mine[i] = b.out[i];
+      return launch_load_convert(p->his_dtype, p->dtype, hs, vec, his, b.st_in, mine, b.st_out, nb, r, stream);
+    }
+    case PLAN_BRICK:
+      return Launch<T>::reorder_brick(hs, b, nb, p->brick, p->n_bricks, stream);
+    case PLAN_GATHER_REDUCE: {
+      GatherReduce g = p->gr;
+      const int vec = remap_for_launch(g.r, p->vec, aligned);
+      return Launch<T>::gather_reduce(p->method, hs, vec, b, nb, g, stream);
+    }
+    case PLAN_DRILLDOWN: {  // p->dd_rows
+      int vec;
+      const DrillUpAxis a = axis_for_launch(p, aligned, &vec);
+      const bool divide = p->method == OLAP_SUM;
+      bool whole_groups;
+      if (drilldown_takes_lines<T>(p, a, vec, &whole_groups))
+        return Launch<T>::drilldown_rows_lines(hs, !whole_groups, b, nb, a, divide, p->dd_longest, stream);
+      return Launch<T>::drilldown_rows(hs, vec, b, nb, a, divide, p->dd.use_rounding, p->dd_longest, stream);
+    }
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
 // `rule` >= 0: the drillUp rule to run with instead of the one the plan was built for (a drillUp plan's tables do not
 // depend on it; nothing in the plan is written, so a cached plan stays shareable)
 template <typename T>
@@ -1780,6 +1840,12 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
   hipError_t e = hipSuccess;
   if (p->xy_ok && !hs) {  // reorder without a mask to honour: pure permutation of the cells
     e = launch_transpose_xy(p->xy, (int)sizeof(T), in_v, out_v, out_s, all_aligned16(in_v, nullptr, out_v, out_s), stream);
+    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+    return OLAP_OK;
+  }
+  if (gather_family_batches(p, hs)) {  // a single pair is a batch of one
+    e = launch_gather_family<T>(p, hs, Batch<T>::one(in, in_s, out, out_s), 1, all_aligned16(in, in_s, out, out_s),
+                                all_aligned16(nullptr, nullptr, out, out_s), stream);
     if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
     return OLAP_OK;
   }
@@ -1801,66 +1867,25 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_DRILLUP_GENERIC:
       e = Launch<T>::drillup_generic(drillup_method, hs, in, in_s, out, out_s, p->gen, stream);
       break;
-    case PLAN_GATHER: {
-      if (p->dice_direct && all_aligned16(nullptr, nullptr, out, out_s)) {
-        e = Launch<T>::dice_direct(hs, in, in_s, out, out_s, p->dice_rows, stream);
-        break;
-      }
-      Remap r = p->remap;
-      const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
-      e = Launch<T>::gather(hs, vec, in, in_s, out, out_s, r, stream);
-      break;
-    }
-    case PLAN_LOAD: {
-      if (p->his_dtype != p->dtype) {  // between cell types: a batch of one
-        Remap r = p->remap;
-        const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
-        e = launch_load_convert(p->his_dtype, p->dtype, hs, vec, &in_v, &in_s, &out_v, &out_s, 1, r, stream);
-        break;
-      }
-      if (p->lperm.perm) {
-        e = Launch<T>::load_permute(hs, in, in_s, out, out_s, p->lperm, stream);
-        break;
-      }
-      Remap r = p->remap;
-      const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
-      e = Launch<T>::load_scatter(hs, vec, in, in_s, out, out_s, r, stream);
-      break;
-    }
+    case PLAN_GATHER:
+    case PLAN_LOAD:
     case PLAN_BRICK:
-      e = Launch<T>::reorder_brick(hs, in, in_s, out, out_s, p->brick, p->n_bricks, stream);
-      break;
+    case PLAN_GATHER_REDUCE:
+      break;  // the gather family, above
     case PLAN_COMPOSE: {  // a batch of one without a fill
       Remap r = p->remap;
       const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
       e = launch_compose(p->dtype, hs, vec, &in_v, &in_s, &out_v, &out_s, nullptr, nullptr, 1, r, stream);
       break;
     }
-    case PLAN_GATHER_REDUCE: {
-      GatherReduce g = p->gr;
-      const int vec = remap_for_launch(g.r, p->vec, all_aligned16(in, in_s, out, out_s));
-      e = Launch<T>::gather_reduce(p->method, hs, vec, in, in_s, out, out_s, g, stream);
-      break;
-    }
-    case PLAN_DRILLDOWN: {
-      if (p->dd_rows) {
-        int vec;
-        const DrillUpAxis a = axis_for_launch(p, all_aligned16(in, in_s, out, out_s), &vec);
-        const bool divide = p->method == OLAP_SUM;
-        bool whole_groups;
-        if (drilldown_takes_lines<T>(p, a, vec, &whole_groups))
-          e = Launch<T>::drilldown_rows_lines(hs, !whole_groups, in, in_s, out, out_s, a, divide, p->dd_longest, stream);
-        else
-          e = Launch<T>::drilldown_rows(hs, vec, in, in_s, out, out_s, a, divide, p->dd.use_rounding, p->dd_longest, stream);
-        break;
-      }
+    case PLAN_DRILLDOWN: {  // the row forms went with the gather family
       if (p->dd_two_pass) {
         T *q = (T *)p->dev_tmp;
         e = Launch<T>::drilldown_scale(hs, in, in_s, q, p->dds, stream);
         if (e != hipSuccess) break;
         Remap r = p->remap;
         const int vec = remap_for_launch(r, p->vec, all_aligned16(nullptr, nullptr, out, out_s));
-        e = Launch<T>::gather(false, vec, q, nullptr, out, out_s, r, stream);
+        e = Launch<T>::gather(false, vec, Batch<T>::one(q, nullptr, out, out_s), 1, r, stream);
         break;
       }
       const unsigned long long init = ~0ull;
@@ -1950,22 +1975,6 @@ static int run_batch_typed(olap_plan *p, const Pairs &q, const int *methods, hip
   return OLAP_OK;
 }
 
-// The gather family (K7 extended): dice and the other remapped copies, the fused dice -> drillUp, the row forms of
-// drillDown and load (every form, between cell types too: `in` is the other store, `out` this one) put up to kMaxBatch
-// pairs behind one launch, and so do the brick forms of reorder.  What stays pair by pair: the two-axis transpose of a reorder
-// without masks, the two-pass drillDown (its quotients live in ONE buffer of the plan), drillDown with distributions
-// and the per-cell drilldown_kernel.
-static bool gather_family_batches(const olap_plan *p, bool masks) {
-  switch (p->kind) {
-    case PLAN_GATHER: return !(p->xy_ok && !masks);
-    case PLAN_GATHER_REDUCE: return true;
-    case PLAN_DRILLDOWN: return p->dd_rows;
-    case PLAN_LOAD: return true;
-    case PLAN_BRICK: return !(p->xy_ok && !masks);
-    default: return false;
-  }
-}
-
 // kernel launches of one olap_plan_run of this plan
 static int launches_per_pair(const olap_plan *p) { return p->kind == PLAN_DRILLDOWN && p->dd_two_pass ? 2 : 1; }
 
@@ -1986,31 +1995,7 @@ static int run_gather_family_typed(olap_plan *p, const Pairs &q, hipStream_t str
       *launches += nb * launches_per_pair(p);
       continue;
     }
-    const bool hs = q.masks();
-    hipError_t e = hipSuccess;
-    if (p->kind == PLAN_GATHER) {
-      e = p->dice_direct ? Launch<T>::dice_direct_batch(hs, b, (unsigned)nb, p->dice_rows, stream)
-                         : Launch<T>::gather_batch(hs, p->vec, b, (unsigned)nb, p->remap, stream);
-    } else if (p->kind == PLAN_GATHER_REDUCE) {
-      e = Launch<T>::gather_reduce_batch(p->method, hs, p->vec, b, (unsigned)nb, p->gr, stream);
-    } else if (p->kind == PLAN_BRICK) {
-      e = Launch<T>::reorder_brick_batch(hs, b, (unsigned)nb, p->brick, p->n_bricks, stream);
-    } else if (p->kind == PLAN_LOAD) {  // the forms as run_typed chooses them
-      if (p->his_dtype != p->dtype)
-        e = launch_load_convert(p->his_dtype, p->dtype, hs, p->vec, q.in_v + first, q.in_s ? q.in_s + first : nullptr, q.out_v + first,
-                                q.out_s ? q.out_s + first : nullptr, (unsigned)nb, p->remap, stream);
-      else if (p->lperm.perm) e = Launch<T>::load_permute_batch(hs, b, (unsigned)nb, p->lperm, stream);
-      else e = Launch<T>::load_scatter_batch(hs, p->vec, b, (unsigned)nb, p->remap, stream);
-    } else {  // the row forms of drillDown, chosen as run_typed chooses them
-      int vec;
-      const DrillUpAxis a = axis_for_launch(p, true, &vec);
-      const bool divide = p->method == OLAP_SUM;
-      bool whole_groups;
-      if (drilldown_takes_lines<T>(p, a, vec, &whole_groups))
-        e = Launch<T>::drilldown_rows_lines_batch(hs, !whole_groups, b, (unsigned)nb, a, divide, p->dd_longest, stream);
-      else
-        e = Launch<T>::drilldown_rows_batch(hs, vec, b, (unsigned)nb, a, divide, p->dd.use_rounding, p->dd_longest, stream);
-    }
+    const hipError_t e = launch_gather_family<T>(p, q.masks(), b, (unsigned)nb, true, true, stream);
     if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
     *launches += 1;
   }

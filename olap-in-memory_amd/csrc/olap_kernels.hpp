@@ -52,8 +52,12 @@ struct DrillUpAxis {
 // kMaxBatch independent (input, output) buffer pairs; blockIdx.y picks the pair.  Cube.drillUp calls the store once
 // per measure (src/cube.js:1012-1020); on cubes of a few MB a launch costs more than the bytes it moves, so the
 // measures that share a rule share a launch (olap_plan_run_batch).  A single measure is a batch of one.
-// The gather family (dice, fused dice -> drillUp, the row forms of drillDown) has batched kernels of its own beside
-// the single-pair ones: *_batch_kernel, the same body over the pair blockIdx.y picks.
+// The gather family (dice, fused dice -> drillUp, reorder, load, the row forms of drillDown) follows the same rule: its
+// launchers take a Batch<T>, a single store is Batch<T>::one(...) with a grid of one in y, and seven of its ten forms
+// are one kernel each.  Three keep a four-pointer kernel beside the batched one (*_batch_kernel) for nb == 1, chosen
+// inside their launchers: gather, gather_reduce and load_scatter measured 0.2 - 0.4 us per launch slower through the
+// Batch<T> form, outside the run-to-run spread of the four-pointer one (profiles/gather_family_one_kernel.txt.  The
+// cause was not looked for; a pair's four pointers lie in four 64-byte lines of a Batch<T> and in one as plain arguments).
 constexpr int kMaxBatch = 8;
 template <typename T>
 struct Batch {
@@ -2480,13 +2484,7 @@ __device__ __forceinline__ void load_scatter_run_cells(const T *__restrict__ his
 }
 
 template <typename T, bool HAS_STATUS, typename IDX>
-__global__ __launch_bounds__(kBlock) void load_scatter_run_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
-                                                                  int32_t *__restrict__ mine_st, const Remap r, const uint64_t n_cells) {
-  load_scatter_run_cells<T, HAS_STATUS, IDX>(his, his_st, mine, mine_st, r, n_cells);
-}
-
-template <typename T, bool HAS_STATUS, typename IDX>
-__global__ __launch_bounds__(kBlock) void load_scatter_run_batch_kernel(const Batch<T> b, const Remap r, const uint64_t n_cells) {
+__global__ __launch_bounds__(kBlock) void load_scatter_run_kernel(const Batch<T> b, const Remap r, const uint64_t n_cells) {
   const uint32_t pair = blockIdx.y;
   load_scatter_run_cells<T, HAS_STATUS, IDX>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], r, n_cells);
 }
@@ -2585,15 +2583,9 @@ __device__ __forceinline__ void load_permute_rows_cells(const T *__restrict__ hi
   }
 }
 
-template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(kBlock) void load_permute_rows_kernel(const T *__restrict__ his, const int32_t *__restrict__ his_st, T *__restrict__ mine,
-                                                                   int32_t *__restrict__ mine_st, const LoadPermute a) {
-  load_permute_rows_cells<T, HAS_STATUS>(his, his_st, mine, mine_st, a);
-}
-
 // (every pair of a batch stages its own tile: the LDS layout depends on "mine has a mask", which a batch shares)
 template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(kBlock) void load_permute_rows_batch_kernel(const Batch<T> b, const LoadPermute a) {
+__global__ __launch_bounds__(kBlock) void load_permute_rows_kernel(const Batch<T> b, const LoadPermute a) {
   const uint32_t pair = blockIdx.y;
   load_permute_rows_cells<T, HAS_STATUS>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a);
 }
@@ -2732,17 +2724,9 @@ __device__ __forceinline__ void reorder_brick_cells(const T *__restrict__ in,
   }
 }
 
-template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(1024) void reorder_brick_kernel(const T *__restrict__ in,
-                                                               const int32_t *__restrict__ st_in,
-                                                               T *__restrict__ out,
-                                                               int32_t *__restrict__ st_out, const Brick b) {
-  reorder_brick_cells<T, HAS_STATUS>(in, st_in, out, st_out, b);
-}
-
 // the measures of a cube reordered together: blockIdx.y picks the pair
 template <typename T, bool HAS_STATUS>
-__global__ __launch_bounds__(1024) void reorder_brick_batch_kernel(const Batch<T> p, const Brick b) {
+__global__ __launch_bounds__(1024) void reorder_brick_kernel(const Batch<T> p, const Brick b) {
   const uint32_t pair = blockIdx.y;
   reorder_brick_cells<T, HAS_STATUS>(p.in[pair], p.st_in[pair], p.out[pair], p.st_out[pair], b);
 }
@@ -2835,15 +2819,7 @@ __device__ __forceinline__ void reorder_brick4_cells(const T *__restrict__ in,
 }
 
 template <typename T, bool HAS_STATUS, int UB>
-__global__ __launch_bounds__(1024) void reorder_brick4_kernel(const T *__restrict__ in,
-                                                                const int32_t *__restrict__ st_in,
-                                                                T *__restrict__ out,
-                                                                int32_t *__restrict__ st_out, const Brick b) {
-  reorder_brick4_cells<T, HAS_STATUS, UB>(in, st_in, out, st_out, b);
-}
-
-template <typename T, bool HAS_STATUS, int UB>
-__global__ __launch_bounds__(1024) void reorder_brick4_batch_kernel(const Batch<T> p, const Brick b) {
+__global__ __launch_bounds__(1024) void reorder_brick4_kernel(const Batch<T> p, const Brick b) {
   const uint32_t pair = blockIdx.y;
   reorder_brick4_cells<T, HAS_STATUS, UB>(p.in[pair], p.st_in[pair], p.out[pair], p.st_out[pair], b);
 }
@@ -3019,15 +2995,9 @@ __device__ __forceinline__ void dice_direct_cells(const T *__restrict__ in, cons
   }
 }
 
-template <typename T, bool HAS_STATUS, int U>
-__global__ __launch_bounds__(kBlock) void dice_direct_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
-                                                             int32_t *__restrict__ st_out, const DiceDirect a) {
-  dice_direct_cells<T, HAS_STATUS, U>(in, st_in, out, st_out, a);
-}
-
 // several measures: blockIdx.y picks the pair (every workgroup of a pair fills the same row table)
 template <typename T, bool HAS_STATUS, int U>
-__global__ __launch_bounds__(kBlock) void dice_direct_batch_kernel(const Batch<T> b, const DiceDirect a) {
+__global__ __launch_bounds__(kBlock) void dice_direct_kernel(const Batch<T> b, const DiceDirect a) {
   const uint32_t pair = blockIdx.y;
   dice_direct_cells<T, HAS_STATUS, U>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a);
 }
@@ -3192,15 +3162,9 @@ __device__ __forceinline__ void drilldown_rows_cells(const T *__restrict__ in,
   }
 }
 
-template <typename T, bool HAS_STATUS, int VEC>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
-                                                                int32_t *__restrict__ st_out, const DrillUpAxis a, int divide, int use_rounding, uint32_t segments) {
-  drilldown_rows_cells<T, HAS_STATUS, VEC>(in, st_in, out, st_out, a, divide, use_rounding, segments);
-}
-
 // the measures of a cube that share sum-or-copy and the integer flag: blockIdx.y picks the pair
 template <typename T, bool HAS_STATUS, int VEC>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_batch_kernel(const Batch<T> b, const DrillUpAxis a, int divide, int use_rounding, uint32_t segments) {
+__global__ __launch_bounds__(kBlock) void drilldown_rows_kernel(const Batch<T> b, const DrillUpAxis a, int divide, int use_rounding, uint32_t segments) {
   const uint32_t pair = blockIdx.y;
   drilldown_rows_cells<T, HAS_STATUS, VEC>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a, divide, use_rounding, segments);
 }
@@ -3340,15 +3304,9 @@ __device__ __forceinline__ void drilldown_rows_lines_cells(const T *__restrict__
   }
 }
 
-template <typename T, bool HAS_STATUS, int VEC, bool ANY>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_kernel(const T *__restrict__ in, const int32_t *__restrict__ st_in, T *__restrict__ out,
-                                                                      int32_t *__restrict__ st_out, const DrillUpAxis a, int divide, uint32_t segments, uint32_t bpr) {
-  drilldown_rows_lines_cells<T, HAS_STATUS, VEC, ANY>(in, st_in, out, st_out, a, divide, segments, bpr);
-}
-
 // several measures: blockIdx.y picks the pair (a row's shift is taken from its own pair's output pointer)
 template <typename T, bool HAS_STATUS, int VEC, bool ANY>
-__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_batch_kernel(const Batch<T> b, const DrillUpAxis a, int divide, uint32_t segments, uint32_t bpr) {
+__global__ __launch_bounds__(kBlock) void drilldown_rows_lines_kernel(const Batch<T> b, const DrillUpAxis a, int divide, uint32_t segments, uint32_t bpr) {
   const uint32_t pair = blockIdx.y;
   drilldown_rows_lines_cells<T, HAS_STATUS, VEC, ANY>(b.in[pair], b.st_in[pair], b.out[pair], b.st_out[pair], a, divide, segments, bpr);
 }
@@ -4017,38 +3975,24 @@ struct Launch {
                                    const DrillUpAxis &a, const DrillUpReduce &rd, hipStream_t stream);
   static hipError_t drillup_generic(int method, bool has_status, const T *in, const int32_t *st_in, T *out,
                                     int32_t *st_out, const DrillUpGeneric &a, hipStream_t stream);
-  static hipError_t gather(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                           const Remap &r, hipStream_t stream);
-  static hipError_t gather_reduce(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out,
-                                  int32_t *st_out, const GatherReduce &a, hipStream_t stream);
-  static hipError_t reorder_brick(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                  const Brick &b, uint64_t n_bricks, hipStream_t stream);
-  static hipError_t load_scatter(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st,
-                                 const Remap &r, hipStream_t stream);
   static hipError_t drilldown(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
                               const DrillDown &a, hipStream_t stream);
-  static hipError_t drilldown_rows(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                   const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group, hipStream_t stream);
-  static hipError_t dice_direct(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const DiceRows &a,
-                                hipStream_t stream);
-  static hipError_t drilldown_rows_lines(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                         const DrillUpAxis &a, int divide, uint32_t longest_group, hipStream_t stream);
   static hipError_t drilldown_scale(bool has_status, const T *in, const int32_t *st_in, T *q, const DrillDownScale &a,
                                     hipStream_t stream);
   // the gather family over nb (<= kMaxBatch) buffer pairs in one launch (blockIdx.y picks the pair); all pairs with or
-  // all without a mask, every argument besides the buffers as the single-pair launcher of the same name takes it
-  static hipError_t gather_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
-  static hipError_t dice_direct_batch(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &a, hipStream_t stream);
-  static hipError_t gather_reduce_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
-                                        hipStream_t stream);
-  static hipError_t drilldown_rows_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
-                                         int use_rounding, uint32_t longest_group, hipStream_t stream);
-  static hipError_t drilldown_rows_lines_batch(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
-                                               int divide, uint32_t longest_group, hipStream_t stream);
+  // all without a mask.  A single store is Batch<T>::one(...) with nb == 1.
+  static hipError_t gather(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
+  static hipError_t dice_direct(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &a, hipStream_t stream);
+  static hipError_t gather_reduce(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
+                                  hipStream_t stream);
+  static hipError_t drilldown_rows(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
+                                   int use_rounding, uint32_t longest_group, hipStream_t stream);
+  static hipError_t drilldown_rows_lines(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+                                         int divide, uint32_t longest_group, hipStream_t stream);
+  static hipError_t reorder_brick(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream);
   // load over nb pairs (his = in, mine = out); the run form needs every `in` / `st_in` on the 16-byte grid
-  static hipError_t reorder_brick_batch(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream);
-  static hipError_t load_scatter_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
-  static hipError_t load_permute_batch(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream);
+  static hipError_t load_scatter(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream);
+  static hipError_t load_permute(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream);
   static hipError_t canonicalize(T *values, int32_t *status, uint64_t n, int def_nan, int use_status,
                                  hipStream_t stream);
   static hipError_t from_f64(const double *src, T *values, int32_t *status, uint64_t n, int def_nan,
@@ -4060,8 +4004,6 @@ struct Launch {
                                    hipStream_t stream);
   static hipError_t drillup_segmented(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
                                       const DrillUpAxis &a, const SegmentedRows &sg, hipStream_t stream);
-  static hipError_t load_permute(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const LoadPermute &a,
-                                 hipStream_t stream);
   static hipError_t total(const T *values, const int32_t *status, uint64_t n, int def_nan, void *workspace, double *total,
                           unsigned long long *count, hipStream_t stream);
   static hipError_t compact_count(const T *values, const int32_t *status, uint64_t n, uint64_t chunk, unsigned n_chunks,
@@ -4520,11 +4462,9 @@ hipError_t Launch<T>::drillup_generic(int method, bool has_status, const T *in, 
                     : drillup_generic_method<T, false>(method, in, st_in, out, st_out, a, stream);
 }
 
-// `b` (nb pairs): the batched launch; else the one pair (in, st_in, out, st_out).  The launchers of the gather family
-// below all take their buffers this way.
+// The launchers of the gather family below all take their buffers as the nb pairs of `b` (blockIdx.y picks the pair).
 template <typename T>
-static hipError_t dice_direct_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
-                                     unsigned nb, const DiceRows &p, hipStream_t stream) {
+hipError_t Launch<T>::dice_direct(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &p, hipStream_t stream) {
   DiceDirect a;
   if (!dice_direct_fits<T>(p, &a)) return hipErrorInvalidValue;
   const int groups = dice_direct_groups();
@@ -4533,11 +4473,7 @@ static hipError_t dice_direct_launch(bool has_status, const T *in, const int32_t
   if (n_out == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((n_out + SPAN - 1) / SPAN);
   const size_t lds = (size_t)a.rows * sizeof(int64_t);  // <= (SPAN / V + 3) entries
-#define OLAP_DD(HS, UU)                                                                                                     \
-  do {                                                                                                                      \
-    if (b) hipLaunchKernelGGL((dice_direct_batch_kernel<T, HS, UU>), dim3(blocks, nb), kBlock, lds, stream, *b, a);         \
-    else hipLaunchKernelGGL((dice_direct_kernel<T, HS, UU>), blocks, kBlock, lds, stream, in, st_in, out, st_out, a);       \
-  } while (0)
+#define OLAP_DD(HS, UU) hipLaunchKernelGGL((dice_direct_kernel<T, HS, UU>), dim3(blocks, nb), kBlock, lds, stream, b, a)
   if (has_status) {
     if (groups == 1) OLAP_DD(true, 1); else if (groups == 2) OLAP_DD(true, 2); else if (groups == 8) OLAP_DD(true, 8); else OLAP_DD(true, 4);
   } else {
@@ -4547,18 +4483,7 @@ static hipError_t dice_direct_launch(bool has_status, const T *in, const int32_t
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t Launch<T>::dice_direct(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const DiceRows &p,
-                                  hipStream_t stream) {
-  return dice_direct_launch<T>(has_status, in, st_in, out, st_out, nullptr, 1, p, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::dice_direct_batch(bool has_status, const Batch<T> &b, unsigned nb, const DiceRows &p, hipStream_t stream) {
-  return dice_direct_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &b, nb, p, stream);
-}
-
-// Which batched gather runs: the lane-loop form (gather_pairs_kernel) or the blockIdx.y form (gather_batch_kernel).
+// Which gather runs for several pairs: the lane-loop form (gather_pairs_kernel) or the blockIdx.y form (gather_batch_kernel).
 // Measured on Float32 pairs without masks (profiles/multi_gather_r31.txt): the two tie within the run's spread for 2 and
 // 4 pairs and for a middle dimension, the lane loop wins at 8 pairs of an innermost-dimension dice (9.3 against 12.0 us),
 // so pairs without masks take it; masked pairs (twice the loads in flight per lane, not measured) keep blockIdx.y.
@@ -4569,20 +4494,20 @@ inline bool gather_batch_lane_loop(bool has_status) {
 }
 
 template <typename T>
-static hipError_t gather_launch(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
-                                unsigned nb, const Remap &r, hipStream_t stream) {
+hipError_t Launch<T>::gather(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
   if (r.total == 0) return hipSuccess;
   const unsigned grid = grid_for(r.total);
   const bool idx32 = r.total * (uint64_t)vec < 0xFFFFFFFFull;
-  const bool lane_loop = b && gather_batch_lane_loop(has_status);
+  const bool one = nb == 1;  // measured slower through the Batch<T> form (see the note at Batch): one pair keeps its own kernel
+  const bool lane_loop = !one && gather_batch_lane_loop(has_status);
 #define OLAP_G(HS, V)                                                                                                        \
   do {                                                                                                                       \
-    if (b && lane_loop && idx32) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, *b, nb, r); \
-    else if (b && lane_loop) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, *b, nb, r); \
-    else if (b && idx32) hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, *b, r); \
-    else if (b) hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);     \
-    else if (idx32) hipLaunchKernelGGL((gather_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, in, st_in, out, st_out, r); \
-    else hipLaunchKernelGGL((gather_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, in, st_in, out, st_out, r);        \
+    if (one && idx32) hipLaunchKernelGGL((gather_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, b.in[0], b.st_in[0], b.out[0], b.st_out[0], r); \
+    else if (one) hipLaunchKernelGGL((gather_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, b.in[0], b.st_in[0], b.out[0], b.st_out[0], r); \
+    else if (lane_loop && idx32) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, b, nb, r); \
+    else if (lane_loop) hipLaunchKernelGGL((gather_pairs_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, b, nb, r);    \
+    else if (idx32) hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, b, r);  \
+    else hipLaunchKernelGGL((gather_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, b, r);             \
   } while (0)
   if (has_status) {
     if (vec == 4) OLAP_G(true, 4); else if (vec == 2) OLAP_G(true, 2); else OLAP_G(true, 1);
@@ -4593,27 +4518,15 @@ static hipError_t gather_launch(bool has_status, int vec, const T *in, const int
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t Launch<T>::gather(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                             const Remap &r, hipStream_t stream) {
-  return gather_launch<T>(has_status, vec, in, st_in, out, st_out, nullptr, 1, r, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::gather_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
-  return gather_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, r, stream);
-}
-
 template <typename T, int METHOD, bool HS>
-static hipError_t gather_reduce_vec(int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b, unsigned nb,
-                                    const GatherReduce &a, hipStream_t stream) {
+static hipError_t gather_reduce_vec(int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a, hipStream_t stream) {
   constexpr bool kAdditive = (METHOD == OLAP_SUM || METHOD == OLAP_AVERAGE || METHOD == OLAP_PARTIAL_AVERAGE);
   const bool fast = kAdditive && !HS && !a.r.def_nan;
   const unsigned grid = grid_for(a.r.total);
 #define OLAP_GR(V, F)                                                                                                              \
-  do {                                                                                                                             \
-    if (b) hipLaunchKernelGGL((gather_reduce_batch_kernel<T, METHOD, HS, V, F>), dim3(grid, nb), kBlock, 0, stream, *b, a);        \
-    else hipLaunchKernelGGL((gather_reduce_kernel<T, METHOD, HS, V, F>), grid, kBlock, 0, stream, in, st_in, out, st_out, a);      \
+  do {  /* one pair keeps its own kernel, as in Launch<T>::gather */                                                               \
+    if (nb == 1) hipLaunchKernelGGL((gather_reduce_kernel<T, METHOD, HS, V, F>), grid, kBlock, 0, stream, b.in[0], b.st_in[0], b.out[0], b.st_out[0], a); \
+    else hipLaunchKernelGGL((gather_reduce_batch_kernel<T, METHOD, HS, V, F>), dim3(grid, nb), kBlock, 0, stream, b, a);           \
   } while (0)
   if constexpr (kAdditive && !HS) {
     if (fast) {
@@ -4627,68 +4540,50 @@ static hipError_t gather_reduce_vec(int vec, const T *in, const int32_t *st_in, 
 }
 
 template <typename T, bool HS>
-static hipError_t gather_reduce_method(int method, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
-                                       unsigned nb, const GatherReduce &a, hipStream_t stream) {
+static hipError_t gather_reduce_method(int method, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a, hipStream_t stream) {
   switch (method) {
-    case OLAP_SUM: return gather_reduce_vec<T, OLAP_SUM, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_AVERAGE: return gather_reduce_vec<T, OLAP_AVERAGE, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_HIGHEST: return gather_reduce_vec<T, OLAP_HIGHEST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_LOWEST: return gather_reduce_vec<T, OLAP_LOWEST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_FIRST: return gather_reduce_vec<T, OLAP_FIRST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_LAST: return gather_reduce_vec<T, OLAP_LAST, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    case OLAP_PARTIAL_AVERAGE: return gather_reduce_vec<T, OLAP_PARTIAL_AVERAGE, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
-    default: return gather_reduce_vec<T, OLAP_PRODUCT, HS>(vec, in, st_in, out, st_out, b, nb, a, stream);
+    case OLAP_SUM: return gather_reduce_vec<T, OLAP_SUM, HS>(vec, b, nb, a, stream);
+    case OLAP_AVERAGE: return gather_reduce_vec<T, OLAP_AVERAGE, HS>(vec, b, nb, a, stream);
+    case OLAP_HIGHEST: return gather_reduce_vec<T, OLAP_HIGHEST, HS>(vec, b, nb, a, stream);
+    case OLAP_LOWEST: return gather_reduce_vec<T, OLAP_LOWEST, HS>(vec, b, nb, a, stream);
+    case OLAP_FIRST: return gather_reduce_vec<T, OLAP_FIRST, HS>(vec, b, nb, a, stream);
+    case OLAP_LAST: return gather_reduce_vec<T, OLAP_LAST, HS>(vec, b, nb, a, stream);
+    case OLAP_PARTIAL_AVERAGE: return gather_reduce_vec<T, OLAP_PARTIAL_AVERAGE, HS>(vec, b, nb, a, stream);
+    default: return gather_reduce_vec<T, OLAP_PRODUCT, HS>(vec, b, nb, a, stream);
   }
 }
 
 template <typename T>
-hipError_t Launch<T>::gather_reduce(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out,
-                                    int32_t *st_out, const GatherReduce &a, hipStream_t stream) {
+hipError_t Launch<T>::gather_reduce(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
+                                    hipStream_t stream) {
   if (a.r.total == 0) return hipSuccess;
-  return has_status ? gather_reduce_method<T, true>(method, vec, in, st_in, out, st_out, nullptr, 1, a, stream)
-                    : gather_reduce_method<T, false>(method, vec, in, st_in, out, st_out, nullptr, 1, a, stream);
+  return has_status ? gather_reduce_method<T, true>(method, vec, b, nb, a, stream)
+                    : gather_reduce_method<T, false>(method, vec, b, nb, a, stream);
 }
 
 template <typename T>
-hipError_t Launch<T>::gather_reduce_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const GatherReduce &a,
-                                          hipStream_t stream) {
-  if (a.r.total == 0) return hipSuccess;
-  return has_status ? gather_reduce_method<T, true>(method, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream)
-                    : gather_reduce_method<T, false>(method, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream);
-}
-
-// p == nullptr: the one pair given by its four pointers; else the nb pairs of *p (blockIdx.y)
-template <typename T>
-static hipError_t reorder_brick_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *p, unsigned nb,
-                                       const Brick &b, uint64_t n_bricks, hipStream_t stream) {
+hipError_t Launch<T>::reorder_brick(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream) {
   if (n_bricks == 0) return hipSuccess;
   if constexpr (sizeof(T) == 4) {
-    bool aligned = (((uintptr_t)in | (uintptr_t)out | (uintptr_t)st_in | (uintptr_t)st_out) & 15u) == 0;
-    for (unsigned i = 0; p && i < nb; ++i)
-      aligned = aligned && (((uintptr_t)p->in[i] | (uintptr_t)p->out[i] | (uintptr_t)p->st_in[i] | (uintptr_t)p->st_out[i]) & 15u) == 0;
+    bool aligned = true;
+    for (unsigned i = 0; i < nb; ++i)
+      aligned = aligned && (((uintptr_t)p.in[i] | (uintptr_t)p.out[i] | (uintptr_t)p.st_in[i] | (uintptr_t)p.st_out[i]) & 15u) == 0;
     if (b.quad && aligned) {
       const size_t padded = (size_t)(b.elems + ((b.elems >> 5) << 2)) * 4;
       const size_t lds4 = padded * (has_status ? 2 : 1);
       // above 64 KiB of dynamic LDS the kernel has to be told once (bricks of 10^4 cells with the mask: 90 KiB)
-      static PerDeviceFlag raised, raised_batch;
-      if (!(p ? raised_batch : raised).test_and_set()) {
-        hipError_t e1 = p ? hipFuncSetAttribute((const void *)reorder_brick4_batch_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
-                          : hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        hipError_t e2 = p ? hipFuncSetAttribute((const void *)reorder_brick4_batch_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
-                          : hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      static PerDeviceFlag raised;
+      if (!raised.test_and_set()) {
+        hipError_t e1 = hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        hipError_t e2 = hipFuncSetAttribute((const void *)reorder_brick4_kernel<T, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         if (e1 != hipSuccess) return e1;
         if (e2 != hipSuccess) return e2;
       }
       unsigned threads4 = kBlock;  // measured: 512 and 1024 lanes lose on the [10]^8 reversal, 512 gains 7 % on a 2-D transpose
       if (const char *e = getenv("OLAP_BRICK_THREADS")) threads4 = (unsigned)atoi(e);
       // groups in flight per lane: 2, 4 and 10 measure the same (the 400-byte runs, not latency, set the pace)
-      if (p) {
-        if (has_status) hipLaunchKernelGGL((reorder_brick4_batch_kernel<T, true, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, *p, b);
-        else hipLaunchKernelGGL((reorder_brick4_batch_kernel<T, false, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, *p, b);
-      } else {
-        if (has_status) hipLaunchKernelGGL((reorder_brick4_kernel<T, true, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
-        else hipLaunchKernelGGL((reorder_brick4_kernel<T, false, 4>), (unsigned)n_bricks, threads4, lds4, stream, in, st_in, out, st_out, b);
-      }
+      if (has_status) hipLaunchKernelGGL((reorder_brick4_kernel<T, true, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, p, b);
+      else hipLaunchKernelGGL((reorder_brick4_kernel<T, false, 4>), dim3((unsigned)n_bricks, nb), threads4, lds4, stream, p, b);
       return hipGetLastError();
     }
   }
@@ -4697,54 +4592,30 @@ static hipError_t reorder_brick_launch(bool has_status, const T *in, const int32
   unsigned threads = kBlock;  // larger workgroups for larger bricks bought nothing (tools/sweep.py)
   if (const char *e = getenv("OLAP_BRICK_THREADS")) threads = (unsigned)atoi(e);
   if (lds > 48 * 1024) {  // bricks sized for the 16-byte form, run here because a buffer is not 16 B aligned
-    static PerDeviceFlag raised_scalar, raised_scalar_batch;
-    if (!(p ? raised_scalar_batch : raised_scalar).test_and_set()) {
-      hipError_t e1 = p ? hipFuncSetAttribute((const void *)reorder_brick_batch_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
-                        : hipFuncSetAttribute((const void *)reorder_brick_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      hipError_t e2 = p ? hipFuncSetAttribute((const void *)reorder_brick_batch_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)
-                        : hipFuncSetAttribute((const void *)reorder_brick_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    static PerDeviceFlag raised_scalar;
+    if (!raised_scalar.test_and_set()) {
+      hipError_t e1 = hipFuncSetAttribute((const void *)reorder_brick_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      hipError_t e2 = hipFuncSetAttribute((const void *)reorder_brick_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
       if (e1 != hipSuccess) return e1;
       if (e2 != hipSuccess) return e2;
     }
   }
-  if (p) {
-    if (has_status) hipLaunchKernelGGL((reorder_brick_batch_kernel<T, true>), dim3((unsigned)n_bricks, nb), threads, lds, stream, *p, b);
-    else hipLaunchKernelGGL((reorder_brick_batch_kernel<T, false>), dim3((unsigned)n_bricks, nb), threads, lds, stream, *p, b);
-  } else {
-    if (has_status) hipLaunchKernelGGL((reorder_brick_kernel<T, true>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
-    else hipLaunchKernelGGL((reorder_brick_kernel<T, false>), (unsigned)n_bricks, threads, lds, stream, in, st_in, out, st_out, b);
-  }
+  if (has_status) hipLaunchKernelGGL((reorder_brick_kernel<T, true>), dim3((unsigned)n_bricks, nb), threads, lds, stream, p, b);
+  else hipLaunchKernelGGL((reorder_brick_kernel<T, false>), dim3((unsigned)n_bricks, nb), threads, lds, stream, p, b);
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t Launch<T>::reorder_brick(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                    const Brick &b, uint64_t n_bricks, hipStream_t stream) {
-  return reorder_brick_launch<T>(has_status, in, st_in, out, st_out, nullptr, 1, b, n_bricks, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::reorder_brick_batch(bool has_status, const Batch<T> &p, unsigned nb, const Brick &b, uint64_t n_bricks, hipStream_t stream) {
-  return reorder_brick_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &p, nb, b, n_bricks, stream);
-}
-
-// b == nullptr: the one pair given by its four pointers; else the nb pairs of *b (blockIdx.y)
-template <typename T>
-static hipError_t load_scatter_launch(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const Batch<T> *b,
-                                      unsigned nb, const Remap &r, hipStream_t stream) {
+hipError_t Launch<T>::load_scatter(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
   if (r.total == 0) return hipSuccess;
   const bool idx32 = r.total * (uint64_t)vec < 0xFFFFFFFFull;
-  bool his_aligned = (((uintptr_t)his | (uintptr_t)his_st) & 15u) == 0;
-  for (unsigned i = 0; b && i < nb; ++i) his_aligned = his_aligned && (((uintptr_t)b->in[i] | (uintptr_t)b->st_in[i]) & 15u) == 0;
+  bool his_aligned = true;
+  for (unsigned i = 0; i < nb; ++i) his_aligned = his_aligned && (((uintptr_t)b.in[i] | (uintptr_t)b.st_in[i]) & 15u) == 0;
   if (vec == 1 && r.nd >= 1 && his_aligned && !getenv("OLAP_LOAD_NO_RUNS")) {
     // the innermost dimension is remapped: 16 bytes of HIS per lane, one decode per lane
     const uint64_t lanes = (r.total + 16 / sizeof(T) - 1) / (16 / sizeof(T));
     const unsigned g = grid_for(lanes);
-#define OLAP_LDR(HS, IDX)                                                                                                               \
-  do {                                                                                                                                  \
-    if (b) hipLaunchKernelGGL((load_scatter_run_batch_kernel<T, HS, IDX>), dim3(g, nb), kBlock, 0, stream, *b, r, r.total);             \
-    else hipLaunchKernelGGL((load_scatter_run_kernel<T, HS, IDX>), g, kBlock, 0, stream, his, his_st, mine, mine_st, r, r.total);      \
-  } while (0)
+#define OLAP_LDR(HS, IDX) hipLaunchKernelGGL((load_scatter_run_kernel<T, HS, IDX>), dim3(g, nb), kBlock, 0, stream, b, r, r.total)
     if (has_status) {
       if (idx32) OLAP_LDR(true, uint32_t); else OLAP_LDR(true, uint64_t);
     } else {
@@ -4754,15 +4625,12 @@ static hipError_t load_scatter_launch(bool has_status, int vec, const T *his, co
     return hipGetLastError();
   }
   const unsigned grid = grid_for(r.total);
-#define OLAP_LD(HS, V)                                                                                                                \
-  do {                                                                                                                                \
-    if (b) {                                                                                                                          \
-      if (idx32) hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);       \
-      else hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, *b, r);             \
-    } else {                                                                                                                          \
-      if (idx32) hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r); \
-      else hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, his, his_st, mine, mine_st, r);     \
-    }                                                                                                                                 \
+#define OLAP_LD(HS, V)                                                                                                      \
+  do {  /* one pair keeps its own kernel, as in Launch<T>::gather */                                                        \
+    if (nb == 1 && idx32) hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint32_t>), grid, kBlock, 0, stream, b.in[0], b.st_in[0], b.out[0], b.st_out[0], r); \
+    else if (nb == 1) hipLaunchKernelGGL((load_scatter_kernel<T, HS, V, uint64_t>), grid, kBlock, 0, stream, b.in[0], b.st_in[0], b.out[0], b.st_out[0], r); \
+    else if (idx32) hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint32_t>), dim3(grid, nb), kBlock, 0, stream, b, r); \
+    else hipLaunchKernelGGL((load_scatter_batch_kernel<T, HS, V, uint64_t>), dim3(grid, nb), kBlock, 0, stream, b, r);      \
   } while (0)
   if (has_status) {
     if (vec == 4) OLAP_LD(true, 4); else if (vec == 2) OLAP_LD(true, 2); else OLAP_LD(true, 1);
@@ -4774,43 +4642,15 @@ static hipError_t load_scatter_launch(bool has_status, int vec, const T *his, co
 }
 
 template <typename T>
-hipError_t Launch<T>::load_scatter(bool has_status, int vec, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st,
-                                   const Remap &r, hipStream_t stream) {
-  return load_scatter_launch<T>(has_status, vec, his, his_st, mine, mine_st, nullptr, 1, r, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::load_scatter_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const Remap &r, hipStream_t stream) {
-  return load_scatter_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, r, stream);
-}
-
-template <typename T>
-static hipError_t load_permute_launch(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const Batch<T> *b,
-                                      unsigned nb, const LoadPermute &a, hipStream_t stream) {
+hipError_t Launch<T>::load_permute(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream) {
   if (a.n_rows == 0 || a.len == 0) return hipSuccess;
   const uint64_t tiles = (a.n_rows + a.rows_per_tile - 1) / a.rows_per_tile;
   if (tiles >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-  const bool my_mask = b ? b->st_out[0] != nullptr : mine_st != nullptr;
+  const bool my_mask = b.st_out[0] != nullptr;
   const size_t lds = kTileBytes + (my_mask ? kTileBytes / sizeof(T) * 4 : 0) + (size_t)a.len * 4;
-  if (b) {
-    if (has_status) hipLaunchKernelGGL((load_permute_rows_batch_kernel<T, true>), dim3((unsigned)tiles, nb), kBlock, lds, stream, *b, a);
-    else hipLaunchKernelGGL((load_permute_rows_batch_kernel<T, false>), dim3((unsigned)tiles, nb), kBlock, lds, stream, *b, a);
-  } else {
-    if (has_status) hipLaunchKernelGGL((load_permute_rows_kernel<T, true>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
-    else hipLaunchKernelGGL((load_permute_rows_kernel<T, false>), (unsigned)tiles, kBlock, lds, stream, his, his_st, mine, mine_st, a);
-  }
+  if (has_status) hipLaunchKernelGGL((load_permute_rows_kernel<T, true>), dim3((unsigned)tiles, nb), kBlock, lds, stream, b, a);
+  else hipLaunchKernelGGL((load_permute_rows_kernel<T, false>), dim3((unsigned)tiles, nb), kBlock, lds, stream, b, a);
   return hipGetLastError();
-}
-
-template <typename T>
-hipError_t Launch<T>::load_permute(bool has_status, const T *his, const int32_t *his_st, T *mine, int32_t *mine_st, const LoadPermute &a,
-                                   hipStream_t stream) {
-  return load_permute_launch<T>(has_status, his, his_st, mine, mine_st, nullptr, 1, a, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::load_permute_batch(bool has_status, const Batch<T> &b, unsigned nb, const LoadPermute &a, hipStream_t stream) {
-  return load_permute_launch<T>(has_status, nullptr, nullptr, nullptr, nullptr, &b, nb, a, stream);
 }
 
 template <typename T>
@@ -4824,18 +4664,14 @@ hipError_t Launch<T>::drilldown(bool has_status, const T *in, const int32_t *st_
 }
 
 template <typename T>
-static hipError_t drilldown_rows_launch(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const Batch<T> *b,
-                                        unsigned nb, const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group,
-                                        hipStream_t stream) {
+hipError_t Launch<T>::drilldown_rows(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
+                                     int use_rounding, uint32_t longest_group, hipStream_t stream) {
   const uint32_t segments = (longest_group + kChildrenPerBlock - 1) / kChildrenPerBlock;
   const uint64_t blocks = a.outer * a.G * a.blocks_per_row * segments;
   if (blocks == 0) return hipSuccess;
   if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-#define OLAP_DD(HS, V)                                                                                                                        \
-  do {                                                                                                                                        \
-    if (b) hipLaunchKernelGGL((drilldown_rows_batch_kernel<T, HS, V>), dim3((unsigned)blocks, nb), kBlock, 0, stream, *b, a, divide, use_rounding, segments); \
-    else hipLaunchKernelGGL((drilldown_rows_kernel<T, HS, V>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, use_rounding, segments); \
-  } while (0)
+#define OLAP_DD(HS, V) \
+  hipLaunchKernelGGL((drilldown_rows_kernel<T, HS, V>), dim3((unsigned)blocks, nb), kBlock, 0, stream, b, a, divide, use_rounding, segments)
   if (has_status) {
     if (vec == 4) OLAP_DD(true, 4); else if (vec == 2) OLAP_DD(true, 2); else OLAP_DD(true, 1);
   } else {
@@ -4846,21 +4682,8 @@ static hipError_t drilldown_rows_launch(bool has_status, int vec, const T *in, c
 }
 
 template <typename T>
-hipError_t Launch<T>::drilldown_rows(bool has_status, int vec, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                     const DrillUpAxis &a, int divide, int use_rounding, uint32_t longest_group, hipStream_t stream) {
-  return drilldown_rows_launch<T>(has_status, vec, in, st_in, out, st_out, nullptr, 1, a, divide, use_rounding, longest_group, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::drilldown_rows_batch(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, int divide,
-                                           int use_rounding, uint32_t longest_group, hipStream_t stream) {
-  return drilldown_rows_launch<T>(has_status, vec, nullptr, nullptr, nullptr, nullptr, &b, nb, a, divide, use_rounding, longest_group, stream);
-}
-
-template <typename T>
-static hipError_t drilldown_rows_lines_launch(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                              const Batch<T> *b, unsigned nb, const DrillUpAxis &a, int divide, uint32_t longest_group,
-                                              hipStream_t stream) {
+hipError_t Launch<T>::drilldown_rows_lines(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+                                           int divide, uint32_t longest_group, hipStream_t stream) {
   constexpr int V = 16 / (int)sizeof(T);
   constexpr uint32_t LINE = 128 / sizeof(T);
   const uint32_t segments = (longest_group + kChildrenPerBlock - 1) / kChildrenPerBlock;
@@ -4868,27 +4691,12 @@ static hipError_t drilldown_rows_lines_launch(bool has_status, bool any_shift, c
   const uint64_t blocks = a.outer * a.G * bpr * segments;
   if (blocks == 0) return hipSuccess;
   if (blocks >= 0x7FFFFFFFull) return hipErrorInvalidValue;
-#define OLAP_DDL(HS, ANY)                                                                                                                     \
-  do {                                                                                                                                        \
-    if (b) hipLaunchKernelGGL((drilldown_rows_lines_batch_kernel<T, HS, V, ANY>), dim3((unsigned)blocks, nb), kBlock, 0, stream, *b, a, divide, segments, (uint32_t)bpr); \
-    else hipLaunchKernelGGL((drilldown_rows_lines_kernel<T, HS, V, ANY>), (unsigned)blocks, kBlock, 0, stream, in, st_in, out, st_out, a, divide, segments, (uint32_t)bpr); \
-  } while (0)
+#define OLAP_DDL(HS, ANY) \
+  hipLaunchKernelGGL((drilldown_rows_lines_kernel<T, HS, V, ANY>), dim3((unsigned)blocks, nb), kBlock, 0, stream, b, a, divide, segments, (uint32_t)bpr)
   if (has_status) { if (any_shift) OLAP_DDL(true, true); else OLAP_DDL(true, false); }
   else { if (any_shift) OLAP_DDL(false, true); else OLAP_DDL(false, false); }
 #undef OLAP_DDL
   return hipGetLastError();
-}
-
-template <typename T>
-hipError_t Launch<T>::drilldown_rows_lines(bool has_status, bool any_shift, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                           const DrillUpAxis &a, int divide, uint32_t longest_group, hipStream_t stream) {
-  return drilldown_rows_lines_launch<T>(has_status, any_shift, in, st_in, out, st_out, nullptr, 1, a, divide, longest_group, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::drilldown_rows_lines_batch(bool has_status, bool any_shift, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
-                                                 int divide, uint32_t longest_group, hipStream_t stream) {
-  return drilldown_rows_lines_launch<T>(has_status, any_shift, nullptr, nullptr, nullptr, nullptr, &b, nb, a, divide, longest_group, stream);
 }
 
 template <typename T>
