@@ -548,6 +548,34 @@ int olap_store_compose_multi(int n, const olap_store *const *sources, const doub
  * launches of up to 8; the two-axis transpose runs pair by pair behind the call. */
 int olap_store_reorder_multi(int n, const olap_store *const *stores, olap_store **out, int ndim,
                              const uint32_t *old_len, const int32_t *perm, int *launches);
+/* Running aggregates along one dimension (Cube.cumulate) of n stores — the stored measures of one cube, a rule each
+ * (methods[i]); a single store is a batch of one.  The cube is lens[0..ndim) in row-major order, `axis` the dimension
+ * the aggregate runs along and map[k] < n_groups the group of its item k (NULL: the whole dimension is one group and
+ * n_groups is not read).  out[i] is a new store of the same cells, type and default as stores[i].  Its cell at item k
+ * of `axis`, every other coordinate fixed, holds what the single item of that dimension holds after
+ *   dice(axis: the items of k's group at positions <= k)  ->  drillUp(axis -> one item, methods[i])
+ * i.e. the state of the reference's drillUp loop (in-memory.js:298-331) after each contribution instead of only after
+ * the last one: contributions arrive in ascending item order; an unset cell contributes nothing and receives the
+ * carried running value (it stays unset only while its group has contributed nothing); a running value equal to the
+ * default is unset at that position and the aggregate restarts with the next contribution (setValue's delete,
+ * :126-131); `average` divides at each position by the contribution count modulo 65 536 and leaves the sum when that
+ * is 0; the float64 state is converted to the cell type once per output cell and never rounded in between.
+ * Every series-and-group is walked sequentially by one lane (olap_cumulate.hip), so float64 sums associate exactly as
+ * the reference's loop does.  One stated deviation OF THE DEFINING CHAIN, not of this call: where that chain lands in
+ * the few-outputs regime of drillUp (fewer than 131 072 outputs and groups of >= 256 members) it re-associates
+ * float64 sums; there this call keeps the reference's order and the chain is the one ~1e-16 off.
+ * Stores that share cell type, default and device share one plan (kept by the plan cache), whatever their rules (a
+ * workgroup reads its pair's rule), and leave in launches of up to 8: *launches (may be NULL) is the sum of
+ * ceil(group size / 8) over the groups.  A mask is read and written
+ * only where it is primary.  n == 0 or a cube of 0 cells launches nothing.
+ * Checked on the host before any device work, with the same codes and messages on a machine without a device, in this
+ * order: a NULL list or n < 0; a NULL entry ("store i of the batch is NULL"); a rule outside the seven reference
+ * methods (OLAP_ERR_UNSUPPORTED_METHOD); ndim and the length vector; axis outside [0, ndim); n_groups above the items of the
+ * dimension (groups nobody maps to may exist, but not more groups than items); a map entry >= n_groups
+ * (OLAP_ERR_INDEX_RANGE); a tracked store ("ordered: ..."); a store whose size is not the product of lens
+ * (OLAP_ERR_LENGTH_MISMATCH); stores on different devices.  On an error no store is created.  The stores are only read. */
+int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                              const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: a cube partitioned along its OUTERMOST dimension.  Row-major layout

@@ -228,7 +228,7 @@ extern "C" int olap_device_synchronize(void) {
 }
 
 // ------------------------------------------------------------------ plans
-enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE };
+enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE };
 
 struct olap_plan {
   PlanKind kind;
@@ -244,6 +244,7 @@ struct olap_plan {
   Brick brick{};
   uint64_t n_bricks = 0;
   GatherReduce gr{};
+  CumulateView cum{};                      // PLAN_CUMULATE (olap_cumulate.hip)
   bool xy_ok = false;                      // reorder without a mask: two-axis LDS transpose (olap_transpose.hip; 4- and 8-byte cells)
   TransposeXY xy{};
   DrillUpReduce reduce{};                  // S > 0: reduce regime of the one-axis drillUp
@@ -335,6 +336,16 @@ static bool is_identity_u32(const uint32_t *m, uint32_t old_len, uint32_t new_le
   return true;
 }
 
+// CSR of a K->G map: members of each group in ascending order (counting sort, stable)
+static void build_csr(const uint32_t *m, uint32_t K, uint32_t G, std::vector<uint32_t> &gstart, std::vector<uint32_t> &order) {
+  gstart.assign((size_t)G + 1, 0);
+  for (uint32_t k = 0; k < K; ++k) gstart[m[k] + 1]++;
+  for (uint32_t g = 0; g < G; ++g) gstart[g + 1] += gstart[g];
+  order.resize(K);
+  std::vector<uint32_t> cur(gstart.begin(), gstart.end() - 1);
+  for (uint32_t k = 0; k < K; ++k) order[cur[m[k]]++] = k;
+}
+
 // ---- drillUp ------------------------------------------------------------------------------
 extern "C" int olap_drillup_plan(olap_plan **out, int dtype, int default_kind, int method, int ndim,
                                  const uint32_t *old_len, const uint32_t *new_len,
@@ -369,16 +380,6 @@ extern "C" int olap_drillup_plan(olap_plan **out, int dtype, int default_kind, i
   p->method = method;
   p->in_cells = product(old_len, ndim);
   p->out_cells = product(new_len, ndim);
-
-  // CSR of a K->G map: members of each group in ascending order (counting sort, stable)
-  auto build_csr = [](const uint32_t *m, uint32_t K, uint32_t G, std::vector<uint32_t> &gstart, std::vector<uint32_t> &order) {
-    gstart.assign((size_t)G + 1, 0);
-    for (uint32_t k = 0; k < K; ++k) gstart[m[k] + 1]++;
-    for (uint32_t g = 0; g < G; ++g) gstart[g + 1] += gstart[g];
-    order.resize(K);
-    std::vector<uint32_t> cur(gstart.begin(), gstart.end() - 1);
-    for (uint32_t k = 0; k < K; ++k) order[cur[m[k]]++] = k;
-  };
 
   if (n_changed <= 1) {
     // One changed axis (or none: then the whole cube is a single untouched "axis" of length 1).
@@ -1872,6 +1873,8 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_BRICK:
     case PLAN_GATHER_REDUCE:
       break;  // the gather family, above
+    case PLAN_CUMULATE:
+      break;  // never here: its plans are private to olap_store_cumulate_multi, which launches them itself (cumulate_run)
     case PLAN_COMPOSE: {  // a batch of one without a fill
       Remap r = p->remap;
       const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
@@ -3524,6 +3527,116 @@ extern "C" int olap_store_reorder_multi(int n, const olap_store *const *stores, 
   return run_multi(
       n, stores, nullptr, out, launches, [&](const olap_store *s, int) { return reorder_key(s, ndim, old_len, perm); },
       [&](olap_plan **p, const olap_store *s, int) { return olap_reorder_plan(p, s->dtype, s->default_kind, ndim, old_len, perm); });
+}
+
+// ---- running aggregates along one dimension (Cube.cumulate; kernels: olap_cumulate.hip) -------------------------------
+static PlanKey cumulate_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map) {
+  PlanKey key;
+  key.i32('K');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
+  key.u32s(lens, ndim);
+  key.i32(map != nullptr);
+  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
+  return key;
+}
+
+// the arguments passed olap_store_cumulate_multi's checks; the rule is not part of a plan (a launch takes one per pair)
+static int cumulate_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
+                         const uint32_t *map) {
+  *out = nullptr;
+  int rc = require_device();
+  if (rc) return rc;
+  olap_plan *p = new (std::nothrow) olap_plan();
+  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
+  p->kind = PLAN_CUMULATE;
+  p->dtype = dtype;
+  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
+  p->method = OLAP_SUM;
+  p->in_cells = p->out_cells = product(lens, ndim);
+  CumulateView &v = p->cum;
+  v.outer = product(lens, axis);
+  v.K = lens[axis];
+  v.inner = product(lens + axis + 1, ndim - axis - 1);
+  v.G = map ? n_groups : 1;
+  v.def_nan = p->def_nan;
+  std::vector<uint32_t> gstart, order;
+  bool contiguous = true;
+  if (map) {
+    build_csr(map, lens[axis], n_groups, gstart, order);
+    for (size_t j = 0; j < order.size(); ++j) contiguous = contiguous && order[j] == j;
+  } else {
+    gstart = {0, lens[axis]};
+  }
+  std::vector<uint32_t> tab(gstart);
+  const size_t order_off = tab.size();
+  if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
+  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) {
+    olap_plan_destroy(p);
+    return rc;
+  }
+  v.gstart = (const uint32_t *)p->dev_tab;
+  v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
+  cumulate_choose(v, (int)olap_dtype_size(dtype), contiguous);
+  p->kernel_name = v.form == CUMULATE_COLUMN ? (v.vec == 1 ? "cumulate_column_kernel<cell>" : "cumulate_column_kernel")
+                   : v.form == CUMULATE_ROW_WHOLE ? "cumulate_rows_kernel" : "cumulate_rows_kernel<chunked>";
+  *out = p;
+  return OLAP_OK;
+}
+
+// the pairs of one group, a rule each, in launches of up to kMaxBatch
+static int cumulate_run(olap_plan *p, const Pairs &q, const int *rules, int *launches) {
+  if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
+  if (p->in_cells == 0) return OLAP_OK;
+  int cur;
+  if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
+  for (int first = 0; first < q.n; first += kMaxBatch) {
+    const int nb = std::min(q.n - first, (int)kMaxBatch);
+    const hipError_t e = launch_cumulate(p->dtype, q.masks(), nb, rules + first, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first,
+                                         p->cum, nullptr);
+    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+    *launches += 1;
+  }
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                                         const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches) {
+  if (launches) *launches = 0;
+  int rc = check_list(n, stores && out && methods, "store / method list is NULL");
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) out[i] = nullptr;
+  if ((rc = check_entries(n, stores))) return rc;
+  // the lists, the rules, the lengths and the map first: refused without looking into a store
+  for (int i = 0; i < n; ++i)
+    if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
+  if ((rc = check_dims(ndim, lens, lens))) return rc;
+  if (axis < 0 || axis >= ndim) return fail(OLAP_ERR_INVALID_ARGUMENT, "axis %d out of range [0, %d)", axis, ndim);
+  // (more groups than items would only be groups without members, and a table of n_groups + 1 entries to build and upload)
+  if (map && n_groups > lens[axis])
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "cumulate: %u groups for the %u items of the dimension", n_groups, lens[axis]);
+  for (uint32_t k = 0; map && k < lens[axis]; ++k)
+    if (map[k] >= n_groups)
+      return fail(OLAP_ERR_INDEX_RANGE, "cumulate map: entry %u = %u is outside the groups (%u)", k, map[k], n_groups);
+  if ((rc = check_untracked(n, stores, "its key order needs the per-item chain"))) return rc;
+  if ((rc = check_cells(n, stores, product(lens, ndim)))) return rc;
+  for (int i = 1; i < n; ++i)
+    if (stores[i]->device != stores[0]->device)
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "cumulate: the stores live on different devices (%d and %d)", stores[0]->device, stores[i]->device);
+  int made = 0;
+  rc = for_each_group(
+      n, [&](int i, int j) { return same_cells(stores[j], stores[i]); },
+      [&](const std::vector<int> &members) {
+        const olap_store *s0 = stores[members[0]];
+        std::vector<int> rules(members.size());
+        for (size_t k = 0; k < members.size(); ++k) rules[k] = methods[members[k]];
+        return run_group(
+            (int)members.size(), members.data(), stores, out, [&] { return cumulate_key(s0, ndim, lens, axis, n_groups, map); }, 0,
+            [&](olap_plan **p) { return cumulate_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, nullptr,
+            [&](olap_plan *plan, const Pairs &q) { return cumulate_run(plan, q, rules.data(), &made); });
+      });
+  if (rc) return drop_results(n, out, rc);
+  if (launches) *launches = made;
+  return OLAP_OK;
 }
 
 static PlanKey load_key(const olap_store *mine, const olap_store *his, int ndim, const uint32_t *my_len, const uint32_t *his_len,

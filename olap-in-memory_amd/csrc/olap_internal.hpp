@@ -171,6 +171,28 @@ struct TransposeXY {
 OLAP_INTERNAL hipError_t launch_transpose_xy(const TransposeXY &t, int cell_bytes, const void *in, void *out, int32_t *st_out, bool aligned16,
                                               hipStream_t stream);
 
+// ---- running aggregates along one axis (olap_cumulate.hip, K13) -----------------------------------
+// View [outer, K, inner] with one K -> G map as the CSR of the drillUp plans: members of group g are
+// order[gstart[g] .. gstart[g + 1]) ascending (order == nullptr: the groups are the contiguous runs themselves).
+constexpr uint32_t kCumulateTileCells = 4096;  // cells of one row-form tile in LDS (NOTEBOOK: cumulate)
+enum CumulateForm { CUMULATE_COLUMN = 0, CUMULATE_ROW_WHOLE = 1, CUMULATE_ROW_CHUNKED = 2 };
+struct CumulateView {
+  uint64_t outer, K, inner, G;
+  const uint32_t *gstart;  // device, [G + 1]
+  const uint32_t *order;   // device, [K], or nullptr
+  int def_nan;
+  int form;                // CumulateForm
+  uint32_t vec;            // column form: cells per slot (16 bytes' worth, or 1: the uncoalesced form of long interleaved series)
+  uint32_t series;         // row forms: series per tile
+  uint32_t rows;           // chunked row form: rows of K per chunk
+  uint32_t pitch;          // row forms: cells between two series of a tile (odd)
+};
+// chooses form, slot width and tile cuts from the shape alone (cell_bytes: 4 or 8); `contiguous`: order == nullptr
+OLAP_INTERNAL void cumulate_choose(CumulateView &v, int cell_bytes, bool contiguous);
+// nb <= 8 pairs of one cell type and default, a rule each (methods[k]); masks on all pairs or on none
+OLAP_INTERNAL hipError_t launch_cumulate(int dtype, bool has_status, int nb, const int *methods, const void *const *in, const int32_t *const *st_in,
+                                         void *const *out, int32_t *const *st_out, const CumulateView &v, hipStream_t stream);
+
 // ---- insertion order of tracked stores (olap_order.hip) --------------------------------------------
 OLAP_INTERNAL void order_free(olap_store *s);
 OLAP_INTERNAL int order_clone(const olap_store *from, olap_store *to);

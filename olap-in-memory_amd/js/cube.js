@@ -734,6 +734,88 @@ class Cube {
     return this._derive(newDimensions, (store, id) => refinedStores[id] || store.drillDown(this.dimensions, newDimensions, this.storedMeasuresRules[id][dimensionId]));
   }
 
+  // ------------------------------------------------------------------ running aggregates
+  /** the checks cumulate and _cumulatePerItem share; returns the dimension's index */
+  _checkCumulate(dimensionId, attribute) {
+    const index = this.getDimensionIndex(dimensionId);
+    if (index === -1) throw new Error(`cumulate: no such dimension: ${dimensionId}`);
+    if (this.dimensions[index].attributes.indexOf(attribute) === -1) throw new Error(`cumulate: no such attribute: ${attribute} in dimension: ${dimensionId}`);
+    return index;
+  }
+
+  /**
+   * Running aggregates along one dimension (year-to-date, cumulative counts, a running maximum, forward-fill): a new
+   * cube with the same dimensions, rules and computed measures in which every stored measure holds, at item i of
+   * `dimensionId` (all other coordinates fixed), what
+   *   this.dice(dimensionId, root, members).drillUp(dimensionId, attribute)
+   * holds in its single item of that dimension, `members` being the items of i's group under `attribute` at positions
+   * <= i — by the measure's rule for that dimension.  'all' makes the whole dimension one group; 'year' on a monthly
+   * dimension is year-to-date.  An unset cell receives the carried running value; a running value equal to the
+   * default is unset and the aggregate restarts.  This cube is untouched.
+   * The stored measures go to the device in one call (HipStore.cumulateMany -> olap_store_cumulate_multi, K13); the
+   * measures it does not take — order-tracking ones (a `first` / `last` rule), sharded ones, stores of another class —
+   * go item by item (_cumulatePerItem, which is also the definition).  HipStore.lastCumulatePath says what ran.
+   */
+  cumulate(dimensionId, attribute = 'all') {
+    const index = this._checkCumulate(dimensionId, attribute);
+    if (this.dimensions[index].rootAttribute === attribute) return this.clone(); // every group has one member
+    const ids = this.storedMeasureIds;
+    const mine = ids.filter((id) => this.storedMeasures[id] instanceof HipStore);
+    const made = {};
+    HipStore.lastCumulatePath = 'per-item';
+    if (mine.length > 0) {
+      const results = HipStore.cumulateMany(mine.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute,
+        mine.map((id) => (this.storedMeasuresRules[id] || {})[dimensionId]));
+      mine.forEach((id, i) => {
+        if (results[i]) made[id] = results[i];
+      });
+    }
+    const rest = ids.filter((id) => !made[id]);
+    const launches = HipStore.lastBatchLaunches;
+    const perItem = rest.length > 0 ? this._cumulatePerItem(dimensionId, attribute, rest) : null;
+    if (HipStore.lastCumulatePath === 'device') HipStore.lastBatchLaunches = launches; // (the chains count their own)
+    return this._derive(this.dimensions.slice(), (store, id) => made[id] || perItem.storedMeasures[id]);
+  }
+
+  /**
+   * The definition of cumulate, run as written: one dice -> drillUp chain per item of the dimension (2 K launches per
+   * measure), each item's rolled-up cells assembled into the result on the host (getData -> setData carries the mask
+   * under both defaults).  The path of the measures the device call does not take, and what the tests compare it with.
+   */
+  _cumulatePerItem(dimensionId, attribute = 'all', measureIds = null) {
+    const index = this._checkCumulate(dimensionId, attribute);
+    const current = this.dimensions[index];
+    const ids = measureIds || this.storedMeasureIds;
+    if (current.rootAttribute === attribute) return this.clone(measureIds || []);
+    // the chains read only the measures asked for (stores are shared: queries never mutate)
+    const source = new Cube(this.dimensions.slice());
+    for (const id of ids) {
+      source.storedMeasures[id] = this.storedMeasures[id];
+      source.storedMeasuresRules[id] = this.storedMeasuresRules[id];
+    }
+    const items = current.getItems();
+    const groups = current.getGroupIndexFromRootIndexMap(attribute);
+    const K = items.length;
+    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
+    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
+    const values = {};
+    for (const id of ids) values[id] = new Array(outer * K * inner);
+    for (let i = 0; i < K; ++i) {
+      const members = items.filter((_, j) => j <= i && groups[j] === groups[i]);
+      const rolled = source.dice(dimensionId, current.rootAttribute, members).drillUp(dimensionId, attribute);
+      for (const id of ids) {
+        const cells = rolled.getData(id);
+        for (let o = 0; o < outer; ++o) for (let j = 0; j < inner; ++j) values[id][(o * K + i) * inner + j] = cells[o * inner + j];
+      }
+    }
+    return this._derive(this.dimensions.slice(), (store, id) => {
+      const rules = this.storedMeasuresRules[id];
+      const fresh = store instanceof HipStore ? this._newStore(store._type, store._defaultValue, rules) : new store.constructor(store.size, store._type, store._defaultValue);
+      fresh.data = values[id];
+      return fresh;
+    }, 'share', (id) => ids.includes(id));
+  }
+
   // ------------------------------------------------------------------ dice / slice
   _diced(index, dimension) {
     // eslint-disable-next-line eqeqeq

@@ -335,6 +335,11 @@ class HipStore {
     return this._nativeStore;
   }
 
+  /** Runs a pending dice (or uploads host-resident cells) now: what the first use of `_native` does. */
+  _materialize() {
+    return this._native;
+  }
+
   /** The host-resident cells while no device store exists yet (null otherwise). */
   get _hostCells() {
     return this._nativeStore ? null : this._host;
@@ -865,6 +870,44 @@ class HipStore {
     }, (store) => store.reorder(oldDimensions, newDimensions));
   }
 
+  /**
+   * Running aggregates along dimension `index` of the stored measures of one cube, each by its own rule — Cube.cumulate:
+   * the cell at item k holds what dice(items of k's group under `attribute` at positions <= k) -> drillUp(rule) holds in
+   * its single item.  Measures held whole on one device, untracked and with cells of their declared type go to the
+   * device in ONE call (addon cumulateMulti -> olap_store_cumulate_multi: one launch for up to 8 measures of one cell
+   * type and default, whatever their rules; DESIGN.md §3 K13) — a single such measure too.  Pending selections are
+   * diced together first (materializeMany).  Returns the new stores in the order given, with null for a measure the
+   * call does not take (order-tracking, sharded, cells of another type, an addon without the call): the caller goes
+   * item by item.  Sets HipStore.lastBatchLaunches and HipStore.lastCumulatePath ('device' when the call ran).
+   */
+  static cumulateMany(stores, dimensions, index, attribute, methods) {
+    const out = new Array(stores.length).fill(null);
+    const addon = backend.load();
+    HipStore.lastCumulatePath = 'per-item';
+    if (typeof addon.cumulateMulti !== 'function') return out;
+    HipStore.materializeMany(stores);
+    let launches = HipStore.lastBatchLaunches;
+    // (a selection alone in its group stays pending there: it is diced now, as the first read of its cells would)
+    for (const store of stores) {
+      if (store._pending && wholeUntracked(store._pending.source)) store._materialize();
+    }
+    const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
+    const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
+    const eligible = (i) => stores[i]._cells === cellTypeOf(stores[i]._type);
+    const run = (natives, together) => {
+      const codes = Int32Array.from(together, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
+      const launchesOut = new Int32Array(1);
+      const made = addon.cumulateMulti(natives, codes, lengthsOf(dimensions), index, groups, nGroups, launchesOut);
+      launches += launchesOut[0];
+      HipStore.lastCumulatePath = 'device';
+      return made;
+    };
+    // (togetherThenSingly sends two or more together; a measure alone among the eligible ones is a batch of one)
+    togetherThenSingly(stores, out, eligible, run, (store, i) => (wholeUntracked(heldStore(store)) && eligible(i) ? store._wrap(run([store._nativeStore], [i])[0]) : null));
+    HipStore.lastBatchLaunches = launches;
+    return out;
+  }
+
   /** in-memory.js:139-176 — mutates this store */
   load(otherStore, myDimensions, hisDimensions) {
     this._loadWith(otherStore, lengthsOf(myDimensions), lengthsOf(hisDimensions), loadTables(myDimensions, hisDimensions));
@@ -1043,6 +1086,9 @@ HipStore.lastBatchLaunches = null;
 // the composeMulti calls the last Cube.compose made: one per source cube that had a measure for it, 0 when every measure
 // took create + fill + load; Cube resets it when compose starts
 HipStore.lastComposeCalls = 0;
+// what the last Cube.cumulate did: 'device' when at least one measure left through cumulateMulti, 'per-item' when every
+// measure took the dice -> drillUp chain item by item (Cube._cumulatePerItem)
+HipStore.lastCumulatePath = null;
 // kernel launches reorderMulti reported for the last reorderMany (null: every measure took reorder one by one)
 HipStore.lastReorderLaunches = null;
 // 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the
