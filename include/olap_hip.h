@@ -576,6 +576,35 @@ int olap_store_reorder_multi(int n, const olap_store *const *stores, olap_store 
  * (OLAP_ERR_LENGTH_MISMATCH); stores on different devices.  On an error no store is created.  The stores are only read. */
 int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
                               const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches);
+/* Rolling-window aggregates along one dimension (Cube.rolling, Cube.shift) of n stores, with the arguments, the
+ * grouping into launches, the results and the mask handling of olap_store_cumulate_multi.  The cell of out[i] at item
+ * k of `axis`, every other coordinate fixed, holds what the single item of that dimension holds after
+ *   dice(axis: the items j of k's group with k - before <= j <= k + after, 0 <= j < K)  ->  drillUp(axis -> one item, methods[i])
+ * and is unset when no item is left (the window lies off the dimension, or outside k's group).  before and after may
+ * each be negative (before = -after = d is a shift by d: a lag for d > 0, a lead for d < 0, the same under every rule);
+ * beyond +-K they act as +-K.  The fold is the reference's drillUp loop (in-memory.js:298-331), started afresh for every
+ * window: set members in ascending item order, a running value equal to the default drops and the fold restarts with
+ * the next member, `average` divides once at the end by the contribution count modulo 65 536 (and leaves the sum when
+ * that is 0), the float64 state is converted to the cell type once per output cell.  No value ever leaves a window by
+ * subtraction and nothing re-associates: a float64 window sum associates as the chain's does.
+ * Cost (olap_rolling.hip): a workgroup stages the rows of its windows in LDS once, `rows + before + after` input rows
+ * for `rows` output rows with rows >= before + after, so a cell is read from device memory at most twice, and folds
+ * each window out of LDS: O(W) LDS reads per cell, W = before + after + 1.  The cliff: a window whose rows do not fit a
+ * tile (16 KiB of input rows: beyond W = 129 for rows of 64 bytes or more once the dimension has more than 256 items;
+ * olap_diag_rolling_choice tells) is folded straight from device memory, O(W) global reads per cell.
+ * Stores that share cell type, default and device share one plan, whatever their rules; the plan-cache key holds
+ * before and after.  Checked on the host before any device work, in cumulate's order and with cumulate's messages
+ * (`rolling` in place of `cumulate`); after the axis and before the groups: before + after < 0
+ * (OLAP_ERR_INVALID_ARGUMENT, "rolling: empty window (before %d, after %d)").  On an error no store is created. */
+int olap_store_rolling_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                             const uint32_t *lens, int axis, int32_t before, int32_t after, uint32_t n_groups,
+                             const uint32_t *map, int *launches);
+/* What olap_store_rolling_multi's planner chooses for cells of cell_bytes (4 or 8) in the view [outer, K, inner] —
+ * host only, no device needed.  choice: the form (0: tiles of whole-width series, 1: tiles of columns, 2: direct),
+ * series per tile, output rows per tile, cells per tile row (0, 0, 0 for the direct form).  has_map: whether a K -> G
+ * map travels (it does not change the cuts today). */
+int olap_diag_rolling_choice(int cell_bytes, uint64_t outer, uint64_t K, uint64_t inner, int32_t before, int32_t after,
+                             int has_map, uint32_t choice[4]);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: a cube partitioned along its OUTERMOST dimension.  Row-major layout

@@ -228,7 +228,7 @@ extern "C" int olap_device_synchronize(void) {
 }
 
 // ------------------------------------------------------------------ plans
-enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE };
+enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE, PLAN_ROLLING };
 
 struct olap_plan {
   PlanKind kind;
@@ -245,6 +245,7 @@ struct olap_plan {
   uint64_t n_bricks = 0;
   GatherReduce gr{};
   CumulateView cum{};                      // PLAN_CUMULATE (olap_cumulate.hip)
+  RollingView roll{};                      // PLAN_ROLLING (olap_rolling.hip)
   bool xy_ok = false;                      // reorder without a mask: two-axis LDS transpose (olap_transpose.hip; 4- and 8-byte cells)
   TransposeXY xy{};
   DrillUpReduce reduce{};                  // S > 0: reduce regime of the one-axis drillUp
@@ -1874,7 +1875,8 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_GATHER_REDUCE:
       break;  // the gather family, above
     case PLAN_CUMULATE:
-      break;  // never here: its plans are private to olap_store_cumulate_multi, which launches them itself (cumulate_run)
+    case PLAN_ROLLING:
+      break;  // never here: their plans are private to olap_store_cumulate_multi / olap_store_rolling_multi, which launch them themselves (cumulate_run, rolling_run)
     case PLAN_COMPOSE: {  // a batch of one without a fill
       Remap r = p->remap;
       const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
@@ -3599,43 +3601,151 @@ static int cumulate_run(olap_plan *p, const Pairs &q, const int *rules, int *lau
   return OLAP_OK;
 }
 
-extern "C" int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
-                                         const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches) {
-  if (launches) *launches = 0;
+// What the calls that run along one dimension share (cumulate, rolling; `what` names the call in the messages): the
+// checks, on the host and in the order the header lists them, and the walk over the groups of one cell type and default.
+// window: rolling's {before, after}, or nullptr.
+static int check_along_axis(const char *what, int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                            const uint32_t *lens, int axis, const int32_t *window, uint32_t n_groups, const uint32_t *map) {
   int rc = check_list(n, stores && out && methods, "store / method list is NULL");
   if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   if ((rc = check_entries(n, stores))) return rc;
-  // the lists, the rules, the lengths and the map first: refused without looking into a store
+  // the lists, the rules, the lengths, the window and the map first: refused without looking into a store
   for (int i = 0; i < n; ++i)
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
   if ((rc = check_dims(ndim, lens, lens))) return rc;
   if (axis < 0 || axis >= ndim) return fail(OLAP_ERR_INVALID_ARGUMENT, "axis %d out of range [0, %d)", axis, ndim);
+  if (window && (int64_t)window[0] + window[1] < 0)
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: empty window (before %d, after %d)", what, window[0], window[1]);
   // (more groups than items would only be groups without members, and a table of n_groups + 1 entries to build and upload)
   if (map && n_groups > lens[axis])
-    return fail(OLAP_ERR_INVALID_ARGUMENT, "cumulate: %u groups for the %u items of the dimension", n_groups, lens[axis]);
+    return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: %u groups for the %u items of the dimension", what, n_groups, lens[axis]);
   for (uint32_t k = 0; map && k < lens[axis]; ++k)
     if (map[k] >= n_groups)
-      return fail(OLAP_ERR_INDEX_RANGE, "cumulate map: entry %u = %u is outside the groups (%u)", k, map[k], n_groups);
+      return fail(OLAP_ERR_INDEX_RANGE, "%s map: entry %u = %u is outside the groups (%u)", what, k, map[k], n_groups);
   if ((rc = check_untracked(n, stores, "its key order needs the per-item chain"))) return rc;
   if ((rc = check_cells(n, stores, product(lens, ndim)))) return rc;
   for (int i = 1; i < n; ++i)
     if (stores[i]->device != stores[0]->device)
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "cumulate: the stores live on different devices (%d and %d)", stores[0]->device, stores[i]->device);
+      return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: the stores live on different devices (%d and %d)", what, stores[0]->device, stores[i]->device);
+  return OLAP_OK;
+}
+
+// key(s0) / build(&plan, s0): the plan of a group, named by its first member; run(plan, pairs, rules, &launches)
+template <typename Key, typename Build, typename Run>
+static int run_along_axis(int n, const olap_store *const *stores, const int *methods, olap_store **out, int *launches, Key key, Build build, Run run) {
   int made = 0;
-  rc = for_each_group(
+  const int rc = for_each_group(
       n, [&](int i, int j) { return same_cells(stores[j], stores[i]); },
       [&](const std::vector<int> &members) {
         const olap_store *s0 = stores[members[0]];
         std::vector<int> rules(members.size());
         for (size_t k = 0; k < members.size(); ++k) rules[k] = methods[members[k]];
         return run_group(
-            (int)members.size(), members.data(), stores, out, [&] { return cumulate_key(s0, ndim, lens, axis, n_groups, map); }, 0,
-            [&](olap_plan **p) { return cumulate_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, nullptr,
-            [&](olap_plan *plan, const Pairs &q) { return cumulate_run(plan, q, rules.data(), &made); });
+            (int)members.size(), members.data(), stores, out, [&] { return key(s0); }, 0, [&](olap_plan **p) { return build(p, s0); }, nullptr,
+            [&](olap_plan *plan, const Pairs &q) { return run(plan, q, rules.data(), &made); });
       });
   if (rc) return drop_results(n, out, rc);
   if (launches) *launches = made;
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
+                                         const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches) {
+  if (launches) *launches = 0;
+  const int rc = check_along_axis("cumulate", n, stores, methods, out, ndim, lens, axis, nullptr, n_groups, map);
+  if (rc) return rc;
+  return run_along_axis(
+      n, stores, methods, out, launches, [&](const olap_store *s0) { return cumulate_key(s0, ndim, lens, axis, n_groups, map); },
+      [&](olap_plan **p, const olap_store *s0) { return cumulate_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, cumulate_run);
+}
+
+// ---- rolling-window aggregates along one dimension (Cube.rolling, Cube.shift; kernels: olap_rolling.hip) --------------
+// before / after as the plan holds them: beyond +-K they act as +-K
+static int64_t window_side(int32_t side, uint32_t K) { return std::max<int64_t>(-(int64_t)K, std::min<int64_t>(side, K)); }
+
+static PlanKey rolling_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, int32_t before, int32_t after, uint32_t n_groups,
+                           const uint32_t *map) {
+  PlanKey key;
+  key.i32('W');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
+  key.u32s(lens, ndim);
+  key.i32((int32_t)window_side(before, lens[axis])), key.i32((int32_t)window_side(after, lens[axis]));
+  key.i32(map != nullptr);
+  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
+  return key;
+}
+
+// the arguments passed olap_store_rolling_multi's checks; the rule is not part of a plan (a launch takes one per pair)
+static int rolling_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, int32_t before, int32_t after,
+                        const uint32_t *map) {
+  *out = nullptr;
+  int rc = require_device();
+  if (rc) return rc;
+  olap_plan *p = new (std::nothrow) olap_plan();
+  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
+  p->kind = PLAN_ROLLING;
+  p->dtype = dtype;
+  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
+  p->method = OLAP_SUM;
+  p->in_cells = p->out_cells = product(lens, ndim);
+  RollingView &v = p->roll;
+  v.outer = product(lens, axis);
+  v.K = lens[axis];
+  v.inner = product(lens + axis + 1, ndim - axis - 1);
+  v.before = window_side(before, lens[axis]);
+  v.after = window_side(after, lens[axis]);
+  v.def_nan = p->def_nan;
+  if (map && (rc = upload(&p->dev_tab, map, (size_t)lens[axis] * sizeof(uint32_t)))) {
+    olap_plan_destroy(p);
+    return rc;
+  }
+  v.map = (const uint32_t *)p->dev_tab;
+  rolling_choose(v, (int)olap_dtype_size(dtype));
+  p->kernel_name = v.form == ROLLING_DIRECT ? "rolling_direct_kernel" : v.form == ROLLING_COLUMNS ? "rolling_tiled_kernel<columns>" : "rolling_tiled_kernel<series>";
+  *out = p;
+  return OLAP_OK;
+}
+
+// the pairs of one group, a rule each, in launches of up to kMaxBatch
+static int rolling_run(olap_plan *p, const Pairs &q, const int *rules, int *launches) {
+  if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
+  if (p->in_cells == 0) return OLAP_OK;
+  int cur;
+  if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
+  for (int first = 0; first < q.n; first += kMaxBatch) {
+    const int nb = std::min(q.n - first, (int)kMaxBatch);
+    const hipError_t e = launch_rolling(p->dtype, q.masks(), nb, rules + first, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first,
+                                        p->roll, nullptr);
+    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+    *launches += 1;
+  }
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_rolling_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim, const uint32_t *lens,
+                                        int axis, int32_t before, int32_t after, uint32_t n_groups, const uint32_t *map, int *launches) {
+  if (launches) *launches = 0;
+  const int32_t window[2] = {before, after};
+  const int rc = check_along_axis("rolling", n, stores, methods, out, ndim, lens, axis, window, n_groups, map);
+  if (rc) return rc;
+  return run_along_axis(
+      n, stores, methods, out, launches, [&](const olap_store *s0) { return rolling_key(s0, ndim, lens, axis, before, after, n_groups, map); },
+      [&](olap_plan **p, const olap_store *s0) { return rolling_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, before, after, map); }, rolling_run);
+}
+
+extern "C" int olap_diag_rolling_choice(int cell_bytes, uint64_t outer, uint64_t K, uint64_t inner, int32_t before, int32_t after, int has_map,
+                                        uint32_t choice[4]) {
+  if (cell_bytes != 4 && cell_bytes != 8) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: cells of %d bytes", cell_bytes);
+  if (!choice) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: NULL result");
+  if (K > 0xFFFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: a dimension of more than 2^32 - 1 items");
+  if ((int64_t)before + after < 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling: empty window (before %d, after %d)", before, after);
+  (void)has_map;  // the map travels as it is: it does not change the cuts
+  RollingView v{};
+  v.outer = outer, v.K = K, v.inner = inner;
+  v.before = window_side(before, (uint32_t)K), v.after = window_side(after, (uint32_t)K);
+  rolling_choose(v, cell_bytes);
+  choice[0] = (uint32_t)v.form, choice[1] = v.series, choice[2] = v.rows, choice[3] = v.cols;
   return OLAP_OK;
 }
 

@@ -24,8 +24,7 @@
 // All rules use Agg<> in float64: for highest / lowest / first / last the round trip through float64 is exact for
 // every cell type and emit_cell keeps such a value as it is, so the result equals Pick<>'s.  The rule is read per
 // pair (Batch<T>::method), uniformly for a workgroup: measures with different rules share a launch.
-#include "olap_internal.hpp"
-#include "olap_kernels.hpp"
+#include "olap_series.hpp"
 
 using namespace olap;
 
@@ -33,18 +32,6 @@ namespace {
 
 constexpr int kRowsAhead = 8;  // row form: cells a lane reads from the tile ahead of the dependent fold
 constexpr uint32_t kTileAlloc = kCumulateTileCells + 256;  // + one pad cell per series (at most 256 series per tile)
-
-// runs CALL with M naming the rule `method` (one of the seven; checked on the host)
-#define CUMULATE_RULE(method, CALL)                                      \
-  switch (method) {                                                      \
-    case OLAP_SUM: { constexpr int M = OLAP_SUM; CALL; break; }          \
-    case OLAP_AVERAGE: { constexpr int M = OLAP_AVERAGE; CALL; break; }  \
-    case OLAP_HIGHEST: { constexpr int M = OLAP_HIGHEST; CALL; break; }  \
-    case OLAP_LOWEST: { constexpr int M = OLAP_LOWEST; CALL; break; }    \
-    case OLAP_FIRST: { constexpr int M = OLAP_FIRST; CALL; break; }      \
-    case OLAP_LAST: { constexpr int M = OLAP_LAST; CALL; break; }        \
-    default: { constexpr int M = OLAP_PRODUCT; CALL; break; }            \
-  }
 
 // One position of a series: the input cell (x, s) contributes if it is set; (x, s) leave as the running cell.
 template <typename T, int METHOD, bool HS>
@@ -67,37 +54,6 @@ __device__ __forceinline__ void running_step(Agg<METHOD> &a, T &x, int32_t &s, b
   Agg<METHOD> f = a;  // average divides a copy: the running sum itself is never rounded or divided
   f.finish(def_nan);
   emit_cell<T>(f.acc, f.has, def_nan, x, s);
-}
-
-// n <= VEC cells from a cell-aligned address: one 16-byte access for a whole slot, cell by cell otherwise
-template <typename T, int VEC>
-__device__ __forceinline__ Vec<T, VEC> load_slot(const T *p, int n) {
-  Vec<T, VEC> r;
-  if constexpr (VEC == 1) {
-    r.v[0] = __builtin_nontemporal_load(p);
-  } else {
-    if (n == VEC) {
-      r = load_stream_cell_aligned<T, VEC>(p);
-    } else {
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) r.v[e] = e < n ? __builtin_nontemporal_load(p + e) : T(0);
-    }
-  }
-  return r;
-}
-template <typename T, int VEC>
-__device__ __forceinline__ void store_slot(T *p, const Vec<T, VEC> &x, int n) {
-  if constexpr (VEC == 1) {
-    __builtin_nontemporal_store(x.v[0], p);
-  } else {
-    if (n == VEC) {
-      store_stream_cell_aligned<T, VEC>(p, x);
-    } else {
-#pragma unroll
-      for (int e = 0; e < VEC; ++e)
-        if (e < n) __builtin_nontemporal_store(x.v[e], p + e);
-    }
-  }
 }
 
 // ---------------------------------------------------------------- column form
@@ -149,34 +105,12 @@ __device__ __forceinline__ void column_walk(const T *__restrict__ in, const int3
 template <typename T, bool HS, int VEC>
 __global__ __launch_bounds__(kBlock) void cumulate_column_kernel(const Batch<T> b, const CumulateView v, const uint64_t items) {
   const uint32_t p = blockIdx.y;
-  CUMULATE_RULE(b.method[p], (column_walk<T, HS, VEC, M>(b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, items)));
+  SERIES_RULE(b.method[p], (column_walk<T, HS, VEC, M>(b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, items)));
 }
 
 // ---------------------------------------------------------------- row form
-// Moves rows [k0, k0 + rows) of `ns` series between global memory and the tile: a series' piece is `seg` contiguous
-// cells, read and written in 16-byte slots (the last slot of a piece cell by cell).
-template <typename T, int VEC, bool LOAD>
-__device__ __forceinline__ void tile_move(T *tile, const T *src, T *dst, uint64_t first_cell, uint64_t series_cells, uint32_t ns, uint32_t seg,
-                                          uint32_t pitch) {
-  const uint32_t slots = (seg + VEC - 1) / VEC;
-  for (uint32_t c = threadIdx.x; c < ns * slots; c += kBlock) {
-    const uint32_t s = c / slots, r = (c % slots) * VEC;
-    const int n = (int)(seg - r < (uint32_t)VEC ? seg - r : (uint32_t)VEC);
-    const uint64_t at = first_cell + (uint64_t)s * series_cells + r;
-    T *cell = tile + s * pitch + r;
-    if constexpr (LOAD) {
-      const Vec<T, VEC> x = load_slot<T, VEC>(src + at, n);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e)
-        if (e < n) cell[e] = x.v[e];
-    } else {
-      Vec<T, VEC> x;
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) x.v[e] = e < n ? cell[e] : T(0);
-      store_slot<T, VEC>(dst + at, x, n);
-    }
-  }
-}
+// (tile_move, olap_series.hpp, moves rows [k0, k0 + rows) of `ns` series between global memory and the tile: a series'
+// piece is rows * inner contiguous cells)
 
 // whole series in the tile: one lane per (series, group, i) walks the group's members
 template <typename T, bool HS, int METHOD>
@@ -290,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void cumulate_rows_kernel(const Batch<T> b,
   __shared__ T tv[kTileAlloc];
   __shared__ int32_t ts[HS ? kTileAlloc : 1];
   const uint32_t p = blockIdx.y;
-  CUMULATE_RULE(b.method[p], (rows_tiles<T, HS, M>(tv, ts, b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, n_tiles)));
+  SERIES_RULE(b.method[p], (rows_tiles<T, HS, M>(tv, ts, b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, n_tiles)));
 }
 
 // Workgroups of a launch along x: beyond it a workgroup takes several tiles, a lane several items.  OLAP_CUMULATE_GRID=n

@@ -193,6 +193,29 @@ OLAP_INTERNAL void cumulate_choose(CumulateView &v, int cell_bytes, bool contigu
 OLAP_INTERNAL hipError_t launch_cumulate(int dtype, bool has_status, int nb, const int *methods, const void *const *in, const int32_t *const *st_in,
                                          void *const *out, int32_t *const *st_out, const CumulateView &v, hipStream_t stream);
 
+// ---- rolling-window aggregates along one axis (olap_rolling.hip, K14) ------------------------------
+// View [outer, K, inner]; the window of item k is [k - before, k + after] clipped to [0, K) and to k's group under the
+// K -> G map, which the device gets as it is (map == nullptr: one group).
+constexpr uint32_t kRollingInBytes = 16384;  // LDS of a tile's input rows (output rows + halo), and of its mask where primary
+constexpr uint32_t kRollingOutBytes = 8192;  // LDS of a tile's output rows (a choice, not a measurement)
+enum RollingForm { ROLLING_SERIES = 0, ROLLING_COLUMNS = 1, ROLLING_DIRECT = 2 };
+struct RollingView {
+  uint64_t outer, K, inner;
+  const uint32_t *map;    // device, [K], or nullptr
+  int64_t before, after;  // within [-K, K]; before + after >= 0
+  int def_nan;
+  int form;               // RollingForm
+  uint32_t series;        // tiled forms: series per tile (ROLLING_COLUMNS: 1)
+  uint32_t rows;          // output rows of K per tile
+  uint32_t cols;          // cells of `inner` per tile row (ROLLING_SERIES: inner)
+  uint32_t pitch;         // LDS cells between two series (ROLLING_SERIES) or two rows (ROLLING_COLUMNS) of the input tile
+};
+// chooses form and tile cuts from shape and window alone (cell_bytes: 4 or 8); before / after already within [-K, K]
+OLAP_INTERNAL void rolling_choose(RollingView &v, int cell_bytes);
+// nb <= 8 pairs of one cell type and default, a rule each (methods[k]); masks on all pairs or on none
+OLAP_INTERNAL hipError_t launch_rolling(int dtype, bool has_status, int nb, const int *methods, const void *const *in, const int32_t *const *st_in,
+                                        void *const *out, int32_t *const *st_out, const RollingView &v, hipStream_t stream);
+
 // ---- insertion order of tracked stores (olap_order.hip) --------------------------------------------
 OLAP_INTERNAL void order_free(olap_store *s);
 OLAP_INTERNAL int order_clone(const olap_store *from, olap_store *to);

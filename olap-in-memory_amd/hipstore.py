@@ -693,6 +693,29 @@ class HipStore:
         check(capi.lib().olap_store_cumulate_multi(n, hs, codes, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), ng, gp, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
+    def rolling(self, lens, axis, method, before, after=0, groups=None, n_groups=None):
+        """Rolling-window aggregate along dimension `axis` of the cube `lens` (olap_store_rolling_multi with one store): the
+        cell at item k holds dice(items of k's group in [k - before, k + after]) -> drillUp(rule); unset where no item is left."""
+        return HipStore.rolling_multi([self], [method], lens, axis, before, after, groups, n_groups)[0][0]
+
+    @staticmethod
+    def rolling_multi(stores, methods, lens, axis, before, after=0, groups=None, n_groups=None):
+        """Rolling-window aggregates of the stored measures of a cube, a rule each, in one call (olap_store_rolling_multi):
+        (new stores in order, kernel launches made).  `n_groups` defaults to max(groups) + 1."""
+        lv = _u32(lens)
+        n = len(stores)
+        hs, (outs, launches) = _handles(stores), _new_stores(n)
+        codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
+        if groups is None:
+            g, gp, ng = None, None, 1
+        else:
+            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
+            gp = g.ctypes.data_as(capi._pu32)
+            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        check(capi.lib().olap_store_rolling_multi(n, hs, codes, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), int(before), int(after), ng, gp,
+                                                  C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
 
 def blocks_report(stores, lens, scanned):
     """Cube.scan / iterateOverDimension for several measures of one cube in one device pass (olap_store_blocks_report):

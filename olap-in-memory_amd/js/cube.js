@@ -735,12 +735,38 @@ class Cube {
   }
 
   // ------------------------------------------------------------------ running aggregates
-  /** the checks cumulate and _cumulatePerItem share; returns the dimension's index */
-  _checkCumulate(dimensionId, attribute) {
+  /** the checks the calls along a dimension share (`what`: cumulate, rolling); returns the dimension's index */
+  _checkAlong(what, dimensionId, attribute) {
     const index = this.getDimensionIndex(dimensionId);
-    if (index === -1) throw new Error(`cumulate: no such dimension: ${dimensionId}`);
-    if (this.dimensions[index].attributes.indexOf(attribute) === -1) throw new Error(`cumulate: no such attribute: ${attribute} in dimension: ${dimensionId}`);
+    if (index === -1) throw new Error(`${what}: no such dimension: ${dimensionId}`);
+    if (this.dimensions[index].attributes.indexOf(attribute) === -1) throw new Error(`${what}: no such attribute: ${attribute} in dimension: ${dimensionId}`);
     return index;
+  }
+
+  _checkCumulate(dimensionId, attribute) {
+    return this._checkAlong('cumulate', dimensionId, attribute);
+  }
+
+  /**
+   * What cumulate and rolling share: the HipStore measures go through many(stores, rules) (null where it does not take
+   * one), the rest item by item through perItem(ids); HipStore[pathField] says what ran.
+   */
+  _alongDimension(dimensionId, pathField, many, perItem) {
+    const ids = this.storedMeasureIds;
+    const mine = ids.filter((id) => this.storedMeasures[id] instanceof HipStore);
+    const made = {};
+    HipStore[pathField] = 'per-item';
+    if (mine.length > 0) {
+      const results = many(mine.map((id) => this.storedMeasures[id]), mine.map((id) => (this.storedMeasuresRules[id] || {})[dimensionId]));
+      mine.forEach((id, i) => {
+        if (results[i]) made[id] = results[i];
+      });
+    }
+    const rest = ids.filter((id) => !made[id]);
+    const launches = HipStore.lastBatchLaunches;
+    const chains = rest.length > 0 ? perItem(rest) : null;
+    if (HipStore[pathField] === 'device') HipStore.lastBatchLaunches = launches; // (the chains count their own)
+    return this._derive(this.dimensions.slice(), (store, id) => made[id] || chains.storedMeasures[id]);
   }
 
   /**
@@ -759,22 +785,9 @@ class Cube {
   cumulate(dimensionId, attribute = 'all') {
     const index = this._checkCumulate(dimensionId, attribute);
     if (this.dimensions[index].rootAttribute === attribute) return this.clone(); // every group has one member
-    const ids = this.storedMeasureIds;
-    const mine = ids.filter((id) => this.storedMeasures[id] instanceof HipStore);
-    const made = {};
-    HipStore.lastCumulatePath = 'per-item';
-    if (mine.length > 0) {
-      const results = HipStore.cumulateMany(mine.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute,
-        mine.map((id) => (this.storedMeasuresRules[id] || {})[dimensionId]));
-      mine.forEach((id, i) => {
-        if (results[i]) made[id] = results[i];
-      });
-    }
-    const rest = ids.filter((id) => !made[id]);
-    const launches = HipStore.lastBatchLaunches;
-    const perItem = rest.length > 0 ? this._cumulatePerItem(dimensionId, attribute, rest) : null;
-    if (HipStore.lastCumulatePath === 'device') HipStore.lastBatchLaunches = launches; // (the chains count their own)
-    return this._derive(this.dimensions.slice(), (store, id) => made[id] || perItem.storedMeasures[id]);
+    return this._alongDimension(dimensionId, 'lastCumulatePath',
+      (stores, rules) => HipStore.cumulateMany(stores, this.dimensions, index, attribute, rules),
+      (rest) => this._cumulatePerItem(dimensionId, attribute, rest));
   }
 
   /**
@@ -802,6 +815,83 @@ class Cube {
     for (const id of ids) values[id] = new Array(outer * K * inner);
     for (let i = 0; i < K; ++i) {
       const members = items.filter((_, j) => j <= i && groups[j] === groups[i]);
+      const rolled = source.dice(dimensionId, current.rootAttribute, members).drillUp(dimensionId, attribute);
+      for (const id of ids) {
+        const cells = rolled.getData(id);
+        for (let o = 0; o < outer; ++o) for (let j = 0; j < inner; ++j) values[id][(o * K + i) * inner + j] = cells[o * inner + j];
+      }
+    }
+    return this._derive(this.dimensions.slice(), (store, id) => {
+      const rules = this.storedMeasuresRules[id];
+      const fresh = store instanceof HipStore ? this._newStore(store._type, store._defaultValue, rules) : new store.constructor(store.size, store._type, store._defaultValue);
+      fresh.data = values[id];
+      return fresh;
+    }, 'share', (id) => ids.includes(id));
+  }
+
+  // ------------------------------------------------------------------ rolling windows
+  /** the checks rolling and _rollingPerItem share; returns the dimension's index */
+  _checkRolling(dimensionId, before, after, attribute) {
+    const index = this._checkAlong('rolling', dimensionId, attribute);
+    if (!Number.isInteger(before) || !Number.isInteger(after)) throw new Error('rolling: before and after must be integers');
+    if (before + after < 0) throw new Error('rolling: empty window');
+    return index;
+  }
+
+  /**
+   * Rolling-window aggregates along one dimension (trailing-12-month totals, a 3-month moving average, a centred
+   * maximum): a new cube with the same dimensions, rules and computed measures in which every stored measure holds, at
+   * item i of `dimensionId` (all other coordinates fixed), what
+   *   this.dice(dimensionId, root, members).drillUp(dimensionId, attribute)
+   * holds in its single item of that dimension, `members` being the items j with i - before <= j <= i + after that
+   * exist and lie in i's group under `attribute` — by the measure's rule for that dimension.  'all' makes the whole
+   * dimension one group.  before and after are integers, either may be negative, before + after >= 0.  A window
+   * without members gives an unset cell.  Every window is folded afresh, its set members in ascending order; nothing
+   * is subtracted on the way.  This cube is untouched.
+   * The stored measures go to the device in one call (HipStore.rollingMany -> olap_store_rolling_multi, K14); the
+   * measures it does not take — order-tracking ones (a `first` / `last` rule), sharded ones, stores of another class —
+   * go item by item (_rollingPerItem, which is also the definition).  HipStore.lastRollingPath says what ran.
+   */
+  rolling(dimensionId, before, after = 0, attribute = 'all') {
+    const index = this._checkRolling(dimensionId, before, after, attribute);
+    return this._alongDimension(dimensionId, 'lastRollingPath',
+      (stores, rules) => HipStore.rollingMany(stores, this.dimensions, index, before, after, attribute, rules),
+      (rest) => this._rollingPerItem(dimensionId, before, after, attribute, rest));
+  }
+
+  /**
+   * Item i receives the cell of item i - offset when that item exists and lies in i's group under `attribute`, and is
+   * unset otherwise: last month's value beside this month's (offset 1), the same month a year ago (12), a lead
+   * (negative).  A window of one item, so the result is the same under every rule.
+   */
+  shift(dimensionId, offset, attribute = 'all') {
+    return this.rolling(dimensionId, offset, 0 - offset, attribute);
+  }
+
+  /**
+   * The definition of rolling, run as written: one dice -> drillUp chain per item of the dimension whose window has
+   * members (2 K launches per measure), assembled on the host as _cumulatePerItem does.  The path of the measures the
+   * device call does not take, and what the tests compare it with.
+   */
+  _rollingPerItem(dimensionId, before, after, attribute = 'all', measureIds = null) {
+    const index = this._checkRolling(dimensionId, before, after, attribute);
+    const current = this.dimensions[index];
+    const ids = measureIds || this.storedMeasureIds;
+    const source = new Cube(this.dimensions.slice());
+    for (const id of ids) {
+      source.storedMeasures[id] = this.storedMeasures[id];
+      source.storedMeasuresRules[id] = this.storedMeasuresRules[id];
+    }
+    const items = current.getItems();
+    const groups = current.getGroupIndexFromRootIndexMap(attribute);
+    const K = items.length;
+    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
+    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
+    const values = {};
+    for (const id of ids) values[id] = new Array(outer * K * inner).fill(this.storedMeasures[id]._defaultValue); // (an empty window: unset)
+    for (let i = 0; i < K; ++i) {
+      const members = items.filter((_, j) => j >= i - before && j <= i + after && groups[j] === groups[i]);
+      if (members.length === 0) continue;
       const rolled = source.dice(dimensionId, current.rootAttribute, members).drillUp(dimensionId, attribute);
       for (const id of ids) {
         const cells = rolled.getData(id);

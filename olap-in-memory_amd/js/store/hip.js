@@ -881,31 +881,20 @@ class HipStore {
    * item by item.  Sets HipStore.lastBatchLaunches and HipStore.lastCumulatePath ('device' when the call ran).
    */
   static cumulateMany(stores, dimensions, index, attribute, methods) {
-    const out = new Array(stores.length).fill(null);
-    const addon = backend.load();
-    HipStore.lastCumulatePath = 'per-item';
-    if (typeof addon.cumulateMulti !== 'function') return out;
-    HipStore.materializeMany(stores);
-    let launches = HipStore.lastBatchLaunches;
-    // (a selection alone in its group stays pending there: it is diced now, as the first read of its cells would)
-    for (const store of stores) {
-      if (store._pending && wholeUntracked(store._pending.source)) store._materialize();
-    }
-    const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
-    const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
-    const eligible = (i) => stores[i]._cells === cellTypeOf(stores[i]._type);
-    const run = (natives, together) => {
-      const codes = Int32Array.from(together, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
-      const launchesOut = new Int32Array(1);
-      const made = addon.cumulateMulti(natives, codes, lengthsOf(dimensions), index, groups, nGroups, launchesOut);
-      launches += launchesOut[0];
-      HipStore.lastCumulatePath = 'device';
-      return made;
-    };
-    // (togetherThenSingly sends two or more together; a measure alone among the eligible ones is a batch of one)
-    togetherThenSingly(stores, out, eligible, run, (store, i) => (wholeUntracked(heldStore(store)) && eligible(i) ? store._wrap(run([store._nativeStore], [i])[0]) : null));
-    HipStore.lastBatchLaunches = launches;
-    return out;
+    return alongMany(stores, dimensions, index, attribute, methods, 'cumulateMulti', 'lastCumulatePath',
+      (addon, natives, codes, lens, groups, nGroups, launchesOut) => addon.cumulateMulti(natives, codes, lens, index, groups, nGroups, launchesOut));
+  }
+
+  /**
+   * Rolling-window aggregates along dimension `index` of the stored measures of one cube, each by its own rule —
+   * Cube.rolling: the cell at item k holds what dice(items of k's group under `attribute` in [k - before, k + after])
+   * -> drillUp(rule) holds in its single item, and is unset where no item is left.  Eligibility, materializeMany, the
+   * ONE call (addon rollingMulti -> olap_store_rolling_multi; DESIGN.md §3 K14) and the nulls are cumulateMany's.
+   * Sets HipStore.lastBatchLaunches and HipStore.lastRollingPath ('device' when the call ran).
+   */
+  static rollingMany(stores, dimensions, index, before, after, attribute, methods) {
+    return alongMany(stores, dimensions, index, attribute, methods, 'rollingMulti', 'lastRollingPath',
+      (addon, natives, codes, lens, groups, nGroups, launchesOut) => addon.rollingMulti(natives, codes, lens, index, before, after, groups, nGroups, launchesOut));
   }
 
   /** in-memory.js:139-176 — mutates this store */
@@ -1089,6 +1078,41 @@ HipStore.lastComposeCalls = 0;
 // what the last Cube.cumulate did: 'device' when at least one measure left through cumulateMulti, 'per-item' when every
 // measure took the dice -> drillUp chain item by item (Cube._cumulatePerItem)
 HipStore.lastCumulatePath = null;
+// the same for the last Cube.rolling / Cube.shift (rollingMulti, Cube._rollingPerItem)
+HipStore.lastRollingPath = null;
+
+/**
+ * What cumulateMany and rollingMany share (`call`: the addon's many-call `name`): the measures held whole on one device,
+ * untracked and with cells of their declared type leave in ONE call; null for the others.  pathField: the HipStore
+ * field that says what ran.
+ */
+function alongMany(stores, dimensions, index, attribute, methods, name, pathField, call) {
+  const out = new Array(stores.length).fill(null);
+  const addon = backend.load();
+  HipStore[pathField] = 'per-item';
+  if (typeof addon[name] !== 'function') return out;
+  HipStore.materializeMany(stores);
+  let launches = HipStore.lastBatchLaunches;
+  // (a selection alone in its group stays pending there: it is diced now, as the first read of its cells would)
+  for (const store of stores) {
+    if (store._pending && wholeUntracked(store._pending.source)) store._materialize();
+  }
+  const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
+  const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
+  const eligible = (i) => stores[i]._cells === cellTypeOf(stores[i]._type);
+  const run = (natives, together) => {
+    const codes = Int32Array.from(together, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
+    const launchesOut = new Int32Array(1);
+    const made = call(addon, natives, codes, lengthsOf(dimensions), groups, nGroups, launchesOut);
+    launches += launchesOut[0];
+    HipStore[pathField] = 'device';
+    return made;
+  };
+  // (togetherThenSingly sends two or more together; a measure alone among the eligible ones is a batch of one)
+  togetherThenSingly(stores, out, eligible, run, (store, i) => (wholeUntracked(heldStore(store)) && eligible(i) ? store._wrap(run([store._nativeStore], [i])[0]) : null));
+  HipStore.lastBatchLaunches = launches;
+  return out;
+}
 // kernel launches reorderMulti reported for the last reorderMany (null: every measure took reorder one by one)
 HipStore.lastReorderLaunches = null;
 // 'device' after a getNestedObject(computed measure, withTotals) that ran as one olap_formula_totals call, and the

@@ -1270,6 +1270,39 @@ static napi_value CumulateMulti(napi_env env, napi_callback_info info) {
   return multi_done(env, rc, argc, argv, 6, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
+// rollingMulti(stores: Store[], methods: Int32Array, lens, axis: number, before: number, after: number, groups: Uint32Array | null, nGroups: number,
+//              launchesOut?) -> Store[]
+// Rolling-window aggregates along dimension `axis` (olap_store_rolling_multi): the window of item k is [k - before, k + after] within k's group.
+static napi_value RollingMulti(napi_env env, napi_callback_info info) {
+  const char *usage =
+      "rollingMulti(stores: Store[], methods: Int32Array, lens: Uint32Array, axis: number, before: number, after: number, groups: Uint32Array | null, "
+      "nGroups: number, launchesOut?: Int32Array)";
+  size_t argc = 9;
+  napi_value argv[9];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::vector<uint32_t> lens, groups;
+  MultiArgs m;
+  bool bad = true;
+  int32_t axis = -1, before = 0, after = 0;
+  uint32_t n_groups = 0;
+  napi_valuetype gt = napi_undefined;
+  if (argc < 8 || !get_u32_vec(env, argv[2], lens) || napi_get_value_int32(env, argv[3], &axis) != napi_ok ||
+      napi_get_value_int32(env, argv[4], &before) != napi_ok || napi_get_value_int32(env, argv[5], &after) != napi_ok ||
+      napi_typeof(env, argv[6], &gt) != napi_ok || napi_get_value_uint32(env, argv[7], &n_groups) != napi_ok)
+    return bad_args(env, usage);
+  const bool one_group = gt == napi_null || gt == napi_undefined;
+  if (!one_group && !get_u32_vec(env, argv[6], groups)) return bad_args(env, usage);
+  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
+  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "rollingMulti: one group per item of the dimension");
+  if (!m.decode(env, argv[0], &argv[1], &bad)) return m.miscounted ? bad_args(env, "rollingMulti: one method per store") : bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  static const uint32_t none = 0;
+  int launches = 0;
+  int rc = olap_store_rolling_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis,
+                                    before, after, n_groups, one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
+  return multi_done(env, rc, argc, argv, 8, launches) ? wrap_new_stores(env, outs) : nullptr;
+}
+
 // ---- ShardedStore: a measure split along dimension 0 over the devices of setDevices() -----------
 // Wraps olap_sharded_store* (include/olap_hip.h, "Multi-GPU").  Method names and argument shapes are
 // those of Store, so the JS HipStore drives either; what a sharded store cannot do in place throws an
@@ -1851,6 +1884,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"diceDrillUpMulti", nullptr, DiceDrillUpMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"cumulateMulti", nullptr, CumulateMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"rollingMulti", nullptr, RollingMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"heldBytes", nullptr, HeldBytes, nullptr, nullptr, nullptr, napi_default, nullptr},
