@@ -259,6 +259,12 @@ int olap_diag_write_ceiling(void *device, uint64_t bytes, void *stream);
  * between two rows of the tile).  `map` is a drillUp map as in olap_drillup_plan.  For tests of the planning code. */
 int olap_diag_tile_placement(int dtype, uint32_t K, uint32_t G, uint32_t inner, const uint32_t *map, uint32_t *cell_pos,
                              uint32_t *group_bounds, uint32_t *pitch);
+/* Diagnostic, host-only: what a plan decided, as one line of key=value pairs (no pointers), at most cap - 1 characters.
+ * A one-axis drillUp plan tells its kind, the form it runs in over 16-byte-aligned buffers (rows, rows_ragged, tile,
+ * gtile, flat, segments, reduce4, reduce, split4, split), vec, outer K G inner, contiguous, perm_pitch, n_gtile, min_group,
+ * longest_group, the reduce regime's S (and, where it is not 0, unit rows seg_len vec4 edge), the segmented rows' S_tot
+ * and, for the tile form, its mode, rows per tile and LDS bytes.  Every other plan tells its kind and kernel name. */
+int olap_diag_plan_describe(const olap_plan *plan, char *buf, size_t cap);
 /* `total` getter (in-memory.js:22-28): float64 sum of the set cells, and their count.
  * Synchronises `stream`. */
 int olap_total(const void *values, const int32_t *status, uint64_t n, int dtype, int default_kind,

@@ -62,6 +62,7 @@ SIGNATURES = {
     "olap_plan_in_cells": (_u64, [_vp]),
     "olap_plan_out_cells": (_u64, [_vp]),
     "olap_plan_kernel_name": (C.c_char_p, [_vp]),
+    "olap_diag_plan_describe": (_i32, [_vp, C.c_char_p, _sz]),
     "olap_plan_run": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "olap_diag_tile_placement": (_i32, [_i32, C.c_uint32, C.c_uint32, C.c_uint32, _pu32, _pu32, _pu32, _pu32]),
     "olap_plan_run_batch": (_i32, [_vp, _i32, _pvp, _pvp, _pvp, _pvp, _vp]),

@@ -19,6 +19,7 @@
 
 #include "olap_internal.hpp"
 #include "olap_kernels.hpp"
+#include "olap_plan.hpp"
 
 using namespace olap;
 
@@ -54,7 +55,7 @@ int hip_fail(hipError_t e, const char *what) {
 // and olap_plan_run refuses to launch.  A diagnostic (which kernel would a query take?) and the way the
 // planning code (CSR, tile cuts, remap and brick tables) runs under AddressSanitizer / UBSan on a machine
 // without a GPU (tests/test_capi_nogpu.py, tools/asan_host.sh).  Never a compute path.
-static bool plan_dry() {
+bool plan_dry() {
   static const bool dry = getenv("OLAP_PLAN_DRY") != nullptr;
   return dry;
 }
@@ -228,56 +229,13 @@ extern "C" int olap_device_synchronize(void) {
 }
 
 // ------------------------------------------------------------------ plans
-enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE, PLAN_ROLLING };
-
-struct olap_plan {
-  PlanKind kind;
-  int dtype = 0, def_nan = 0, his_def_nan = 0, method = 0;
-  int his_dtype = -1;                      // load between cell types: the other store's (>= 0 and != dtype: load_convert kernels)
-  uint64_t in_cells = 0, out_cells = 0;
-  int vec = 1;
-  DrillUpAxis axis{};
-  DrillUpGeneric gen{};
-  Remap remap{};
-  DrillDown dd{};
-  DrillDownScale dds{};
-  Brick brick{};
-  uint64_t n_bricks = 0;
-  GatherReduce gr{};
-  CumulateView cum{};                      // PLAN_CUMULATE (olap_cumulate.hip)
-  RollingView roll{};                      // PLAN_ROLLING (olap_rolling.hip)
-  bool xy_ok = false;                      // reorder without a mask: two-axis LDS transpose (olap_transpose.hip; 4- and 8-byte cells)
-  TransposeXY xy{};
-  DrillUpReduce reduce{};                  // S > 0: reduce regime of the one-axis drillUp
-  LoadPermute lperm{};                     // lperm.perm != nullptr: load whose innermost items are permuted, nothing else (load_permute_rows_kernel)
-  SegmentedRows seg{};                     // S_tot > 0: wide rows of that regime run as the row kernel over segments + a fold (all rules but product)
-  bool dd_two_pass = false;                // float cells, no distributions: scale + broadcast
-  bool dice_direct = false;                // dice of one dimension, rows not whole 16-byte groups: dice_direct_kernel
-  DiceRows dice_rows{};
-  bool dd_rows = false;                    // one refined axis, wide rows: drilldown_rows_kernel (uses `axis`)
-  uint32_t dd_longest = 0;                 // children of the largest parent
-  void *dev_tab2 = nullptr;                // second table set (two-pass drillDown)
-  void *dev_tmp = nullptr;                 // quotients of the two-pass drillDown (old cells)
-  std::vector<void *> owned;               // further device allocations freed with the plan
-  void *dev_tab = nullptr;                 // index tables
-  double *dev_dist = nullptr;              // drillDown distributions
-  unsigned long long *dev_err = nullptr;   // drillDown deferred error word
-  std::string kernel_name;
-  hipStream_t last_stream = nullptr;
-  bool ran = false;
-  int device = 0;                          // the device the tables and scratch live on (current at creation)
-  olap_plan() { (void)hipGetDevice(&device); }
-  int cache_refs = 0;                      // handle-layer LRU: users between find() and release() (guarded by the cache lock)
-  bool cache_evicted = false;              // evicted while in use: the last release() destroys it
-};
-
-static uint64_t product(const uint32_t *v, int n) {
+uint64_t product(const uint32_t *v, int n) {
   uint64_t p = 1;
   for (int i = 0; i < n; ++i) p *= v[i];
   return p;
 }
 
-static int check_dims(int ndim, const uint32_t *a, const uint32_t *b) {
+int check_dims(int ndim, const uint32_t *a, const uint32_t *b) {
   if (ndim < 0 || ndim > OLAP_MAX_DIMS) return fail(OLAP_ERR_INVALID_ARGUMENT, "ndim %d out of range [0, %d]", ndim, OLAP_MAX_DIMS);
   if (ndim > 0 && (!a || !b)) return fail(OLAP_ERR_INVALID_ARGUMENT, "dimension length vectors must not be NULL");
   // 2^40 cells (4 TiB of float32) is far beyond one device; it also keeps index math in range
@@ -290,7 +248,7 @@ static int check_dims(int ndim, const uint32_t *a, const uint32_t *b) {
   return OLAP_OK;
 }
 
-static int upload(void **dev, const void *host, size_t bytes) {
+int upload(void **dev, const void *host, size_t bytes) {
   *dev = nullptr;
   if (bytes == 0) bytes = 16;
   HIP_TRY(dev_alloc(dev, bytes));
@@ -299,7 +257,7 @@ static int upload(void **dev, const void *host, size_t bytes) {
   return OLAP_OK;
 }
 
-static int vec_for(int dtype, uint64_t contiguous) {
+int vec_for(int dtype, uint64_t contiguous) {
   const int maxv = dtype == OLAP_FLOAT64 ? 2 : 4;  // 16 B per lane
   for (int v = maxv; v > 1; v >>= 1)
     if (contiguous % (uint64_t)v == 0) return v;
@@ -330,7 +288,7 @@ extern "C" uint64_t olap_plan_in_cells(const olap_plan *p) { return p ? p->in_ce
 extern "C" uint64_t olap_plan_out_cells(const olap_plan *p) { return p ? p->out_cells : 0; }
 extern "C" const char *olap_plan_kernel_name(const olap_plan *p) { return p ? p->kernel_name.c_str() : ""; }
 
-static bool is_identity_u32(const uint32_t *m, uint32_t old_len, uint32_t new_len) {
+bool is_identity_u32(const uint32_t *m, uint32_t old_len, uint32_t new_len) {
   if (old_len != new_len) return false;
   for (uint32_t k = 0; k < old_len; ++k)
     if (m[k] != k) return false;
@@ -338,379 +296,13 @@ static bool is_identity_u32(const uint32_t *m, uint32_t old_len, uint32_t new_le
 }
 
 // CSR of a K->G map: members of each group in ascending order (counting sort, stable)
-static void build_csr(const uint32_t *m, uint32_t K, uint32_t G, std::vector<uint32_t> &gstart, std::vector<uint32_t> &order) {
+void build_csr(const uint32_t *m, uint32_t K, uint32_t G, std::vector<uint32_t> &gstart, std::vector<uint32_t> &order) {
   gstart.assign((size_t)G + 1, 0);
   for (uint32_t k = 0; k < K; ++k) gstart[m[k] + 1]++;
   for (uint32_t g = 0; g < G; ++g) gstart[g + 1] += gstart[g];
   order.resize(K);
   std::vector<uint32_t> cur(gstart.begin(), gstart.end() - 1);
   for (uint32_t k = 0; k < K; ++k) order[cur[m[k]]++] = k;
-}
-
-// ---- drillUp ------------------------------------------------------------------------------
-extern "C" int olap_drillup_plan(olap_plan **out, int dtype, int default_kind, int method, int ndim,
-                                 const uint32_t *old_len, const uint32_t *new_len,
-                                 const uint32_t *const *maps) {
-  if (!out) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan out-pointer is NULL");
-  *out = nullptr;
-  int rc;
-  if ((rc = check_dtype(dtype)) || (rc = check_default(default_kind))) return rc;
-  if (method < OLAP_SUM || method > OLAP_PARTIAL_AVERAGE)
-    return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", method);
-  if ((rc = check_dims(ndim, old_len, new_len))) return rc;
-  if (ndim > 0 && !maps) return fail(OLAP_ERR_INVALID_ARGUMENT, "maps is NULL");
-  std::vector<bool> ident(ndim);
-  int n_changed = 0, changed = -1;
-  for (int d = 0; d < ndim; ++d) {
-    if (old_len[d] && !maps[d]) return fail(OLAP_ERR_INVALID_ARGUMENT, "maps[%d] is NULL", d);
-    for (uint32_t k = 0; k < old_len[d]; ++k)
-      if (maps[d][k] >= new_len[d])
-        return fail(OLAP_ERR_INDEX_RANGE, "drillUp map of dimension %d: entry %u = %u is outside the new dimension (%u items)", d, k, maps[d][k], new_len[d]);
-    ident[d] = is_identity_u32(maps[d], old_len[d], new_len[d]);
-    if (!ident[d]) {
-      ++n_changed;
-      changed = d;
-    }
-  }
-  if ((rc = require_device())) return rc;
-
-  olap_plan *p = new (std::nothrow) olap_plan();
-  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
-  p->dtype = dtype;
-  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
-  p->method = method;
-  p->in_cells = product(old_len, ndim);
-  p->out_cells = product(new_len, ndim);
-
-  if (n_changed <= 1) {
-    // One changed axis (or none: then the whole cube is a single untouched "axis" of length 1).
-    p->kind = PLAN_DRILLUP_AXIS;
-    DrillUpAxis &a = p->axis;
-    std::vector<uint32_t> gstart, order;
-    if (n_changed == 1) {
-      a.outer = product(old_len, changed);
-      a.K = old_len[changed];
-      a.G = new_len[changed];
-      a.inner = product(old_len + changed + 1, ndim - changed - 1);
-      build_csr(maps[changed], old_len[changed], new_len[changed], gstart, order);
-    } else {
-      a.outer = 1;
-      a.K = 1;
-      a.G = 1;
-      a.inner = p->in_cells;
-      gstart = {0, 1};
-      order = {0};
-    }
-    bool contiguous = true;
-    for (size_t j = 0; j < order.size(); ++j)
-      if (order[j] != j) contiguous = false;
-    p->vec = vec_for(dtype, a.inner);
-    a.def_nan = p->def_nan;
-    a.min_group = 0;
-    a.depth = 0;
-    std::vector<uint32_t> tab(gstart);
-    const size_t order_off = tab.size();
-    if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
-    if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) {
-      olap_plan_destroy(p);
-      return rc;
-    }
-    a.gstart = (const uint32_t *)p->dev_tab;
-    a.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
-    // row-tile regime with interleaved groups (drillup_tile_kernel MODE 3): where every cell of a row goes in
-    // the permuted tile
-    a.perm_cell = a.perm_grp = nullptr;
-    a.perm_pitch = 0;
-    {
-      const uint64_t budget = kTileBytes / olap_dtype_size(dtype);
-      if (!contiguous && a.inner > 0 && a.inner < 4096 && a.K * a.inner <= budget) {
-        TilePerm tp;
-        tile_perm_build(gstart.data(), order.data(), (uint32_t)a.K, (uint32_t)a.G, (uint32_t)a.inner, budget, 16 / olap_dtype_size(dtype), &tp);
-        std::vector<uint32_t> both(tp.cell);
-        both.insert(both.end(), tp.grp.begin(), tp.grp.end());
-        void *dev_perm = nullptr;
-        if ((rc = upload(&dev_perm, both.data(), both.size() * sizeof(uint32_t)))) {
-          olap_plan_destroy(p);
-          return rc;
-        }
-        p->owned.push_back(dev_perm);
-        a.perm_cell = (const uint32_t *)dev_perm;
-        a.perm_grp = (const uint32_t *)dev_perm + tp.cell.size();
-        a.perm_pitch = tp.pitch;
-      }
-    }
-    // group-tile regime (drillup_gtile_kernel): contiguous groups, short row pieces, rows too long for
-    // the row-tile regime; the group list is cut into tiles of whole groups that fit kTileBytes
-    bool gtile_ok = false;
-    a.gtile = nullptr;
-    a.n_gtile = 0;
-    {
-      const uint64_t budget = kTileBytes / olap_dtype_size(dtype);
-      const uint64_t vcells = 16 / olap_dtype_size(dtype);
-      uint64_t gtile_max_slots = 128;
-      if (const char *e = getenv("OLAP_GTILE_MAX_SLOTS")) gtile_max_slots = (uint64_t)atoll(e);  // developer knob
-      if (contiguous && a.G > 1 && a.inner > 0 && a.inner / (uint64_t)p->vec < gtile_max_slots && a.K * a.inner > budget && !getenv("OLAP_NO_GTILE")) {
-        std::vector<uint32_t> cut{0};
-        uint64_t cells = 0;
-        uint32_t groups = 0;
-        bool fits = true;
-        for (uint32_t g = 0; g < a.G && fits; ++g) {
-          const uint64_t c = (uint64_t)(gstart[g + 1] - gstart[g]) * a.inner;
-          if (c > budget - vcells) fits = false;
-          if (cells + c > budget - vcells || groups == kGroupTileMaxGroups) {
-            cut.push_back(g);
-            cells = 0;
-            groups = 0;
-          }
-          cells += c;
-          ++groups;
-        }
-        cut.push_back((uint32_t)a.G);
-        // a tile reduces groups-in-tile x inner output cells, one lane each: with a long group or two
-        // per tile most of the workgroup idles and the flat form is faster ([3001,3333,10] -> 11 groups
-        // of 303 members: 145 us here, 89 us flat) — unless every group is long enough for several lanes to share an
-        // output cell (>= 256 members: the kernel's cooperative form)
-        uint32_t shortest = ~0u;
-        for (uint32_t g = 0; g < a.G; ++g) shortest = std::min(shortest, gstart[g + 1] - gstart[g]);
-        const bool coop = shortest >= 256 && !getenv("OLAP_GTILE_NO_COOP");  // (whatever the rule: a plan's tables do not depend on it)
-        // (short groups too: a lane's work is its group's members, so a tile with few output cells is cheap when those are
-        // few — day -> month over 8-byte cells with the day innermost: 67 months per tile, 31 LDS reads each; 320 us flat)
-        uint32_t longest_group = 0;
-        for (uint32_t g = 0; g < a.G; ++g) longest_group = std::max(longest_group, gstart[g + 1] - gstart[g]);
-        const bool enough_lanes = a.G * a.inner >= 64 * (cut.size() - 1) || coop || longest_group <= 64;
-        if (fits && enough_lanes && a.outer * (cut.size() - 1) < 0x7FFFFFFFull) {
-          void *dev_cut = nullptr;
-          if ((rc = upload(&dev_cut, cut.data(), cut.size() * sizeof(uint32_t)))) {
-            olap_plan_destroy(p);
-            return rc;
-          }
-          p->owned.push_back(dev_cut);
-          a.gtile = (const uint32_t *)dev_cut;
-          a.n_gtile = (uint32_t)(cut.size() - 1);
-          a.min_group = coop ? shortest : 0;
-          gtile_ok = true;
-        }
-      }
-    }
-    // few output cells and long groups: cooperative reduction of S segments per group (workspace
-    // in the plan), see DrillUpReduce
-    {
-      uint32_t longest = 0;
-      for (size_t gi = 0; gi + 1 < gstart.size(); ++gi) longest = std::max(longest, gstart[gi + 1] - gstart[gi]);
-      const uint64_t cells = a.outer * a.G * a.inner;
-      // (a wavefront per 271-cell row was tried for more outputs than this: 260 us against the tile's 103)
-      uint64_t reduce_max_cells = 131072;
-      if (const char *e = getenv("OLAP_REDUCE_MAX_CELLS")) reduce_max_cells = (uint64_t)atoll(e);  // developer / test knob: who takes small outputs
-      if (cells > 0 && cells < reduce_max_cells && longest >= 256) {
-        DrillUpReduce &rd = p->reduce;
-        uint64_t S;
-        // (rows of up to 1 024 four-byte cells too when the 16-byte form below applies — one contiguous '-> all' group
-        // whose steps are whole 16-byte groups: a unit then streams its segment as ONE contiguous range, 1-7 rows per
-        // step, where the lane-per-cell split form reads 4 KB pieces a row apart: [4e5,250] -> [1,250] 88 us -> see DESIGN K1r)
-        // (V = cells per 16 bytes; the smallest whole number of rows that is whole 16-byte groups must fit a unit's lanes)
-        const uint64_t V16 = 16 / olap_dtype_size(dtype);
-        uint64_t rows_min = 1;
-        while ((rows_min * a.inner) % V16 != 0) rows_min *= 2;
-        const bool wide16 = a.inner > 128 && rows_min * a.inner <= (uint64_t)kBlock * V16 && contiguous && a.G == 1 && (a.K * a.inner) % V16 == 0 &&
-                            !getenv("OLAP_REDUCE_NO_WIDE");
-        if (a.inner <= 128 || wide16) {
-          const uint64_t groups = a.outer * a.G;
-          // Segments per group.  More, shorter segments lose to the per-unit epilogue and to the partials they write
-          // and the merge reads back ([1e6,100] -> [1,100] with 4 096 units: 81 us; with 512: 65 us); fewer leave CUs
-          // idle.  Workgroup-sized units are few enough to be resident all at once, so what matters is that every CU gets
-          // the same number: k per CU for the smallest k in 2..8 that the groups fill to >= 94 % (1 per CU is slower:
-          // 84-100 us); with more groups than that the dispatcher balances ~4 K units by itself (tools/reduce_units.py).
-          uint64_t by_grid = (4096 + groups - 1) / groups;
-          if (const char *e = getenv("OLAP_REDUCE_UNITS")) {
-            by_grid = std::max<uint64_t>(1, (uint64_t)atoll(e) / groups);
-          } else {
-            int cus = 256;
-            if (!plan_dry()) {
-              int dev = 0, n = 0;
-              if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-            }
-            for (uint64_t k = 2; k <= 8; ++k) {
-              const uint64_t total = (uint64_t)cus * k, s_k = total / groups;
-              if (s_k >= 1 && groups * s_k * 100 >= total * 94) {
-                by_grid = s_k;
-                break;
-              }
-            }
-          }
-          const uint64_t by_work = std::max<uint64_t>(1, (uint64_t)longest * a.inner / 8192);  // >= 8 K cells each
-          S = std::max<uint64_t>(1, std::min(by_grid, by_work));
-          // short segments: a wavefront per segment; long ones: the whole workgroup
-          const uint64_t seg_cells = ((uint64_t)longest + S - 1) / S * a.inner;
-          rd.unit = (seg_cells <= 16384 && a.inner <= 64) ? 64 : kBlock;
-          uint32_t rows = 1;
-          while (rows * 2 * a.inner <= (uint64_t)rd.unit) rows *= 2;
-          rd.rows = rows;
-          // 16 B form: one contiguous '-> all' group, whole rows and segments in multiples of 4 cells
-          uint64_t seg_len = ((uint64_t)longest + S - 1) / S;
-          seg_len = (seg_len + 3) & ~3ull;
-          // rows per step: a power of two whose cells are whole 16-byte groups (4-byte cells: 1 for rows of a multiple of 4
-          // cells, 2 for even rows, 4 otherwise; 8-byte cells: 1 for even rows, 2 otherwise), doubled while the unit's lanes hold them
-          uint32_t rows4 = (uint32_t)rows_min;
-          while ((uint64_t)rows4 * 2 * a.inner <= (uint64_t)rd.unit * V16) rows4 *= 2;
-          if (rows4 < V16 && a.inner <= 128) rows4 = (uint32_t)V16;  // (narrow rows: as before)
-          if (contiguous && a.G == 1 && (a.K * a.inner) % V16 == 0 && (uint64_t)rows4 * a.inner <= (uint64_t)rd.unit * V16) {
-            // as many rows per step as the unit's lanes hold (whole 16-byte groups): 10 rows of 100 cells fill 250 of 256
-            // lanes where the power of two below fills 200; the rows are then merged through LDS instead of lane to lane
-            uint64_t rows_any = (uint64_t)rd.unit * V16 / a.inner;
-            while (rows_any > rows4 && (rows_any * a.inner) % V16 != 0) --rows_any;
-            if (a.inner * 2 > V16 && rows_any * 10 >= (uint64_t)rows4 * 11 && !getenv("OLAP_REDUCE_POW2_ROWS")) rows4 = (uint32_t)rows_any;
-            rd.vec4 = 1;
-            rd.rows = rows4;
-            rd.seg_len = (uint32_t)seg_len;
-          } else if (contiguous && a.G == 1 && a.inner == 1) {
-            // rows at any cell offset: aligned 16-byte groups with masked ends (every lane of the unit busy)
-            rd.vec4 = 1;
-            rd.edge = 1;
-            rd.rows = rd.unit * (uint32_t)V16;
-            rd.seg_len = (uint32_t)seg_len;
-          }
-        } else {
-          rd.rows = 0;
-          rd.unit = kBlock;
-          S = std::max<uint64_t>(1, std::min<uint64_t>((524288 + cells - 1) / cells, longest / 32));
-          // 16-byte lanes (drillup_split4_kernel): four output cells per lane; as many segments as give every CU the same
-          // number of workgroups (k per CU, smallest k in 2..8 filled to >= 94 %), each of at least 32 members
-          if (olap_dtype_size(dtype) == 4 && a.inner % 4 == 0 && !getenv("OLAP_NO_SPLIT4")) {
-            rd.vec4 = 1;
-            int cus = 256;
-            if (!plan_dry()) {
-              int dev = 0, n = 0;
-              if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-            }
-            const uint64_t lanes_per_seg = cells / 4;
-            uint64_t s_bal = 0;
-            for (uint64_t k = 2; k <= 8 && !s_bal; ++k) {
-              const uint64_t total = (uint64_t)cus * k * kBlock, s_k = total / lanes_per_seg;
-              if (s_k >= 1 && lanes_per_seg * s_k * 100 >= total * 94) s_bal = s_k;
-            }
-            if (!s_bal) s_bal = std::max<uint64_t>(1, (uint64_t)cus * 8 * kBlock / lanes_per_seg);
-            if (const char *e = getenv("OLAP_SPLIT_K")) s_bal = std::max<uint64_t>(1, (uint64_t)cus * (uint64_t)atoll(e) * kBlock / lanes_per_seg);  // developer knob: workgroups per CU
-            S = std::max<uint64_t>(1, std::min<uint64_t>(s_bal, longest / 32));
-          }
-        }
-        if (rd.rows == 0 && !plan_dry() && !getenv("OLAP_NO_SEGMENTED_ROWS") && a.inner / (uint64_t)p->vec >= 128 && a.inner * olap_dtype_size(dtype) >= 2048) {
-          // Wide rows (beyond the cooperative forms): the row kernel over SEGMENTS of the groups + a fold (see
-          // SegmentedRows) — as many segments as give the chip ~8 workgroups per CU, at least 16 members each.
-          int cus = 256;
-          {
-            int dev = 0, n = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-          }
-          const uint64_t n_vec = a.inner / (uint64_t)p->vec, bpr = (n_vec + kBlock - 1) / kBlock;
-          // (two workgroups per CU with four rows in flight per lane: [1e4,1e4] -> [1,1e4] 62.9 us; eight per CU with one
-          // row in flight, as the plain row regime runs: 75-77 us — four times the partials to write and to fold)
-          uint64_t per_cu = 2;
-          if (const char *e = getenv("OLAP_SEG_WG_PER_CU")) per_cu = std::max<uint64_t>(1, (uint64_t)atoll(e));  // developer knob
-          const uint64_t want = std::max<uint64_t>(1, (uint64_t)cus * per_cu / std::max<uint64_t>(1, a.outer * bpr));
-          const uint64_t seg_len = std::max<uint64_t>(16, (a.K + want - 1) / want);
-          std::vector<uint32_t> sg_gstart{0}, sg_first{0};
-          for (uint64_t gi = 0; gi < a.G; ++gi) {
-            for (uint64_t j = gstart[gi]; j < gstart[gi + 1]; j += seg_len) sg_gstart.push_back((uint32_t)std::min<uint64_t>(j + seg_len, gstart[gi + 1]));
-            sg_first.push_back((uint32_t)sg_gstart.size() - 1);
-          }
-          const uint64_t s_tot = sg_gstart.size() - 1;
-          void *d_g = nullptr, *d_f = nullptr, *d_p = nullptr, *d_a = nullptr;
-          if (s_tot > a.G && a.outer * s_tot * bpr < 0x7FFFFFFFull && !(rc = upload(&d_g, sg_gstart.data(), sg_gstart.size() * 4)) &&
-              !(rc = upload(&d_f, sg_first.data(), sg_first.size() * 4))) {
-            hipError_t e1 = dev_alloc(&d_p, a.outer * s_tot * a.inner * sizeof(double));
-            if (e1 == hipSuccess) e1 = dev_alloc(&d_a, a.outer * s_tot * a.inner * sizeof(int32_t));
-            if (e1 == hipSuccess) {
-              p->seg.S_tot = (uint32_t)s_tot;
-              p->seg.gstart = (const uint32_t *)d_g;
-              p->seg.seg_start = (const uint32_t *)d_f;
-              p->seg.partial = d_p;
-              p->seg.aux = (int32_t *)d_a;
-            } else {
-              (void)hipGetLastError();  // no room for the partials: the split forms below need less
-            }
-          }
-          for (void *q : {d_g, d_f, d_p, d_a})
-            if (q) p->owned.push_back(q);
-          if (rc) {
-            olap_plan_destroy(p);
-            return rc;
-          }
-        }
-        rd.S = (uint32_t)S;
-        if (!rd.vec4 || rd.rows == 0) rd.seg_len = (uint32_t)((longest + S - 1) / S);
-        hipError_t e = dev_alloc(&p->dev_tmp, cells * S * sizeof(Partial));
-        if (e != hipSuccess) {
-          olap_plan_destroy(p);
-          return hip_fail(e, "hipMalloc(drillUp reduce workspace)");
-        }
-        rd.part = (Partial *)p->dev_tmp;
-      }
-    }
-    if (p->seg.S_tot > 0 && method != OLAP_PRODUCT && method != OLAP_PARTIAL_AVERAGE)
-      p->kernel_name = "drillup_rows_kernel (segments)+segments_combine_kernel";
-    else if (p->reduce.S > 0)
-      p->kernel_name = p->reduce.rows == 0 ? (p->reduce.vec4 ? "drillup_split4_kernel+drillup_merge_kernel" : "drillup_split_kernel+drillup_merge_kernel")
-                       : p->reduce.vec4    ? (p->reduce.S == 1 ? "drillup_reduce4_kernel" : "drillup_reduce4_kernel+drillup_merge_kernel")
-                                           : "drillup_reduce_kernel+drillup_merge_kernel";
-    else if (gtile_ok) p->kernel_name = "drillup_gtile_kernel";
-    else if (a.inner / (uint64_t)p->vec >= 128) p->kernel_name = "drillup_rows_kernel";
-    else if (a.inner < 128 && a.K * a.inner <= (16 * 1024) / olap_dtype_size(dtype) && a.K * a.inner > 0 &&
-             (a.perm_cell && !getenv("OLAP_TILE_NO_PERMUTE") ? 2 * a.G : a.G + 1 + (contiguous ? 0 : a.K)) * 4 <= 16 * 1024)
-      p->kernel_name = "drillup_tile_kernel";  // (the launcher re-checks alignment; may still pick the flat form)
-    else p->kernel_name = "drillup_flat_kernel";
-  } else {
-    p->kind = PLAN_DRILLUP_GENERIC;
-    DrillUpGeneric &g = p->gen;
-    std::vector<uint32_t> tab;
-    std::vector<uint64_t> old_stride(ndim);
-    {
-      uint64_t s = 1;
-      for (int d = ndim - 1; d >= 0; --d) {
-        old_stride[d] = s;
-        s *= old_len[d];
-      }
-    }
-    int nd = 0;
-    for (int d = 0; d < ndim; ++d) {
-      if (ident[d] && nd > 0 && g.csr[nd - 1] < 0 && ident[d - 1]) {
-        // merge with the previous identity dim
-        g.new_len[nd - 1] *= new_len[d];
-        g.old_stride[nd - 1] = old_stride[d];
-        continue;
-      }
-      if (nd == kMaxDims) {
-        olap_plan_destroy(p);
-        return fail(OLAP_ERR_INVALID_ARGUMENT, "drillUp: more than %d non-mergeable dimensions", kMaxDims);
-      }
-      g.new_len[nd] = new_len[d];
-      g.old_stride[nd] = old_stride[d];
-      if (ident[d]) {
-        g.csr[nd] = -1;
-        g.ord[nd] = -1;
-      } else {
-        std::vector<uint32_t> gstart, order;
-        build_csr(maps[d], old_len[d], new_len[d], gstart, order);
-        const uint32_t ord_base = (uint32_t)(tab.size() + gstart.size());
-        g.csr[nd] = (int32_t)tab.size();
-        g.ord[nd] = 0;  // gstart entries index straight into `tab` (absolute)
-        for (auto &x : gstart) x += ord_base;
-        tab.insert(tab.end(), gstart.begin(), gstart.end());
-        tab.insert(tab.end(), order.begin(), order.end());
-      }
-      ++nd;
-    }
-    g.nd = nd;
-    g.total = p->out_cells;
-    g.def_nan = p->def_nan;
-    if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) {
-      olap_plan_destroy(p);
-      return rc;
-    }
-    g.tab = (const uint32_t *)p->dev_tab;
-    p->kernel_name = "drillup_generic_kernel";
-  }
-  *out = p;
-  return OLAP_OK;
 }
 
 // ---- shared: build a Remap over destination dims -------------------------------------------
@@ -776,7 +368,8 @@ extern "C" int olap_dice_plan(olap_plan **out, int dtype, int default_kind, int 
         return fail(OLAP_ERR_INDEX_RANGE, "dice selection of dimension %d: entry %u = %d is outside the old dimension (%u items)", d, j, sel[d][j], old_len[d]);
   }
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_GATHER;
   p->dtype = dtype;
@@ -806,10 +399,7 @@ extern "C" int olap_dice_plan(olap_plan **out, int dtype, int default_kind, int 
     }
     stride *= old_len[d];
   }
-  if ((rc = finish_remap(p, dims, p->out_cells, true))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = finish_remap(p, dims, p->out_cells, true))) return rc;
   p->kernel_name = "gather(dice)";
   // One diced dimension over rows that are not whole 16-byte groups (cubes with odd extents): the gather would move
   // 4 bytes per lane; dice_direct_kernel writes aligned 16-byte groups of the (contiguous) result and fetches each
@@ -843,10 +433,7 @@ extern "C" int olap_dice_plan(olap_plan **out, int dtype, int default_kind, int 
         for (uint32_t j = 0; j < K; ++j)
           if (sel[axis][j] >= 0 && last[sel[axis][j]] == (int64_t)j) eff[j] = sel[axis][j];
         void *dev = nullptr;
-        if ((rc = upload(&dev, eff.data(), eff.size() * sizeof(int32_t)))) {
-          olap_plan_destroy(p);
-          return rc;
-        }
+        if ((rc = upload(&dev, eff.data(), eff.size() * sizeof(int32_t)))) return rc;
         p->owned.push_back(dev);
         rows.sel = (const int32_t *)dev;
         p->dice_rows = rows;
@@ -855,7 +442,7 @@ extern "C" int olap_dice_plan(olap_plan **out, int dtype, int default_kind, int 
       }
     }
   }
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -894,7 +481,8 @@ extern "C" int olap_dice_drillup_plan(olap_plan **out, int dtype, int default_ki
     if (ndim == 0) return olap_dice_plan(out, dtype, default_kind, ndim, old_len, mid_len, sel);
   }
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_GATHER_REDUCE;
   p->dtype = dtype;
@@ -951,10 +539,7 @@ extern "C" int olap_dice_drillup_plan(olap_plan **out, int dtype, int default_ki
       dims.push_back(rd);
     }
   }
-  if ((int)dims.size() > kMaxDims) {
-    olap_plan_destroy(p);
-    return fail(OLAP_ERR_INVALID_ARGUMENT, "more than %d non-mergeable dimensions", kMaxDims);
-  }
+  if ((int)dims.size() > kMaxDims) return fail(OLAP_ERR_INVALID_ARGUMENT, "more than %d non-mergeable dimensions", kMaxDims);
   GatherReduce &g = p->gr;
   Remap &r = g.r;
   std::vector<int64_t> tab;
@@ -991,19 +576,13 @@ extern "C" int olap_dice_drillup_plan(olap_plan **out, int dtype, int default_ki
   r.total = p->out_cells / (uint64_t)p->vec;
   r.def_nan = p->def_nan;
   r.src_def_nan = p->def_nan;
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(int64_t)))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(int64_t)))) return rc;
   r.tab = (const int64_t *)p->dev_tab;
   g.member_off = r.tab + member_at;
-  if ((rc = upload(&p->dev_tab2, gstart.data(), gstart.size() * sizeof(uint32_t)))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = upload(&p->dev_tab2, gstart.data(), gstart.size() * sizeof(uint32_t)))) return rc;
   g.gstart = (const uint32_t *)p->dev_tab2;
   p->kernel_name = "gather_reduce_kernel";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -1023,7 +602,8 @@ extern "C" int olap_reorder_plan(olap_plan **out, int dtype, int default_kind, i
     seen[perm[d]] = true;
   }
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_GATHER;
   p->dtype = dtype;
@@ -1321,10 +901,7 @@ extern "C" int olap_reorder_plan(olap_plan **out, int dtype, int default_kind, i
           }
         }
       }
-      if ((rc = upload(&p->dev_tab, tabs.data(), tabs.size() * sizeof(uint32_t)))) {
-        olap_plan_destroy(p);
-        return rc;
-      }
+      if ((rc = upload(&p->dev_tab, tabs.data(), tabs.size() * sizeof(uint32_t)))) return rc;
       const uint32_t *dev = (const uint32_t *)p->dev_tab;
       b.rd_off = dev;
       b.wr_off = dev + elems;
@@ -1338,16 +915,13 @@ extern "C" int olap_reorder_plan(olap_plan **out, int dtype, int default_kind, i
       p->kind = PLAN_BRICK;
       p->n_bricks = bricks;
       p->kernel_name = p->xy_ok ? "transpose_xy_kernel" : quad ? "reorder_brick4_kernel" : "reorder_brick_kernel";
-      *out = p;
+      *out = owner.release();
       return OLAP_OK;
     }
   }
-  if ((rc = finish_remap(p, dims, p->out_cells, true))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = finish_remap(p, dims, p->out_cells, true))) return rc;
   p->kernel_name = p->xy_ok ? "transpose_xy_kernel" : "gather(reorder)";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -1389,7 +963,8 @@ static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_def
   if ((rc = check_dtype(dtype)) || (rc = check_dtype(his_dtype)) || (rc = check_default(my_default_kind)) || (rc = check_default(his_default_kind))) return rc;
   if ((rc = check_load_maps(ndim, my_len, his_len, his_to_mine))) return rc;
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   const bool convert = his_dtype != dtype;
   p->kind = PLAN_LOAD;
@@ -1439,10 +1014,7 @@ static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_def
     LoadPermute lp{};
     if (ok && small_div_for(his_len[last], row_cap, &lp.by_len)) {
       void *dev = nullptr;
-      if ((rc = upload(&dev, perm.data(), perm.size() * sizeof(uint32_t)))) {
-        olap_plan_destroy(p);
-        return rc;
-      }
+      if ((rc = upload(&dev, perm.data(), perm.size() * sizeof(uint32_t)))) return rc;
       p->owned.push_back(dev);
       lp.perm = (const uint32_t *)dev;
       lp.len = his_len[last];
@@ -1460,10 +1032,7 @@ static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_def
     dims.push_back(one);
   }
   // (16-byte lanes when the innermost merged run is contiguous in both stores: finish_remap checks it)
-  if ((rc = finish_remap(p, dims, p->in_cells, !convert))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = finish_remap(p, dims, p->in_cells, !convert))) return rc;
   if (convert) {  // a lane holds 16 bytes of HIS: lanes when the contiguous run is a whole number of them
     Remap &r = p->remap;
     const uint32_t v = (uint32_t)(16 / olap_dtype_size(his_dtype));
@@ -1472,13 +1041,13 @@ static int load_plan_build(olap_plan **out, int dtype, int his_dtype, int my_def
       r.total = p->in_cells / v;
     }
     p->kernel_name = p->vec > 1 ? "load_convert (16-byte lanes of the other store)" : "load_convert (16-byte runs of the other store)";
-    *out = p;
+    *out = owner.release();
     return OLAP_OK;
   }
   p->kernel_name = permuted_rows ? "load_permute_rows_kernel"
                    : p->vec > 1  ? "load_scatter (16-byte lanes)"
                                  : "load_scatter (16-byte runs of the other store)";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -1494,7 +1063,8 @@ extern "C" int olap_compose_plan(olap_plan **out, int dtype, int default_kind, i
   if ((rc = check_dtype(dtype)) || (rc = check_default(default_kind))) return rc;
   if ((rc = check_load_maps(ndim, my_len, his_len, his_to_mine))) return rc;
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_COMPOSE;
   p->dtype = p->his_dtype = dtype;
@@ -1523,17 +1093,14 @@ extern "C" int olap_compose_plan(olap_plan **out, int dtype, int default_kind, i
     one.len = 1, one.arithmetic = true, one.stride = 1;
     dims.push_back(one);
   }
-  if ((rc = finish_remap(p, dims, p->out_cells, true))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = finish_remap(p, dims, p->out_cells, true))) return rc;
   // lanes only of 16 bytes: an innermost run that is no whole number of them takes the per-cell form
   if (p->vec != (int)(16 / olap_dtype_size(dtype))) {
     p->remap.total *= (uint64_t)p->vec;
     p->vec = 1;
   }
   p->kernel_name = p->vec > 1 ? "compose_gather (16-byte lanes)" : "compose_gather (16-byte runs of this store)";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -1558,7 +1125,8 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
         return fail(OLAP_ERR_INDEX_RANGE, "drillDown map of dimension %d: entry %u = %u is outside the old dimension (%u items)", d, j, maps[d][j], old_len[d]);
   }
   if ((rc = require_device())) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_DRILLDOWN;
   p->dtype = dtype;
@@ -1591,10 +1159,7 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
       bcast.back().stride = old_stride[d];
       continue;
     }
-    if (nd == kMaxDims) {
-      olap_plan_destroy(p);
-      return fail(OLAP_ERR_INVALID_ARGUMENT, "drillDown: more than %d non-mergeable dimensions", kMaxDims);
-    }
+    if (nd == kMaxDims) return fail(OLAP_ERR_INVALID_ARGUMENT, "drillDown: more than %d non-mergeable dimensions", kMaxDims);
     a.new_len[nd] = new_len[d];
     a.old_stride[nd] = old_stride[d];
     sc.old_len[nd] = old_len[d];
@@ -1660,10 +1225,7 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
         const size_t order_at = csr.size();
         if (!contiguous) csr.insert(csr.end(), order.begin(), order.end());
         void *dev = nullptr;
-        if ((rc = upload(&dev, csr.data(), csr.size() * sizeof(uint32_t)))) {
-          olap_plan_destroy(p);
-          return rc;
-        }
+        if ((rc = upload(&dev, csr.data(), csr.size() * sizeof(uint32_t)))) return rc;
         p->owned.push_back(dev);
         ax.gstart = (const uint32_t *)dev;
         ax.order = contiguous ? nullptr : (const uint32_t *)dev + order_at;
@@ -1675,23 +1237,16 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
   }
   p->dd_two_pass = !p->dd_rows && !distributions && !integer_measure;
   if (p->dd_two_pass) {
-    if ((rc = finish_remap(p, bcast, p->out_cells, true))) {  // uploads p->dev_tab (int64 offsets)
-      olap_plan_destroy(p);
-      return rc;
-    }
+    if ((rc = finish_remap(p, bcast, p->out_cells, true))) return rc;  // uploads p->dev_tab (int64 offsets)
     p->dev_tab2 = p->dev_tab;  // keep: the per-cell tables below go to dev_tab
     p->dev_tab = nullptr;
     void *cnt = nullptr;
-    if ((rc = upload(&cnt, tab2.data(), tab2.size() * sizeof(uint32_t)))) {
-      olap_plan_destroy(p);
-      return rc;
-    }
+    if ((rc = upload(&cnt, tab2.data(), tab2.size() * sizeof(uint32_t)))) return rc;
     sc.tab = (const uint32_t *)cnt;
     p->dev_tmp = nullptr;
     hipError_t e = dev_alloc(&p->dev_tmp, (p->in_cells ? p->in_cells : 1) * olap_dtype_size(dtype) + (size_t)16);
     if (e != hipSuccess) {
       dev_free(cnt);
-      olap_plan_destroy(p);
       return hip_fail(e, "hipMalloc(drillDown quotients)");
     }
     p->owned.push_back(cnt);
@@ -1702,17 +1257,11 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
   a.use_rounding = integer_measure;  // in-memory.js:343
   a.dist = nullptr;
   a.n_dist = 0;
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
   a.tab = (const uint32_t *)p->dev_tab;
   if (distributions) {
     void *dv = nullptr;
-    if ((rc = upload(&dv, distributions, n_dist * sizeof(double)))) {
-      olap_plan_destroy(p);
-      return rc;
-    }
+    if ((rc = upload(&dv, distributions, n_dist * sizeof(double)))) return rc;
     p->dev_dist = (double *)dv;
     a.dist = p->dev_dist;
     a.n_dist = n_dist;
@@ -1723,17 +1272,14 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
   {
     void *ev = nullptr;
     const unsigned long long init = ~0ull;
-    if ((rc = upload(&ev, &init, sizeof(init)))) {
-      olap_plan_destroy(p);
-      return rc;
-    }
+    if ((rc = upload(&ev, &init, sizeof(init)))) return rc;
     p->dev_err = (unsigned long long *)ev;
     a.err = p->dev_err;
   }
   const bool dd_lines = p->dd_rows && !(method == OLAP_SUM && p->dd.use_rounding) && (p->axis.inner * olap_dtype_size(dtype)) % 128 != 0 &&
                         ((size_t)p->vec * olap_dtype_size(dtype) == 16 || p->axis.inner * olap_dtype_size(dtype) >= 2048);
   p->kernel_name = p->dd_rows ? (dd_lines ? "drilldown_rows_lines_kernel" : "drilldown_rows_kernel") : (p->dd_two_pass ? "drilldown_scale_kernel+gather_kernel" : "drilldown_kernel");
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -1741,7 +1287,7 @@ extern "C" int olap_drilldown_plan(olap_plan **out, int dtype, int default_kind,
 // What a launch over p->axis runs with: buffers off the 16-byte grid take one cell per lane.  The drillDown row
 // kernels read neither `total` nor `xcd_order`, and the mixed-rule launcher declines unaligned buffers before it
 // looks at the lane width, so one preparation serves all four launches.
-static DrillUpAxis axis_for_launch(const olap_plan *p, bool aligned, int *vec) {
+DrillUpAxis axis_for_launch(const olap_plan *p, bool aligned, int *vec) {
   DrillUpAxis a = p->axis;
   a.aligned16 = aligned;
   *vec = aligned ? p->vec : 1;
@@ -1855,15 +1401,15 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_DRILLUP_AXIS: {
       int vec;
       const DrillUpAxis a = axis_for_launch(p, all_aligned16(in, in_s, out, out_s), &vec);
-      if (p->seg.S_tot > 0 && drillup_method != OLAP_PRODUCT && drillup_method != OLAP_PARTIAL_AVERAGE) {
-        e = Launch<T>::drillup_segmented(drillup_method, hs, vec, in, in_s, out, out_s, a, p->seg, stream);
-        break;
+      const DrillUpChoice c = drillup_form(a, vec, sizeof(T), hs, drillup_method, p->reduce, p->seg);
+      switch (c.form) {
+        case FORM_SEGMENTS: e = Launch<T>::drillup_segmented(drillup_method, hs, vec, in, in_s, out, out_s, a, p->seg, stream); break;
+        case FORM_REDUCE4:
+        case FORM_REDUCE:
+        case FORM_SPLIT4:
+        case FORM_SPLIT: e = Launch<T>::drillup_reduce(drillup_method, hs, in, in_s, out, out_s, c, stream); break;
+        default: e = Launch<T>::drillup_axis_batch(drillup_method, hs, vec, Batch<T>::one(in, in_s, out, out_s), 1, c, stream); break;
       }
-      if (p->reduce.S > 0) {
-        e = Launch<T>::drillup_reduce(drillup_method, hs, in, in_s, out, out_s, a, p->reduce, stream);
-        break;
-      }
-      e = Launch<T>::drillup_axis(drillup_method, hs, vec, in, in_s, out, out_s, a, stream);
       break;
     }
     case PLAN_DRILLUP_GENERIC:
@@ -1972,8 +1518,9 @@ static int run_batch_typed(olap_plan *p, const Pairs &q, const int *methods, hip
     int vec;
     const Batch<T> b = fill_batch<T>(q, first, nb, methods, &aligned);
     const DrillUpAxis a = axis_for_launch(p, aligned, &vec);
-    const hipError_t e = methods ? Launch<T>::drillup_rows_mixed(q.masks(), vec, b, (unsigned)nb, a, deep, stream)
-                                 : Launch<T>::drillup_axis_batch(p->method, q.masks(), vec, b, (unsigned)nb, a, stream);
+    const DrillUpChoice c = drillup_axis_form(a, vec, sizeof(T), q.masks(), /*ragged_slots=*/!methods);
+    const hipError_t e = methods ? Launch<T>::drillup_rows_mixed(q.masks(), vec, b, (unsigned)nb, c, deep, stream)
+                                 : Launch<T>::drillup_axis_batch(p->method, q.masks(), vec, b, (unsigned)nb, c, stream);
     if (methods && e == hipErrorNotSupported && first == 0) return OLAP_MIXED_NOT_APPLICABLE;
     if (e != hipSuccess) return hip_fail(e, methods ? "drillup_rows_mixed_kernel" : p->kernel_name.c_str());
   }
@@ -2233,19 +1780,37 @@ extern "C" int olap_diag_tile_placement(int dtype, uint32_t K, uint32_t G, uint3
     return fail(OLAP_ERR_INVALID_ARGUMENT, "tile placement: NULL argument or empty extent");
   const uint64_t budget = kTileBytes / olap_dtype_size(dtype);
   if ((uint64_t)K * inner > budget) return fail(OLAP_ERR_INVALID_ARGUMENT, "tile placement: a row of %llu cells does not fit a tile of %llu", (unsigned long long)K * inner, (unsigned long long)budget);
-  std::vector<uint32_t> gstart((size_t)G + 1, 0), order(K);
-  for (uint32_t k = 0; k < K; ++k) {
+  for (uint32_t k = 0; k < K; ++k)
     if (map[k] >= G) return fail(OLAP_ERR_INDEX_RANGE, "tile placement: map entry %u = %u is outside the new dimension (%u items)", k, map[k], G);
-    gstart[map[k] + 1]++;
-  }
-  for (uint32_t g = 0; g < G; ++g) gstart[g + 1] += gstart[g];
-  std::vector<uint32_t> cur(gstart.begin(), gstart.end() - 1);
-  for (uint32_t k = 0; k < K; ++k) order[cur[map[k]]++] = k;
+  std::vector<uint32_t> gstart, order;
+  build_csr(map, K, G, gstart, order);
   TilePerm tp;
   tile_perm_build(gstart.data(), order.data(), K, G, inner, budget, 16 / olap_dtype_size(dtype), &tp);
   memcpy(cell_pos, tp.cell.data(), (size_t)K * inner * sizeof(uint32_t));
   memcpy(group_bounds, tp.grp.data(), tp.grp.size() * sizeof(uint32_t));
   *pitch = tp.pitch;
+  return OLAP_OK;
+}
+
+extern "C" int olap_diag_plan_describe(const olap_plan *p, char *buf, size_t cap) {
+  if (!p || !buf || cap == 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan describe: NULL argument or empty buffer");
+  static const char *const kinds[] = {"drillup_axis", "drillup_generic", "gather", "load", "drilldown", "brick", "gather_reduce", "compose", "cumulate", "rolling"};
+  if (p->kind != PLAN_DRILLUP_AXIS) {
+    snprintf(buf, cap, "kind=%s kernel=%s", kinds[p->kind], p->kernel_name.c_str());
+    return OLAP_OK;
+  }
+  const DrillUpChoice c = plan_drillup_form(p, p->method);
+  const DrillUpAxis &a = p->axis;
+  const DrillUpReduce &rd = p->reduce;
+  size_t n = 0;
+  auto put = [&](const char *fmt, auto... v) { n += n < cap ? (size_t)snprintf(buf + n, cap - n, fmt, v...) : 0; };  // appends, truncating at cap
+  put("kind=%s form=%s vec=%d outer=%llu K=%llu G=%llu inner=%llu contiguous=%d perm_pitch=%u n_gtile=%u min_group=%u longest_group=%u", kinds[p->kind],
+      drillup_form_name(c.form), p->vec, (unsigned long long)a.outer, (unsigned long long)a.K, (unsigned long long)a.G, (unsigned long long)a.inner,
+      a.order == nullptr, a.perm_pitch, a.n_gtile, a.min_group, p->longest_group);
+  if (rd.S == 0) put(" reduce.S=%u", rd.S);  // (not the few-outputs regime: nothing else of it was decided)
+  else put(" reduce.S=%u reduce.unit=%u reduce.rows=%u reduce.seg_len=%u reduce.vec4=%u reduce.edge=%u", rd.S, rd.unit, rd.rows, rd.seg_len, rd.vec4, rd.edge);
+  put(" seg.S_tot=%u", p->seg.S_tot);
+  if (c.form == FORM_TILE) put(" tile.mode=%d tile.rows=%u tile.lds=%zu", c.tile.mode, c.tile.tl.rows_per_tile, c.tile.lds);
   return OLAP_OK;
 }
 
@@ -3548,7 +3113,8 @@ static int cumulate_plan(olap_plan **out, int dtype, int default_kind, int ndim,
   *out = nullptr;
   int rc = require_device();
   if (rc) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_CUMULATE;
   p->dtype = dtype;
@@ -3572,16 +3138,13 @@ static int cumulate_plan(olap_plan **out, int dtype, int default_kind, int ndim,
   std::vector<uint32_t> tab(gstart);
   const size_t order_off = tab.size();
   if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
   v.gstart = (const uint32_t *)p->dev_tab;
   v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
   cumulate_choose(v, (int)olap_dtype_size(dtype), contiguous);
   p->kernel_name = v.form == CUMULATE_COLUMN ? (v.vec == 1 ? "cumulate_column_kernel<cell>" : "cumulate_column_kernel")
                    : v.form == CUMULATE_ROW_WHOLE ? "cumulate_rows_kernel" : "cumulate_rows_kernel<chunked>";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 
@@ -3682,7 +3245,8 @@ static int rolling_plan(olap_plan **out, int dtype, int default_kind, int ndim, 
   *out = nullptr;
   int rc = require_device();
   if (rc) return rc;
-  olap_plan *p = new (std::nothrow) olap_plan();
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
   if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
   p->kind = PLAN_ROLLING;
   p->dtype = dtype;
@@ -3696,14 +3260,11 @@ static int rolling_plan(olap_plan **out, int dtype, int default_kind, int ndim, 
   v.before = window_side(before, lens[axis]);
   v.after = window_side(after, lens[axis]);
   v.def_nan = p->def_nan;
-  if (map && (rc = upload(&p->dev_tab, map, (size_t)lens[axis] * sizeof(uint32_t)))) {
-    olap_plan_destroy(p);
-    return rc;
-  }
+  if (map && (rc = upload(&p->dev_tab, map, (size_t)lens[axis] * sizeof(uint32_t)))) return rc;
   v.map = (const uint32_t *)p->dev_tab;
   rolling_choose(v, (int)olap_dtype_size(dtype));
   p->kernel_name = v.form == ROLLING_DIRECT ? "rolling_direct_kernel" : v.form == ROLLING_COLUMNS ? "rolling_tiled_kernel<columns>" : "rolling_tiled_kernel<series>";
-  *out = p;
+  *out = owner.release();
   return OLAP_OK;
 }
 

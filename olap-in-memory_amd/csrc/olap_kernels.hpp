@@ -3959,20 +3959,21 @@ __global__ __launch_bounds__(kBlock) void scatter_sparse_kernel(T *values, const
 }
 
 // ======================================================================= launchers
+struct DrillUpChoice;  // a form of the one-axis roll-up with its launch geometry (below)
 template <typename T>
 struct Launch {
-  static hipError_t drillup_axis(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out,
-                                 int32_t *st_out, const DrillUpAxis &a, hipStream_t stream);
-  // the same roll-up over nb (<= kMaxBatch) buffer pairs in one launch; all with or all without a mask
-  static hipError_t drillup_axis_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+  // The one-axis roll-up in the form `c` (drillup_axis_form, below) over nb (<= kMaxBatch) buffer pairs in one launch; all
+  // with or all without a mask.  A single pair is Batch<T>::one(...) with nb == 1.
+  static hipError_t drillup_axis_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpChoice &c,
                                        hipStream_t stream);
   // pairs with DIFFERENT rules (b.method[]) in one launch: the row regime (16-byte lanes, or 8-byte lanes of 4-byte cells)
-  // and the row-tile regime — anything else returns hipErrorNotSupported and the caller launches rule by rule.  `deep`:
-  // some pair's rule wants 4 rows in flight.
-  static hipError_t drillup_rows_mixed(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, bool deep,
+  // and the row-tile regime — anything else returns hipErrorNotSupported and the caller launches rule by rule.  `c`:
+  // drillup_axis_form without the ragged slots; `deep`: some pair's rule wants 4 rows in flight.
+  static hipError_t drillup_rows_mixed(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpChoice &c, bool deep,
                                        hipStream_t stream);
+  // `c`: drillup_reduce_form
   static hipError_t drillup_reduce(int method, bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                   const DrillUpAxis &a, const DrillUpReduce &rd, hipStream_t stream);
+                                   const DrillUpChoice &c, hipStream_t stream);
   static hipError_t drillup_generic(int method, bool has_status, const T *in, const int32_t *st_in, T *out,
                                     int32_t *st_out, const DrillUpGeneric &a, hipStream_t stream);
   static hipError_t drilldown(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
@@ -4040,7 +4041,13 @@ inline unsigned grid_stride_for(uint64_t n) {
   return (unsigned)(want < 1 ? 1 : (want < cap ? want : cap));
 }
 
-#ifdef OLAP_KERNELS_IMPL
+// ======================================================================= which form a one-axis roll-up runs in
+// Decided HERE and nowhere else: the planner names a plan's kernels with drillup_form, the typed launch
+// units switch on its result.  Host code, outside OLAP_KERNELS_IMPL so that both see the same functions.  What stays in
+// the launchers are choices of a template variant: FAST, contiguous groups or not, rows in flight, METHOD and HS.
+enum DrillUpForm {
+  FORM_ROWS, FORM_ROWS_RAGGED, FORM_TILE, FORM_GTILE, FORM_FLAT, FORM_SEGMENTS, FORM_REDUCE4, FORM_REDUCE, FORM_SPLIT4, FORM_SPLIT, FORM_GENERIC
+};
 
 // Whether the LDS row-tile regime takes this roll-up (small `inner`: short row pieces make the flat regime's accesses
 // waste much of every cache line; whole rows of K*inner cells staged per workgroup, kTileBytes of cells), and how.
@@ -4049,13 +4056,14 @@ struct TileGeometry {
   uint64_t tiles = 0;
   size_t lds = 0;
   int mode = 0;  // table mode of drillup_tile_kernel
+  bool shape_fits = false;  // the shape is the regime's (short row pieces; a row and its tables fit): where tile_geometry
+                            // still says no, the 16-byte grid does (the buffers, or no whole number of rows per tile lands on it)
 };
-template <typename T>
-static bool tile_geometry(const DrillUpAxis &a, bool has_status, TileGeometry *out) {
+inline bool tile_geometry(const DrillUpAxis &a, size_t cell, bool has_status, TileGeometry *out) {
   const bool contig = a.order == nullptr;
   const uint64_t row_elems = a.K * a.inner;
-  const uint64_t budget = kTileBytes / sizeof(T);
-  constexpr uint64_t V = 16 / sizeof(T);
+  const uint64_t budget = kTileBytes / cell;
+  const uint64_t V = 16 / cell;
   static const bool no_permute = getenv("OLAP_TILE_NO_PERMUTE") != nullptr;
   // interleaved groups: cells permuted into group order while they are staged (MODE 3, tables from the plan)
   const bool permute = !contig && a.perm_cell && !no_permute;
@@ -4064,7 +4072,8 @@ static bool tile_geometry(const DrillUpAxis &a, bool has_status, TileGeometry *o
   const uint64_t R = tile_rows_for(row_elems, permute ? (uint64_t)a.perm_pitch * a.inner : row_elems, budget, V);
   uint64_t tile_max_inner = 128;  // tools/sweep3.py: the LDS form wins up to ~100 cells per row piece
   if (const char *e = getenv("OLAP_TILE_MAX_INNER")) tile_max_inner = (uint64_t)atoll(e);
-  if (!(a.aligned16 && a.inner < tile_max_inner && R > 0 && csr_bytes <= 16 * 1024 && a.G * a.inner <= 0xFFFFFFFFull)) return false;
+  out->shape_fits = a.inner < tile_max_inner && row_elems > 0 && row_elems <= budget && csr_bytes <= 16 * 1024;
+  if (!(a.aligned16 && out->shape_fits && R > 0 && a.G * a.inner <= 0xFFFFFFFFull)) return false;  // (R > 0: the padded rows fit as well)
   DrillUpTile &tl = out->tl;
   tl.rows_per_tile = (uint32_t)R;
   tl.row_elems = (uint32_t)row_elems;
@@ -4089,7 +4098,10 @@ static bool tile_geometry(const DrillUpAxis &a, bool has_status, TileGeometry *o
 // is nearly empty is the worst choice by far (135 slots: 128 + 7 lanes 99 us, one workgroup of 256 lanes 75 us, 64 + 64
 // + 7 lanes 78 us; 69 slots: 64 + 5 lanes 100 us, one of 128 lanes 76 us — full and empty workgroups alternate, and
 // with an even number of CUs per XCD the full ones keep landing on the same half of them).
-static inline unsigned rows_lanes_for(uint64_t n_vec) {
+// OLAP_ROWS_LANES = 64 | 128 | 256 (developer knob, read once) forces the width.
+inline unsigned rows_lanes_for(uint64_t n_vec) {
+  static const int forced = getenv("OLAP_ROWS_LANES") ? atoi(getenv("OLAP_ROWS_LANES")) : 0;
+  if (forced == 64 || forced == 128 || forced == 256) return (unsigned)forced;
   if (n_vec <= 64) return 64u;
   if (n_vec <= 128) return 128u;
   if (n_vec <= 256) return 256u;
@@ -4103,280 +4115,318 @@ static inline unsigned rows_lanes_for(uint64_t n_vec) {
   return lanes;
 }
 
-// Row regime when a row of VEC-slots fills at least one wavefront-sized piece of a workgroup
-// reasonably (>= 128 slots); otherwise the flat regime.  FAST = additive method, zero default, no
-// mask read.  The grid of the row regime is outer*G*blocks_per_row workgroups.
-template <typename T, int METHOD, bool HS, int VEC>
-static hipError_t drillup_axis_launch(const Batch<T> &b, unsigned nb, const DrillUpAxis &a, hipStream_t stream) {
-  constexpr bool kAdditive = (METHOD == OLAP_SUM || METHOD == OLAP_AVERAGE || METHOD == OLAP_PARTIAL_AVERAGE);
-  const bool fast = kAdditive && !HS && !a.def_nan;
-  const bool contig = a.order == nullptr;
-  // a row takes a whole number of workgroups: 271 slots fill 271 of 512 lanes at 256 lanes per
-  // workgroup, 271 of 320 at 64 — the row regime picks the largest workgroup that fills >= 85 %
-  unsigned row_lanes = kBlock;
-  {
-    static const int forced = getenv("OLAP_ROWS_LANES") ? atoi(getenv("OLAP_ROWS_LANES")) : 0;
-    row_lanes = rows_lanes_for(a.n_vec);
-    if (forced == 64 || forced == 128 || forced == 256) row_lanes = (unsigned)forced;
-  }
+// A form and the launch geometry that goes with it.
+struct DrillUpChoice {
+  DrillUpForm form = FORM_FLAT;
+  DrillUpAxis axis{};      // as the kernel takes it: the row forms with their own slots, workgroup width and grid
+  uint64_t blocks = 0;     // workgroups along x (rows, ragged rows, gtile, the stage of a reduce form)
+  TileGeometry tile;       // FORM_TILE
+  DrillUpReduce reduce{};  // the reduce forms: as the kernel takes it
+  bool merge = false;      // the reduce forms: a merge kernel folds the segments' partials
+};
+
+// Row regime when a row of VEC-slots fills at least one wavefront-sized piece of a workgroup reasonably (>= 128 slots;
+// its grid is outer*G*blocks_per_row workgroups); short row pieces take the LDS tile, the plan's group tiles or the flat
+// regime.  `a`: the axis with alignment and lane width (`vec` cells) applied; `cell`: bytes per cell; `ragged_slots`:
+// the kernel has the form for rows that are not whole 16-byte groups (the mixed-rule kernel has not).
+inline DrillUpChoice drillup_axis_form(const DrillUpAxis &a, int vec, size_t cell, bool has_status, bool ragged_slots = true) {
+  DrillUpChoice c;
+  c.axis = a;
+  const unsigned row_lanes = rows_lanes_for(a.n_vec);
   const uint64_t row_blocks = a.outer * a.G * ((a.n_vec + row_lanes - 1) / row_lanes);
   const bool rows = a.n_vec >= 128 && row_blocks < 0x7FFFFFFFull;
+  if (!rows && tile_geometry(a, cell, has_status, &c.tile)) {
+    c.form = FORM_TILE;
+    return c;
+  }
+  if (a.gtile && a.n_gtile > 0 && a.aligned16 && a.outer * a.n_gtile < 0x7FFFFFFFull) {  // (the plan decides; also over rows of >= 128 slots)
+    c.form = FORM_GTILE;
+    c.blocks = a.outer * a.n_gtile;
+    return c;
+  }
+  if (!rows) return c;  // FORM_FLAT
+  if (ragged_slots && (size_t)vec * cell < 16) {
+    // rows that are not whole 16-byte groups (or buffers that are not 16-byte aligned): 16-byte slots at
+    // cell-aligned addresses instead of 4-byte lanes
+    const uint64_t RV = 16 / cell;
+    static const bool no_ragged = getenv("OLAP_NO_RAGGED_ROWS") != nullptr;
+    // (8-byte lanes — 4-byte cells in rows of an even, not fourfold, number of cells — too: [3652,100,274] city -> country
+    // 79-82 us with 8-byte lanes, 76 us with these; OLAP_NO_RAGGED_VEC2 keeps the 8-byte lanes)
+    static const bool no_ragged2 = getenv("OLAP_NO_RAGGED_VEC2") != nullptr;
+    if (!no_ragged && (vec == 1 || !no_ragged2)) {
+      DrillUpAxis rg = a;
+      rg.n_vec = (a.inner + RV - 1) / RV;
+      rg.lanes = rows_lanes_for(rg.n_vec);
+      rg.blocks_per_row = (rg.n_vec + rg.lanes - 1) / rg.lanes;
+      const uint64_t blocks = a.outer * a.G * rg.blocks_per_row;
+      if (blocks < 0x7FFFFFFFull) {
+        rg.grid = (uint32_t)blocks;
+        c.form = FORM_ROWS_RAGGED;
+        c.axis = rg;
+        c.blocks = blocks;
+        return c;
+      }
+    }
+  }
+  c.form = FORM_ROWS;  // the row regime's own workgroup width
+  c.axis.blocks_per_row = (a.n_vec + row_lanes - 1) / row_lanes;
+  c.axis.lanes = row_lanes;
+  c.axis.grid = (uint32_t)row_blocks;
+  c.blocks = row_blocks;
+  return c;
+}
+
+// The plan's reduce regime (rd.S > 0): which of its kernels, and with what.
+inline DrillUpChoice drillup_reduce_form(const DrillUpAxis &a, const DrillUpReduce &rd, size_t cell) {
+  DrillUpChoice c;
+  c.axis = a;
+  c.reduce = rd;
+  c.merge = true;
+  const uint64_t cells = a.outer * a.G * a.inner;
+  // cooperative form: rows of up to 128 cells, or — 16-byte form only — of up to 1 024 (the scalar form gives a lane
+  // one cell of one row per step: rows must fit the unit's lanes; otherwise the lane-per-cell split form below)
+  const bool vec4_now = rd.vec4 && a.aligned16 && (rd.rows > 0 || cell == 4);  // (16-byte form: 4 cells of 4 bytes, 2 of 8)
+  if (rd.rows > 0 && (vec4_now || a.inner <= rd.unit)) {
+    const uint64_t upb = kBlock / rd.unit;
+    c.blocks = (a.outer * a.G * rd.S + upb - 1) / upb;
+    if (vec4_now) {
+      c.form = FORM_REDUCE4;
+      c.merge = rd.S != 1;  // one segment per group: the result left from the reduction
+    } else {
+      c.form = FORM_REDUCE;
+      if (rd.vec4) {  // plan sized `rows` for 16 B lanes; the scalar form covers unit cells per step
+        uint32_t rows = 1;
+        while ((uint64_t)rows * 2 * a.inner <= rd.unit) rows *= 2;
+        c.reduce.rows = rows;
+      }
+    }
+  } else if (rd.rows == 0 && rd.vec4 && a.aligned16 && cell == 4 && a.inner % 4 == 0) {  // 16-byte lanes
+    c.form = FORM_SPLIT4;
+    c.blocks = grid_for(cells / 4 * rd.S);
+  } else {
+    c.form = FORM_SPLIT;
+    c.blocks = grid_for(cells * rd.S);
+  }
+  return c;
+}
+
+// One changed axis: the segmented rows (all rules but the two that do not fold), the plan's reduce regime, else by the axis.
+inline DrillUpChoice drillup_form(const DrillUpAxis &a, int vec, size_t cell, bool has_status, int method, const DrillUpReduce &rd,
+                                  const SegmentedRows &sg) {
+  if (sg.S_tot > 0 && method != OLAP_PRODUCT && method != OLAP_PARTIAL_AVERAGE) return DrillUpChoice{FORM_SEGMENTS, a};
+  return rd.S > 0 ? drillup_reduce_form(a, rd, cell) : drillup_axis_form(a, vec, cell, has_status);
+}
+
+inline const char *drillup_form_name(DrillUpForm f) {
+  static const char *const names[] = {"rows", "rows_ragged", "tile", "gtile", "flat", "segments", "reduce4", "reduce", "split4", "split", "generic"};
+  return names[f];
+}
+// the kernels of a form, as olap_plan_kernel_name reports them
+inline const char *drillup_form_kernels(const DrillUpChoice &c) {
+  switch (c.form) {
+    case FORM_ROWS:
+    case FORM_ROWS_RAGGED: return "drillup_rows_kernel";
+    case FORM_TILE: return "drillup_tile_kernel";
+    case FORM_GTILE: return "drillup_gtile_kernel";
+    // (a plan has always named the tile kernel for the tile regime's shapes, "the launcher re-checks alignment": rows of an odd
+    // number of cells of which fewer than four fit a tile run flat even over aligned buffers, and tests assert the name)
+    case FORM_FLAT: return c.tile.shape_fits ? "drillup_tile_kernel" : "drillup_flat_kernel";
+    case FORM_SEGMENTS: return "drillup_rows_kernel (segments)+segments_combine_kernel";
+    case FORM_REDUCE4: return c.merge ? "drillup_reduce4_kernel+drillup_merge_kernel" : "drillup_reduce4_kernel";
+    case FORM_REDUCE: return "drillup_reduce_kernel+drillup_merge_kernel";
+    case FORM_SPLIT4: return "drillup_split4_kernel+drillup_merge_kernel";
+    case FORM_SPLIT: return "drillup_split_kernel+drillup_merge_kernel";
+    default: return "drillup_generic_kernel";
+  }
+}
+
+#ifdef OLAP_KERNELS_IMPL
+
+// The form `c` (drillup_axis_form) over the nb pairs of `b`.  FAST = additive method, zero default, no mask read.
+template <typename T, int METHOD, bool HS, int VEC>
+static hipError_t drillup_axis_launch(const Batch<T> &b, unsigned nb, const DrillUpChoice &c, hipStream_t stream) {
+  constexpr bool kAdditive = (METHOD == OLAP_SUM || METHOD == OLAP_AVERAGE || METHOD == OLAP_PARTIAL_AVERAGE);
+  const DrillUpAxis &a = c.axis;
+  const bool fast = kAdditive && !HS && !a.def_nan;
+  const bool contig = a.order == nullptr;
+  constexpr int U = 4;
   // Rows in flight per lane.  With full 16 B lanes and rows that fill whole workgroups ONE is
   // fastest for the plain streaming forms (tools/microbench.hip, profiles/microbench_r01.txt: 67 us
   // against 70-71 us at 2..10 on the 10^8 cube): 32 waves per CU already keep 32 KiB in flight and
   // the waves sweep the K rows together.  Narrow lanes or short rows (e.g. inner = 274) need the
   // depth back, and so does the heavier exact state machine.
-  constexpr int U = 4;
   bool shallow = (kAdditive || IsPick<METHOD>::value) && VEC * sizeof(T) >= 16 && a.n_vec >= 1024;
   if (a.depth == 4) shallow = false;
   if (const char *e = getenv("OLAP_ROWS_DEPTH")) shallow = atoi(e) == 1;  // A/B: 1 or 4 rows in flight
-  if (!rows) {
-    // LDS tile regime for small `inner` (short row pieces make the flat regime's accesses waste much
-    // of every cache line): whole rows of K*inner cells staged per workgroup, kTileBytes of cells
-    TileGeometry tg;
-    if (tile_geometry<T>(a, HS, &tg)) {
-      const DrillUpTile &tl = tg.tl;
-      const uint64_t tiles = tg.tiles;
-      const size_t lds = tg.lds;
-      const bool all = tg.mode == 1, permute = tg.mode == 3;
-      if (tiles < 0x7FFFFFFFull) {
-#define OLAP_TILE(F, M) hipLaunchKernelGGL((drillup_tile_kernel<T, METHOD, HS, F, M>), dim3((unsigned)tiles, nb), kBlock, lds, stream, b, a, tl)
-        if constexpr (kAdditive && !HS) {
-          if (fast) {
-            if (all) OLAP_TILE(true, 1); else if (contig) OLAP_TILE(true, 2); else if (permute) OLAP_TILE(true, 3); else OLAP_TILE(true, 0);
-            return hipGetLastError();
-          }
-        }
-        if (all) OLAP_TILE(false, 1); else if (contig) OLAP_TILE(false, 2); else if (permute) OLAP_TILE(false, 3); else OLAP_TILE(false, 0);
+  // LAUNCH(true) where FAST applies (only additive rules without a mask have the variant), else LAUNCH(false)
+#define OLAP_FAST_OR_NOT(LAUNCH)                                                     \
+  do {                                                                               \
+    if constexpr (kAdditive && !HS) {                                                \
+      if (fast) { LAUNCH(true); return hipGetLastError(); }                          \
+    }                                                                                \
+    LAUNCH(false);                                                                   \
+    return hipGetLastError();                                                        \
+  } while (0)
+  switch (c.form) {
+    case FORM_TILE: {
+      const DrillUpTile &tl = c.tile.tl;
+      const int mode = c.tile.mode;
+#define OLAP_TILE(F, M) hipLaunchKernelGGL((drillup_tile_kernel<T, METHOD, HS, F, M>), dim3((unsigned)c.tile.tiles, nb), kBlock, c.tile.lds, stream, b, a, tl)
+#define OLAP_TILE_MODE(F) if (mode == 1) OLAP_TILE(F, 1); else if (mode == 2) OLAP_TILE(F, 2); else if (mode == 3) OLAP_TILE(F, 3); else OLAP_TILE(F, 0)
+      OLAP_FAST_OR_NOT(OLAP_TILE_MODE);
+#undef OLAP_TILE_MODE
 #undef OLAP_TILE
-        return hipGetLastError();
-      }
     }
-  }
-  if (a.gtile && a.n_gtile > 0 && a.aligned16 && a.outer * a.n_gtile < 0x7FFFFFFFull) {  // (the plan decides; also over rows of >= 128 slots)
-    const size_t lds = kTileBytes + (HS ? kTileBytes / sizeof(T) * 4 : 0) + (kGroupTileMaxGroups + 1) * 4;
-    const unsigned blocks = (unsigned)(a.outer * a.n_gtile);
-    const uint64_t n_cells = a.outer * a.K * a.inner;
-#define OLAP_GTILE(F) hipLaunchKernelGGL((drillup_gtile_kernel<T, METHOD, HS, F>), dim3(blocks, nb), kBlock, lds, stream, b, a, n_cells)
-    if constexpr (kAdditive && !HS) {
-      if (fast) { OLAP_GTILE(true); return hipGetLastError(); }
-    }
-    OLAP_GTILE(false);
+    case FORM_GTILE: {
+      const size_t lds = kTileBytes + (HS ? kTileBytes / sizeof(T) * 4 : 0) + (kGroupTileMaxGroups + 1) * 4;
+      const uint64_t n_cells = a.outer * a.K * a.inner;
+#define OLAP_GTILE(F) hipLaunchKernelGGL((drillup_gtile_kernel<T, METHOD, HS, F>), dim3((unsigned)c.blocks, nb), kBlock, lds, stream, b, a, n_cells)
+      OLAP_FAST_OR_NOT(OLAP_GTILE);
 #undef OLAP_GTILE
-    return hipGetLastError();
-  }
-#define OLAP_ROWS(C, F) hipLaunchKernelGGL((drillup_rows_kernel<T, METHOD, HS, VEC, U, C, F>), dim3((unsigned)row_blocks, nb), row_lanes, 0, stream, b, ar)
-#define OLAP_ROWS1(C, F) hipLaunchKernelGGL((drillup_rows_kernel<T, METHOD, HS, VEC, 1, C, F>), dim3((unsigned)row_blocks, nb), row_lanes, 0, stream, b, ar)
+    }
+    case FORM_ROWS_RAGGED:
+      if constexpr (VEC * sizeof(T) < 16) {
+        constexpr int RV = 16 / sizeof(T);
+#define OLAP_RAGGED(C, F) hipLaunchKernelGGL((drillup_rows_kernel<T, METHOD, HS, RV, U, C, F, true, true>), dim3((unsigned)c.blocks, nb), a.lanes, 0, stream, b, a)
+#define OLAP_RAGGED_C(F) if (contig) OLAP_RAGGED(true, F); else OLAP_RAGGED(false, F)
+        OLAP_FAST_OR_NOT(OLAP_RAGGED_C);
+#undef OLAP_RAGGED_C
+#undef OLAP_RAGGED
+      }
+      return hipErrorInvalidValue;  // (only lanes of less than 16 bytes have the form)
+    case FORM_ROWS: {
+#define OLAP_ROWS(UU, C, F) hipLaunchKernelGGL((drillup_rows_kernel<T, METHOD, HS, VEC, UU, C, F>), dim3((unsigned)c.blocks, nb), a.lanes, 0, stream, b, a)
+#define OLAP_ROWS_C(UU, F) if (contig) OLAP_ROWS(UU, true, F); else OLAP_ROWS(UU, false, F)
+      if constexpr (kAdditive && !HS) {
+        if (fast) {
+          if (shallow) OLAP_ROWS_C(1, true); else OLAP_ROWS_C(U, true);
+          return hipGetLastError();
+        }
+      }
+      if constexpr (IsPick<METHOD>::value && !HS) {
+        if (shallow) { OLAP_ROWS_C(1, false); return hipGetLastError(); }
+      }
+      if (HS && shallow) OLAP_ROWS_C(1, false);  // values + mask: two wide streams per row already, one row in flight (155 -> 147 us)
+      else OLAP_ROWS_C(U, false);
+#undef OLAP_ROWS_C
+#undef OLAP_ROWS
+      return hipGetLastError();
+    }
+    case FORM_FLAT: {
 #define OLAP_FLAT(F)                                                                                                                              \
   do {                                                                                                                                             \
     if (a.total < 0xFFFFFF00ull) hipLaunchKernelGGL((drillup_flat_kernel<T, METHOD, HS, VEC, F, uint32_t>), dim3(grid_for(a.total), nb), kBlock, 0, stream, b, a); \
     else hipLaunchKernelGGL((drillup_flat_kernel<T, METHOD, HS, VEC, F, uint64_t>), dim3(grid_for(a.total), nb), kBlock, 0, stream, b, a);                        \
   } while (0)
-  DrillUpAxis ar = a;  // the row regime's own workgroup width
-  ar.blocks_per_row = (a.n_vec + row_lanes - 1) / row_lanes;
-  ar.lanes = row_lanes;
-  ar.grid = rows ? (uint32_t)row_blocks : 0u;
-  if constexpr (VEC * sizeof(T) < 16) {
-    // rows that are not whole 16-byte groups (or buffers that are not 16-byte aligned): 16-byte slots at
-    // cell-aligned addresses instead of 4-byte lanes
-    constexpr int RV = 16 / sizeof(T);
-    static const bool no_ragged = getenv("OLAP_NO_RAGGED_ROWS") != nullptr;
-    // (8-byte lanes — 4-byte cells in rows of an even, not fourfold, number of cells — too: [3652,100,274] city -> country
-    // 79-82 us with 8-byte lanes, 76 us with these; OLAP_NO_RAGGED_VEC2 keeps the 8-byte lanes)
-    static const bool no_ragged2 = getenv("OLAP_NO_RAGGED_VEC2") != nullptr;
-    if (rows && !no_ragged && (VEC == 1 || !no_ragged2)) {
-      DrillUpAxis rg = a;
-      rg.n_vec = (a.inner + RV - 1) / RV;
-      unsigned lanes = rows_lanes_for(rg.n_vec);
-      {
-        static const int forced = getenv("OLAP_ROWS_LANES") ? atoi(getenv("OLAP_ROWS_LANES")) : 0;
-        if (forced == 64 || forced == 128 || forced == 256) lanes = (unsigned)forced;
-      }
-      rg.blocks_per_row = (rg.n_vec + lanes - 1) / lanes;
-      rg.lanes = lanes;
-      const uint64_t blocks = a.outer * a.G * rg.blocks_per_row;
-      rg.grid = blocks < 0x7FFFFFFFull ? (uint32_t)blocks : 0u;
-      if (blocks < 0x7FFFFFFFull) {
-#define OLAP_RAGGED(C, F) hipLaunchKernelGGL((drillup_rows_kernel<T, METHOD, HS, RV, U, C, F, true, true>), dim3((unsigned)blocks, nb), lanes, 0, stream, b, rg)
-        if constexpr (kAdditive && !HS) {
-          if (fast) {
-            if (contig) OLAP_RAGGED(true, true); else OLAP_RAGGED(false, true);
-            return hipGetLastError();
-          }
-        }
-        if (contig) OLAP_RAGGED(true, false); else OLAP_RAGGED(false, false);
-#undef OLAP_RAGGED
-        return hipGetLastError();
-      }
-    }
-  }
-  if (rows) {
-    if constexpr (kAdditive && !HS) {
-      if (fast) {
-        if (shallow) { if (contig) OLAP_ROWS1(true, true); else OLAP_ROWS1(false, true); }
-        else { if (contig) OLAP_ROWS(true, true); else OLAP_ROWS(false, true); }
-        return hipGetLastError();
-      }
-    }
-    if constexpr (IsPick<METHOD>::value && !HS) {
-      if (shallow) {
-        if (contig) OLAP_ROWS1(true, false); else OLAP_ROWS1(false, false);
-        return hipGetLastError();
-      }
-    }
-    if (HS && shallow) {  // values + mask: two wide streams per row already, one row in flight (155 -> 147 us)
-      if (contig) OLAP_ROWS1(true, false); else OLAP_ROWS1(false, false);
-      return hipGetLastError();
-    }
-    if (contig) OLAP_ROWS(true, false); else OLAP_ROWS(false, false);
-  } else {
-    if constexpr (kAdditive && !HS) {
-      if (fast) { OLAP_FLAT(true); return hipGetLastError(); }
-    }
-    OLAP_FLAT(false);
-  }
-#undef OLAP_ROWS
-#undef OLAP_ROWS1
+      OLAP_FAST_OR_NOT(OLAP_FLAT);
 #undef OLAP_FLAT
-  return hipGetLastError();
+    }
+    default:
+      return hipErrorInvalidValue;  // (the other forms have launchers of their own)
+  }
+#undef OLAP_FAST_OR_NOT
 }
 
 template <typename T, int METHOD, bool HS>
-static hipError_t drillup_axis_vec(int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, hipStream_t stream) {
-  if (vec == 4) return drillup_axis_launch<T, METHOD, HS, 4>(b, nb, a, stream);
-  if (vec == 2) return drillup_axis_launch<T, METHOD, HS, 2>(b, nb, a, stream);
-  return drillup_axis_launch<T, METHOD, HS, 1>(b, nb, a, stream);
+static hipError_t drillup_axis_vec(int vec, const Batch<T> &b, unsigned nb, const DrillUpChoice &c, hipStream_t stream) {
+  if (vec == 4) return drillup_axis_launch<T, METHOD, HS, 4>(b, nb, c, stream);
+  if (vec == 2) return drillup_axis_launch<T, METHOD, HS, 2>(b, nb, c, stream);
+  return drillup_axis_launch<T, METHOD, HS, 1>(b, nb, c, stream);
 }
 
-template <typename T, bool HS>
-static hipError_t drillup_axis_method(int method, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, hipStream_t stream) {
-  switch (method) {
-    case OLAP_SUM: return drillup_axis_vec<T, OLAP_SUM, HS>(vec, b, nb, a, stream);
-    case OLAP_AVERAGE: return drillup_axis_vec<T, OLAP_AVERAGE, HS>(vec, b, nb, a, stream);
-    case OLAP_HIGHEST: return drillup_axis_vec<T, OLAP_HIGHEST, HS>(vec, b, nb, a, stream);
-    case OLAP_LOWEST: return drillup_axis_vec<T, OLAP_LOWEST, HS>(vec, b, nb, a, stream);
-    case OLAP_FIRST: return drillup_axis_vec<T, OLAP_FIRST, HS>(vec, b, nb, a, stream);
-    case OLAP_LAST: return drillup_axis_vec<T, OLAP_LAST, HS>(vec, b, nb, a, stream);
-    case OLAP_PARTIAL_AVERAGE: return drillup_axis_vec<T, OLAP_PARTIAL_AVERAGE, HS>(vec, b, nb, a, stream);
-    default: return drillup_axis_vec<T, OLAP_PRODUCT, HS>(vec, b, nb, a, stream);
+// Runs CALL (a statement; it may return) with M naming the rule `method` as a compile-time constant (anything else:
+// OLAP_PRODUCT).  The one rule dispatch of the drillUp launchers.
+#define DISPATCH_METHOD(method, M, CALL)                                                  \
+  switch (method) {                                                                       \
+    case OLAP_SUM: { constexpr int M = OLAP_SUM; CALL; } break;                           \
+    case OLAP_AVERAGE: { constexpr int M = OLAP_AVERAGE; CALL; } break;                   \
+    case OLAP_HIGHEST: { constexpr int M = OLAP_HIGHEST; CALL; } break;                   \
+    case OLAP_LOWEST: { constexpr int M = OLAP_LOWEST; CALL; } break;                     \
+    case OLAP_FIRST: { constexpr int M = OLAP_FIRST; CALL; } break;                       \
+    case OLAP_LAST: { constexpr int M = OLAP_LAST; CALL; } break;                         \
+    case OLAP_PARTIAL_AVERAGE: { constexpr int M = OLAP_PARTIAL_AVERAGE; CALL; } break;   \
+    default: { constexpr int M = OLAP_PRODUCT; CALL; } break;                             \
   }
-}
 
 template <typename T>
-hipError_t Launch<T>::drillup_axis(int method, bool has_status, int vec, const T *in, const int32_t *st_in, T *out,
-                                   int32_t *st_out, const DrillUpAxis &a, hipStream_t stream) {
-  return drillup_axis_batch(method, has_status, vec, Batch<T>::one(in, st_in, out, st_out), 1, a, stream);
-}
-
-template <typename T>
-hipError_t Launch<T>::drillup_axis_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a,
+hipError_t Launch<T>::drillup_axis_batch(int method, bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpChoice &c,
                                          hipStream_t stream) {
-  if (a.total == 0 || nb == 0) return hipSuccess;
-  return has_status ? drillup_axis_method<T, true>(method, vec, b, nb, a, stream)
-                    : drillup_axis_method<T, false>(method, vec, b, nb, a, stream);
+  if (c.axis.total == 0 || nb == 0) return hipSuccess;
+  if (has_status) DISPATCH_METHOD(method, M, return (drillup_axis_vec<T, M, true>(vec, b, nb, c, stream)));
+  DISPATCH_METHOD(method, M, return (drillup_axis_vec<T, M, false>(vec, b, nb, c, stream)));
 }
 
 template <typename T, int VEC>
-static hipError_t drillup_rows_mixed_vec(bool has_status, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, bool deep, hipStream_t stream) {
-  const unsigned row_lanes = rows_lanes_for(a.n_vec);  // (as drillup_axis_launch picks it)
-  DrillUpAxis ar = a;
-  ar.blocks_per_row = (a.n_vec + row_lanes - 1) / row_lanes;
-  ar.lanes = row_lanes;
-  const uint64_t row_blocks = a.outer * a.G * ar.blocks_per_row;
-  if (row_blocks >= 0x7FFFFFFFull) return hipErrorNotSupported;
-  ar.grid = (uint32_t)row_blocks;
-  const bool shallow = !deep && VEC * sizeof(T) >= 16 && a.n_vec >= 1024;
-  const bool contig = a.order == nullptr;
-  const dim3 grid((unsigned)row_blocks, nb);
-#define OLAP_MIXED(HS, UU, C) hipLaunchKernelGGL((drillup_rows_mixed_kernel<T, HS, VEC, UU, C>), grid, row_lanes, 0, stream, b, ar)
+static hipError_t drillup_rows_mixed_vec(bool has_status, const Batch<T> &b, unsigned nb, const DrillUpChoice &c, bool deep, hipStream_t stream) {
+  const DrillUpAxis &ar = c.axis;
+  const bool shallow = !deep && VEC * sizeof(T) >= 16 && ar.n_vec >= 1024;
+  const bool contig = ar.order == nullptr;
+  const dim3 grid((unsigned)c.blocks, nb);
+#define OLAP_MIXED(HS, UU, C) hipLaunchKernelGGL((drillup_rows_mixed_kernel<T, HS, VEC, UU, C>), grid, ar.lanes, 0, stream, b, ar)
+#define OLAP_MIXED_C(HS, UU) if (contig) OLAP_MIXED(HS, UU, true); else OLAP_MIXED(HS, UU, false)
   if (has_status) {
-    if (shallow) { if (contig) OLAP_MIXED(true, 1, true); else OLAP_MIXED(true, 1, false); }
-    else { if (contig) OLAP_MIXED(true, 4, true); else OLAP_MIXED(true, 4, false); }
+    if (shallow) OLAP_MIXED_C(true, 1); else OLAP_MIXED_C(true, 4);
   } else {
-    if (shallow) { if (contig) OLAP_MIXED(false, 1, true); else OLAP_MIXED(false, 1, false); }
-    else { if (contig) OLAP_MIXED(false, 4, true); else OLAP_MIXED(false, 4, false); }
+    if (shallow) OLAP_MIXED_C(false, 1); else OLAP_MIXED_C(false, 4);
   }
+#undef OLAP_MIXED_C
 #undef OLAP_MIXED
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t Launch<T>::drillup_rows_mixed(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpAxis &a, bool deep,
+hipError_t Launch<T>::drillup_rows_mixed(bool has_status, int vec, const Batch<T> &b, unsigned nb, const DrillUpChoice &c, bool deep,
                                          hipStream_t stream) {
   constexpr int FULL = 16 / sizeof(T);
+  const DrillUpAxis &a = c.axis;
   if (a.total == 0 || nb == 0) return hipSuccess;
   // the row regime with 16-byte lanes, or 8-byte lanes of 4-byte cells (rows of an even number of cells: config 5's
-  // [120,100,274] -> country); single cells per lane and the other regimes go rule by rule
+  // [120,100,274] -> country), and the row-tile regime take mixed rules; single cells per lane and the other forms go
+  // rule by rule
   if (!a.aligned16) return hipErrorNotSupported;
-  if (a.n_vec < 128) {  // not the row regime: the row-tile regime takes mixed rules too, the others do not
-    TileGeometry tg;
-    if (!tile_geometry<T>(a, has_status, &tg)) return hipErrorNotSupported;
+  if (c.form == FORM_TILE) {
+    const TileGeometry &tg = c.tile;
     const dim3 grid((unsigned)tg.tiles, nb);
 #define OLAP_TILE_MIXED(HS, M) hipLaunchKernelGGL((drillup_tile_mixed_kernel<T, HS, M>), grid, kBlock, tg.lds, stream, b, a, tg.tl)
-    if (has_status) {
-      switch (tg.mode) {
-        case 1: OLAP_TILE_MIXED(true, 1); break;
-        case 2: OLAP_TILE_MIXED(true, 2); break;
-        case 3: OLAP_TILE_MIXED(true, 3); break;
-        default: OLAP_TILE_MIXED(true, 0); break;
-      }
-    } else {
-      switch (tg.mode) {
-        case 1: OLAP_TILE_MIXED(false, 1); break;
-        case 2: OLAP_TILE_MIXED(false, 2); break;
-        case 3: OLAP_TILE_MIXED(false, 3); break;
-        default: OLAP_TILE_MIXED(false, 0); break;
-      }
-    }
+#define OLAP_TILE_MIXED_MODE(HS) if (tg.mode == 1) OLAP_TILE_MIXED(HS, 1); else if (tg.mode == 2) OLAP_TILE_MIXED(HS, 2); else if (tg.mode == 3) OLAP_TILE_MIXED(HS, 3); else OLAP_TILE_MIXED(HS, 0)
+    if (has_status) OLAP_TILE_MIXED_MODE(true); else OLAP_TILE_MIXED_MODE(false);
+#undef OLAP_TILE_MIXED_MODE
 #undef OLAP_TILE_MIXED
     return hipGetLastError();
   }
-  if (vec == FULL) return drillup_rows_mixed_vec<T, FULL>(has_status, b, nb, a, deep, stream);
+  if (c.form != FORM_ROWS) return hipErrorNotSupported;
+  if (vec == FULL) return drillup_rows_mixed_vec<T, FULL>(has_status, b, nb, c, deep, stream);
   if constexpr (FULL == 4) {
-    if (vec == 2) return drillup_rows_mixed_vec<T, 2>(has_status, b, nb, a, deep, stream);
+    if (vec == 2) return drillup_rows_mixed_vec<T, 2>(has_status, b, nb, c, deep, stream);
   }
   return hipErrorNotSupported;
 }
 
+// The reduce form `c` (drillup_reduce_form): its stage, then the merge of the segments' partials where there is one.
 template <typename T, int METHOD>
-static hipError_t drillup_reduce_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
-                                        const DrillUpAxis &a, const DrillUpReduce &rd, hipStream_t stream) {
+static hipError_t drillup_reduce_launch(bool has_status, const T *in, const int32_t *st_in, T *out, int32_t *st_out, const DrillUpChoice &c,
+                                        hipStream_t stream) {
+  const DrillUpAxis &a = c.axis;
+  const DrillUpReduce &rd = c.reduce;
   const uint64_t cells = a.outer * a.G * a.inner;
   constexpr bool kAdditive = (METHOD == OLAP_SUM || METHOD == OLAP_AVERAGE || METHOD == OLAP_PARTIAL_AVERAGE);
   const bool fast = kAdditive && !has_status && !a.def_nan;
-  // cooperative form: rows of up to 128 cells, or — 16-byte form only — of up to 1 024 (the scalar form gives a lane
-  // one cell of one row per step: rows must fit the unit's lanes; otherwise the lane-per-cell split form below)
-  const bool vec4_now = rd.vec4 && a.aligned16 && (rd.rows > 0 || sizeof(T) == 4);  // (16-byte form: 4 cells of 4 bytes, 2 of 8)
-  if (rd.rows > 0 && (vec4_now || a.inner <= rd.unit)) {
-    const uint64_t upb = kBlock / rd.unit;
-    const unsigned grid = (unsigned)((a.outer * a.G * rd.S + upb - 1) / upb);
-    if (vec4_now) {
-      if (has_status) hipLaunchKernelGGL((drillup_reduce4_kernel<T, METHOD, true, false>), grid, kBlock, 0, stream, in, st_in, out, st_out, a, rd);
-      else if (kAdditive && fast) hipLaunchKernelGGL((drillup_reduce4_kernel<T, METHOD, false, kAdditive>), grid, kBlock, 0, stream, in, st_in, out, st_out, a, rd);
-      else hipLaunchKernelGGL((drillup_reduce4_kernel<T, METHOD, false, false>), grid, kBlock, 0, stream, in, st_in, out, st_out, a, rd);
-      if (rd.S == 1) return hipGetLastError();  // one segment per group: the result left from the reduction
-    } else {
-      DrillUpReduce r1 = rd;
-      if (rd.vec4) {  // plan sized `rows` for 16 B lanes; the scalar form covers unit cells per step
-        uint32_t rows = 1;
-        while ((uint64_t)rows * 2 * a.inner <= rd.unit) rows *= 2;
-        r1.rows = rows;
-      }
-      if (has_status) hipLaunchKernelGGL((drillup_reduce_kernel<T, METHOD, true, false>), grid, kBlock, 0, stream, in, st_in, a, r1);
-      else if (kAdditive && fast) hipLaunchKernelGGL((drillup_reduce_kernel<T, METHOD, false, kAdditive>), grid, kBlock, 0, stream, in, st_in, a, r1);
-      else hipLaunchKernelGGL((drillup_reduce_kernel<T, METHOD, false, false>), grid, kBlock, 0, stream, in, st_in, a, r1);
-    }
-  } else if (rd.rows == 0 && rd.vec4 && a.aligned16 && sizeof(T) == 4 && a.inner % 4 == 0) {  // 16-byte lanes
-    const unsigned grid = grid_for(cells / 4 * rd.S);
-    if (has_status) hipLaunchKernelGGL((drillup_split4_kernel<T, METHOD, true, false>), grid, kBlock, 0, stream, in, st_in, a, rd);
-    else if (kAdditive && fast) hipLaunchKernelGGL((drillup_split4_kernel<T, METHOD, false, kAdditive>), grid, kBlock, 0, stream, in, st_in, a, rd);
-    else hipLaunchKernelGGL((drillup_split4_kernel<T, METHOD, false, false>), grid, kBlock, 0, stream, in, st_in, a, rd);
-  } else {
-    const unsigned grid = grid_for(cells * rd.S);
-    if (has_status) hipLaunchKernelGGL((drillup_split_kernel<T, METHOD, true, false>), grid, kBlock, 0, stream, in, st_in, a, rd);
-    else if (kAdditive && fast) hipLaunchKernelGGL((drillup_split_kernel<T, METHOD, false, kAdditive>), grid, kBlock, 0, stream, in, st_in, a, rd);
-    else hipLaunchKernelGGL((drillup_split_kernel<T, METHOD, false, false>), grid, kBlock, 0, stream, in, st_in, a, rd);
+  const unsigned grid = (unsigned)c.blocks;
+#define OLAP_STAGE(KERNEL, ...)                                                                                                                     \
+  do {                                                                                                                                              \
+    if (has_status) hipLaunchKernelGGL((KERNEL<T, METHOD, true, false>), grid, kBlock, 0, stream, __VA_ARGS__);                                     \
+    else if (kAdditive && fast) hipLaunchKernelGGL((KERNEL<T, METHOD, false, kAdditive>), grid, kBlock, 0, stream, __VA_ARGS__);                    \
+    else hipLaunchKernelGGL((KERNEL<T, METHOD, false, false>), grid, kBlock, 0, stream, __VA_ARGS__);                                               \
+  } while (0)
+  switch (c.form) {
+    case FORM_REDUCE4: OLAP_STAGE(drillup_reduce4_kernel, in, st_in, out, st_out, a, rd); break;
+    case FORM_REDUCE: OLAP_STAGE(drillup_reduce_kernel, in, st_in, a, rd); break;
+    case FORM_SPLIT4: OLAP_STAGE(drillup_split4_kernel, in, st_in, a, rd); break;
+    case FORM_SPLIT: OLAP_STAGE(drillup_split_kernel, in, st_in, a, rd); break;
+    default: return hipErrorInvalidValue;
   }
+#undef OLAP_STAGE
+  if (!c.merge) return hipGetLastError();
   if (rd.S <= 16) hipLaunchKernelGGL((drillup_merge_few_kernel<T, METHOD>), grid_for(cells), kBlock, 0, stream, out, st_out, a, rd);
   else if (rd.S >= 512) hipLaunchKernelGGL((drillup_merge_block_kernel<T, METHOD>), (unsigned)cells, kBlock, 0, stream, out, st_out, a, rd);
   else hipLaunchKernelGGL((drillup_merge_kernel<T, METHOD>), grid_for(cells * 64), kBlock, 0, stream, out, st_out, a, rd);
@@ -4385,18 +4435,9 @@ static hipError_t drillup_reduce_launch(bool has_status, const T *in, const int3
 
 template <typename T>
 hipError_t Launch<T>::drillup_reduce(int method, bool has_status, const T *in, const int32_t *st_in, T *out,
-                                     int32_t *st_out, const DrillUpAxis &a, const DrillUpReduce &rd, hipStream_t stream) {
-  if (a.outer * a.G * a.inner == 0) return hipSuccess;
-  switch (method) {
-    case OLAP_SUM: return drillup_reduce_launch<T, OLAP_SUM>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_AVERAGE: return drillup_reduce_launch<T, OLAP_AVERAGE>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_HIGHEST: return drillup_reduce_launch<T, OLAP_HIGHEST>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_LOWEST: return drillup_reduce_launch<T, OLAP_LOWEST>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_FIRST: return drillup_reduce_launch<T, OLAP_FIRST>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_LAST: return drillup_reduce_launch<T, OLAP_LAST>(has_status, in, st_in, out, st_out, a, rd, stream);
-    case OLAP_PARTIAL_AVERAGE: return drillup_reduce_launch<T, OLAP_PARTIAL_AVERAGE>(has_status, in, st_in, out, st_out, a, rd, stream);
-    default: return drillup_reduce_launch<T, OLAP_PRODUCT>(has_status, in, st_in, out, st_out, a, rd, stream);
-  }
+                                     int32_t *st_out, const DrillUpChoice &c, hipStream_t stream) {
+  if (c.axis.outer * c.axis.G * c.axis.inner == 0) return hipSuccess;
+  DISPATCH_METHOD(method, M, return (drillup_reduce_launch<T, M>(has_status, in, st_in, out, st_out, c, stream)));
 }
 
 template <typename T>
@@ -4417,7 +4458,8 @@ hipError_t Launch<T>::drillup_segmented(int method, bool has_status, int vec, co
   a1.depth = 4;                // few, long workgroups (two per CU): four rows in flight per lane
   const bool want_aux = additive ? (method == OLAP_AVERAGE || a.def_nan || mask_primary) : mask_primary;
   int32_t *aux = want_aux ? sg.aux : nullptr;
-  hipError_t e = drillup_axis(additive ? OLAP_PARTIAL_AVERAGE : method, has_status, vec, in, st_in, (T *)sg.partial, aux, a1, stream);
+  hipError_t e = drillup_axis_batch(additive ? OLAP_PARTIAL_AVERAGE : method, has_status, vec, Batch<T>::one(in, st_in, (T *)sg.partial, aux), 1,
+                                    drillup_axis_form(a1, vec, sizeof(T), has_status), stream);
   if (e != hipSuccess) return e;
   // stage 2: a group's segments folded in order
   const uint64_t blocks = a.outer * a.G * ((a.inner + 63) / 64);
@@ -4439,18 +4481,7 @@ template <typename T, bool HS>
 static hipError_t drillup_generic_method(int method, const T *in, const int32_t *st_in, T *out, int32_t *st_out,
                                          const DrillUpGeneric &a, hipStream_t stream) {
   const unsigned grid = grid_for(a.total);
-#define OLAP_GEN(M) hipLaunchKernelGGL((drillup_generic_kernel<T, M, HS>), grid, kBlock, 0, stream, in, st_in, out, st_out, a)
-  switch (method) {
-    case OLAP_SUM: OLAP_GEN(OLAP_SUM); break;
-    case OLAP_AVERAGE: OLAP_GEN(OLAP_AVERAGE); break;
-    case OLAP_HIGHEST: OLAP_GEN(OLAP_HIGHEST); break;
-    case OLAP_LOWEST: OLAP_GEN(OLAP_LOWEST); break;
-    case OLAP_FIRST: OLAP_GEN(OLAP_FIRST); break;
-    case OLAP_LAST: OLAP_GEN(OLAP_LAST); break;
-    case OLAP_PARTIAL_AVERAGE: OLAP_GEN(OLAP_PARTIAL_AVERAGE); break;
-    default: OLAP_GEN(OLAP_PRODUCT); break;
-  }
-#undef OLAP_GEN
+  DISPATCH_METHOD(method, M, hipLaunchKernelGGL((drillup_generic_kernel<T, M, HS>), grid, kBlock, 0, stream, in, st_in, out, st_out, a));
   return hipGetLastError();
 }
 
@@ -4805,6 +4836,7 @@ hipError_t Launch<T>::set_cell(T *values, int32_t *status, uint64_t index, doubl
   return hipGetLastError();
 }
 
+#undef DISPATCH_METHOD
 #endif  // OLAP_KERNELS_IMPL
 
 }  // namespace olap

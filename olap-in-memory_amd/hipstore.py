@@ -273,6 +273,12 @@ class Plan:
     def kernel_name(self):
         return capi.lib().olap_plan_kernel_name(self._h).decode()
 
+    def describe(self):
+        """The scalars the plan decided, one line of key=value pairs (olap_diag_plan_describe)."""
+        buf = C.create_string_buffer(512)
+        check(capi.lib().olap_diag_plan_describe(self._h, buf, len(buf)))
+        return buf.value.decode()
+
     def run(self, in_values, in_status, out_values, out_status, stream=None):
         """All four are integer device addresses (0/None = absent); stream = hipStream_t address."""
         check(capi.lib().olap_plan_run(self._h, in_values or None, in_status or None, out_values or None,
