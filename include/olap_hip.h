@@ -611,6 +611,39 @@ int olap_store_rolling_multi(int n, const olap_store *const *stores, const int *
  * map travels (it does not change the cuts today). */
 int olap_diag_rolling_choice(int cell_bytes, uint64_t outer, uint64_t K, uint64_t inner, int32_t before, int32_t after,
                              int has_map, uint32_t choice[4]);
+/* Order statistics along one dimension (Cube.quantile, Cube.median) of n stores, with the arguments, the grouping into
+ * launches and the mask handling of olap_store_cumulate_multi, and no `methods` list: a measure's rule is not consulted.
+ * out[i] is a new store of outer * G * inner cells — outer and inner the products of the lengths before and after
+ * `axis`, G = n_groups (1 when map is NULL) — of the type and default of stores[i].  Its cell (o, g, i) holds the
+ * q-quantile of the SET cells (o, k, i) with map[k] == g; a group nobody maps to, or without a set cell, gives an unset
+ * cell.  With the n members sorted ascending by the IEEE total order on values (-0 before +0, every NaN last) as
+ * float64 v[0..n):  h = q * (n - 1), lo = floor(h), frac = h - lo, and the cell is v[lo] + frac * (v[lo + 1] - v[lo])
+ * where frac > 0 and v[lo] otherwise — every operation rounded on its own, nothing fused — converted to the cell type
+ * once, as every other operation converts; a result equal to the default is unset; a NaN result is the one quiet NaN
+ * (0x7FF8000000000000 before the conversion).  Selection is exact (olap_quantile.hip): the two order statistics are
+ * found by counting on an order-preserving integer key of the cell and decoded from their keys.
+ * Cost: where the rows of the largest group (or, for rows of fewer than four 16-byte slots, a whole series) fit a tile
+ * of 32 KiB of LDS, every cell is read from device memory once and selected out of LDS; beyond that the selection reads
+ * the group straight from device memory once per pass (34 passes for 4-byte cells, 66 for Float64) — no shape goes to
+ * the host.  olap_diag_quantile_choice tells which.
+ * Stores that share cell type, default and device share one plan; q is NOT part of the plan-cache key (it travels as
+ * a launch argument).  *launches as olap_store_cumulate_multi counts them.  Checked on the host before any device work,
+ * in cumulate's order and with cumulate's messages (`quantile` in place of `cumulate`; the list message is "store list
+ * is NULL"); after the axis and before the groups: q outside [0, 1], NaN included (OLAP_ERR_INVALID_ARGUMENT,
+ * "quantile: q must lie in [0, 1] (got %g)").  One deliberate difference: a store that tracks its insertion order is
+ * ACCEPTED — a quantile does not depend on order, and values and mask are dense whatever the order; the result is an
+ * ordinary untracked store.  On an error no store is created.  The stores are only read. */
+int olap_store_quantile_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens,
+                              int axis, double q, uint32_t n_groups, const uint32_t *map, int *launches);
+/* What olap_store_quantile_multi's planner chooses for cells of cell_bytes (4 or 8; has_mask: integer cells under a
+ * NaN default, whose mask tile shares the LDS) in the view [outer, K, inner] with n_groups groups, the largest of
+ * `longest` members — host only, no device needed.  choice: the form (0: column, 1: row, 2: direct, a lane per output
+ * cell, 3: direct, a workgroup per output cell), the cells a tile may hold (OLAP_QUANTILE_TILE lowers it), series per
+ * tile and LDS pitch between two series (row form), cells per tile row and rows per tile (column form); 0 where a
+ * form does not use a cut.  contiguous: whether every group is a run of neighbouring items (it does not change the
+ * cuts today: interleaved groups are staged member by member). */
+int olap_diag_quantile_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner,
+                              uint32_t n_groups, uint32_t longest, int contiguous, uint32_t choice[6]);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU: a cube partitioned along its OUTERMOST dimension.  Row-major layout

@@ -216,6 +216,36 @@ OLAP_INTERNAL void rolling_choose(RollingView &v, int cell_bytes);
 OLAP_INTERNAL hipError_t launch_rolling(int dtype, bool has_status, int nb, const int *methods, const void *const *in, const int32_t *const *st_in,
                                         void *const *out, int32_t *const *st_out, const RollingView &v, hipStream_t stream);
 
+// ---- order statistics along one axis (olap_quantile.hip, K15) --------------------------------------
+// View [outer, K, inner] with one K -> G map as the CSR of CumulateView; the result is [outer, G, inner].
+constexpr uint32_t kQuantileTileBytes = 32768;  // LDS of one tile: cells, and their mask where it is primary
+enum QuantileForm { QUANTILE_COLUMN = 0, QUANTILE_ROW = 1, QUANTILE_DIRECT_LANES = 2, QUANTILE_DIRECT_BLOCK = 3 };
+struct QuantileView {
+  uint64_t outer, K, inner, G;
+  const uint32_t *gstart;  // device, [G + 1]
+  const uint32_t *order;   // device, [K], or nullptr
+  const uint32_t *gtile;   // device, [n_gtile + 1]: column form, tile t holds the groups [gtile[t], gtile[t + 1])
+  int def_nan;
+  int form;                // QuantileForm
+  uint32_t tile;           // cells a tile may hold (kQuantileTileBytes' worth, or OLAP_QUANTILE_TILE)
+  uint32_t longest;        // members of the largest group
+  uint32_t series;         // row form: series per tile
+  uint32_t pitch;          // row form: cells between two series of a tile (odd)
+  uint32_t cols;           // column form: cells of `inner` per tile row
+  uint32_t rows;           // column form: rows a tile may hold
+  uint32_t n_gtile;        // column form: tiles of groups per (outer, slice of inner)
+  uint32_t team;           // tiled forms: neighbouring lanes of a wave that share one output cell's walk (a power of two)
+};
+// cells of one tile for cells of cell_bytes (4 or 8), with a mask tile beside them or not; OLAP_QUANTILE_TILE lowers it
+OLAP_INTERNAL uint32_t quantile_tile_cells(int cell_bytes, bool has_mask);
+// chooses form and tile cuts from the shape, the tile and the largest group alone; fills everything but the tables
+OLAP_INTERNAL void quantile_choose(QuantileView &v, int cell_bytes);
+// the column form's cut of the groups into tiles of at most v.rows rows (host CSR; needs v.rows >= the largest group)
+OLAP_INTERNAL std::vector<uint32_t> quantile_group_tiles(const QuantileView &v, const uint32_t *gstart);
+// nb <= 8 pairs of one cell type and default; masks on all pairs or on none
+OLAP_INTERNAL hipError_t launch_quantile(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
+                                         int32_t *const *st_out, const QuantileView &v, double q, hipStream_t stream);
+
 // ---- insertion order of tracked stores (olap_order.hip) --------------------------------------------
 OLAP_INTERNAL void order_free(olap_store *s);
 OLAP_INTERNAL int order_clone(const olap_store *from, olap_store *to);

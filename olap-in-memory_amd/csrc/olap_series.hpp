@@ -1,5 +1,5 @@
 // olap_series.hpp — what the kernels that walk series along one dimension share (olap_cumulate.hip, K13;
-// olap_rolling.hip, K14): the per-pair rule dispatch, 16-byte slots at cell-aligned addresses and the move of
+// olap_rolling.hip, K14; olap_quantile.hip, K15): the per-pair rule dispatch, 16-byte slots at cell-aligned addresses and the move of
 // contiguous pieces between global memory and an LDS tile.
 #pragma once
 
@@ -52,16 +52,16 @@ __device__ __forceinline__ void store_slot(T *p, const Vec<T, VEC> &x, int n) {
 }
 
 // Moves `ns` pieces of `seg` contiguous cells between global memory and an LDS tile: piece s starts at cell
-// first_cell + s * piece_stride in global memory and at s * pitch in the tile.  Read and written in 16-byte slots (the
-// last slot of a piece cell by cell).
+// first_cell + s * piece_stride in global memory (`piece` given: first_cell + piece[s] * piece_stride) and at s * pitch
+// in the tile.  Read and written in 16-byte slots (the last slot of a piece cell by cell).
 template <typename T, int VEC, bool LOAD>
 __device__ __forceinline__ void tile_move(T *tile, const T *src, T *dst, uint64_t first_cell, uint64_t piece_stride, uint32_t ns, uint32_t seg,
-                                          uint32_t pitch) {
+                                          uint32_t pitch, const uint32_t *piece = nullptr) {
   const uint32_t slots = (seg + VEC - 1) / VEC;
   for (uint32_t c = threadIdx.x; c < ns * slots; c += kBlock) {
     const uint32_t s = c / slots, r = (c % slots) * VEC;
     const int n = (int)(seg - r < (uint32_t)VEC ? seg - r : (uint32_t)VEC);
-    const uint64_t at = first_cell + (uint64_t)s * piece_stride + r;
+    const uint64_t at = first_cell + (uint64_t)(piece ? piece[s] : s) * piece_stride + r;
     T *cell = tile + s * pitch + r;
     if constexpr (LOAD) {
       const Vec<T, VEC> x = load_slot<T, VEC>(src + at, n);

@@ -906,6 +906,119 @@ class Cube {
     }, 'share', (id) => ids.includes(id));
   }
 
+  // ------------------------------------------------------------------ order statistics
+  /** the checks quantile and _quantileHost share; returns the dimension's index */
+  _checkQuantile(dimensionId, attribute, q) {
+    const index = this._checkAlong('quantile', dimensionId, attribute);
+    if (typeof q !== 'number' || !(q >= 0 && q <= 1)) throw new Error('quantile: q must lie in [0, 1]');
+    return index;
+  }
+
+  /**
+   * Order-statistic roll-up of one dimension (the median day of a month, the p90 of a region): a new cube with the
+   * dimensions of drillUp(dimensionId, attribute), the same rules and computed measures, in which every stored
+   * measure's cell holds the q-quantile of the SET cells of its group along that dimension, all other coordinates
+   * fixed — linear interpolation between the two neighbouring order statistics (_quantileHost is the definition).  The
+   * measure's rule for the dimension is not consulted: `median` is not an eighth rule, it is this call.  A group
+   * without a set cell gives an unset cell; the root attribute gives a clone (every group has one member).  This cube
+   * is untouched.
+   * The stored measures go to the device in one call (HipStore.quantileMany -> olap_store_quantile_multi, K15), tracked
+   * ones included; sharded measures and stores of another class are selected on the host (_quantileHost).
+   * HipStore.lastQuantilePath says what ran.
+   */
+  quantile(dimensionId, attribute, q) {
+    const index = this._checkQuantile(dimensionId, attribute, q);
+    const current = this.dimensions[index];
+    if (current.rootAttribute === attribute) return this.clone();
+    const newDimensions = this._withDimension(index, current.drillUp(attribute));
+    const ids = this.storedMeasureIds;
+    const made = {};
+    HipStore.lastQuantilePath = 'host';
+    if (ids.length > 0) {
+      const results = HipStore.quantileMany(ids.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute, q);
+      ids.forEach((id, i) => {
+        if (results[i]) made[id] = results[i];
+      });
+    }
+    const rest = ids.filter((id) => !made[id]);
+    const onHost = rest.length > 0 ? this._quantileHost(dimensionId, attribute, q, rest) : null;
+    return this._derive(newDimensions, (store, id) => {
+      if (!made[id]) return onHost.storedMeasures[id];
+      // (the device's result is an ordinary store: the order is kept from here on where the rules ask for it, as _newStore does)
+      if (Object.values(this.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last')) made[id].trackOrder();
+      return made[id];
+    });
+  }
+
+  /** quantile(dimensionId, attribute, 0.5) */
+  median(dimensionId, attribute) {
+    return this.quantile(dimensionId, attribute, 0.5);
+  }
+
+  /**
+   * The definition of quantile, written out; also the path of the measures the device call does not take.  For one
+   * output cell: (1) the members are the cells of the group's items that are set, as float64; none: the cell is unset;
+   * (2) sorted ascending by the IEEE total order on values (-0 before +0), every NaN last; (3) h = q * (n - 1),
+   * lo = floor(h), frac = h - lo; (4) frac > 0: v[lo] + frac * (v[lo + 1] - v[lo]) — one subtraction, one
+   * multiplication, one addition — otherwise v[lo]; (5) converted to the store's cell type once (the `data` setter),
+   * a result equal to the default being unset.
+   */
+  _quantileHost(dimensionId, attribute, q, measureIds = null) {
+    const index = this._checkQuantile(dimensionId, attribute, q);
+    const current = this.dimensions[index];
+    const ids = measureIds || this.storedMeasureIds;
+    if (current.rootAttribute === attribute) return this.clone(measureIds || []);
+    const rolled = current.drillUp(attribute);
+    const newDimensions = this._withDimension(index, rolled);
+    const groups = current.getGroupIndexFromRootIndexMap(attribute);
+    const K = current.numItems;
+    const G = rolled.numItems;
+    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
+    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
+    const members = Array.from({ length: G }, () => []);
+    for (let k = 0; k < K; ++k) members[groups[k]].push(k);
+    // NaN last, -0 before +0, the rest by value
+    const ascending = (a, b) => {
+      if (Number.isNaN(a) || Number.isNaN(b)) return (Number.isNaN(a) ? 1 : 0) - (Number.isNaN(b) ? 1 : 0);
+      if (a === b) return (Object.is(a, -0) ? 0 : 1) - (Object.is(b, -0) ? 0 : 1);
+      return a < b ? -1 : 1;
+    };
+    const target = new Cube(newDimensions);
+    return this._derive(newDimensions, (store, id) => {
+      const cells = store.data;
+      const set = new Uint8Array(cells.length); // the status map: the keys of the set cells
+      for (const at of store._dataMap.keys()) set[at] = 1;
+      const values = new Array(outer * G * inner).fill(store._defaultValue);
+      for (let o = 0; o < outer; ++o) {
+        for (let g = 0; g < G; ++g) {
+          for (let i = 0; i < inner; ++i) {
+            const v = [];
+            for (const k of members[g]) {
+              const at = (o * K + k) * inner + i;
+              if (set[at]) v.push(cells[at]);
+            }
+            if (v.length === 0) continue;
+            v.sort(ascending);
+            const h = q * (v.length - 1);
+            const lo = Math.floor(h);
+            const frac = h - lo;
+            let r = v[lo];
+            if (frac > 0) {
+              const d = v[lo + 1] - r;
+              const m = frac * d;
+              r += m;
+            }
+            values[(o * G + g) * inner + i] = r;
+          }
+        }
+      }
+      const rules = this.storedMeasuresRules[id];
+      const fresh = store instanceof HipStore ? target._newStore(store._type, store._defaultValue, rules) : new store.constructor(outer * G * inner, store._type, store._defaultValue);
+      fresh.data = values;
+      return fresh;
+    }, 'share', (id) => ids.includes(id));
+  }
+
   // ------------------------------------------------------------------ dice / slice
   _diced(index, dimension) {
     // eslint-disable-next-line eqeqeq

@@ -897,6 +897,50 @@ class HipStore {
       (addon, natives, codes, lens, groups, nGroups, launchesOut) => addon.rollingMulti(natives, codes, lens, index, before, after, groups, nGroups, launchesOut));
   }
 
+  /**
+   * The q-quantile along dimension `index` of the stored measures of one cube, group by group under `attribute` —
+   * Cube.quantile: new stores over the dimensions of drillUp(dimension, attribute) whose cell holds the quantile (linear
+   * interpolation between the two neighbouring order statistics; Cube._quantileHost is the definition) of the SET cells
+   * of its group.  A measure's rule is not consulted and its insertion order does not matter, so measures held whole on
+   * one device — tracked or not — with cells of their declared type's cell type (an integer measure in Float64 cells
+   * keeps a median of 1.5) go to the device in ONE call (addon quantileMulti -> olap_store_quantile_multi: one launch
+   * for up to 8 measures of one cell type and default; DESIGN.md §3 K15).  Pending selections are diced together first
+   * (materializeMany).  Returns the new stores in the order given, with null for a measure the call does not take
+   * (sharded, a store of another class, an addon without the call): the caller takes the host path.  Sets
+   * HipStore.lastBatchLaunches and HipStore.lastQuantilePath ('device' when the call ran).
+   */
+  static quantileMany(stores, dimensions, index, attribute, q) {
+    const out = new Array(stores.length).fill(null);
+    const addon = backend.load();
+    HipStore.lastQuantilePath = 'host';
+    if (typeof addon.quantileMulti !== 'function') return out;
+    const mine = stores.filter((store) => store instanceof HipStore);
+    HipStore.materializeMany(mine);
+    let launches = HipStore.lastBatchLaunches;
+    const whole = (native) => !!native && !native.isSharded;
+    // (a selection alone in its group stays pending there, host-resident cells have no device store yet: both get one now)
+    for (const store of mine) {
+      if (store._pending ? whole(store._pending.source) : !store._nativeStore) store._materialize();
+    }
+    const together = [];
+    stores.forEach((store, i) => {
+      if (store instanceof HipStore && whole(heldStore(store)) && store._cells === cellTypeOf(store._type)) together.push(i);
+    });
+    if (together.length > 0) {
+      const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
+      const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
+      const launchesOut = new Int32Array(1);
+      const made = addon.quantileMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(dimensions), index, q, groups, nGroups, launchesOut);
+      together.forEach((i, j) => {
+        out[i] = stores[i]._wrap(made[j]);
+      });
+      launches += launchesOut[0];
+      HipStore.lastQuantilePath = 'device';
+    }
+    HipStore.lastBatchLaunches = launches;
+    return out;
+  }
+
   /** in-memory.js:139-176 — mutates this store */
   load(otherStore, myDimensions, hisDimensions) {
     this._loadWith(otherStore, lengthsOf(myDimensions), lengthsOf(hisDimensions), loadTables(myDimensions, hisDimensions));
@@ -1080,6 +1124,9 @@ HipStore.lastComposeCalls = 0;
 HipStore.lastCumulatePath = null;
 // the same for the last Cube.rolling / Cube.shift (rollingMulti, Cube._rollingPerItem)
 HipStore.lastRollingPath = null;
+// what the last Cube.quantile / Cube.median did: 'device' when at least one measure left through quantileMulti, 'host' when every
+// measure was selected on the host (Cube._quantileHost)
+HipStore.lastQuantilePath = null;
 
 /**
  * What cumulateMany and rollingMany share (`call`: the addon's many-call `name`): the measures held whole on one device,
