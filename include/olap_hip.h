@@ -265,6 +265,9 @@ int olap_diag_tile_placement(int dtype, uint32_t K, uint32_t G, uint32_t inner, 
  * longest_group, the reduce regime's S (and, where it is not 0, unit rows seg_len vec4 edge), the segmented rows' S_tot
  * and, for the tile form, its mode, rows per tile and LDS bytes.  Every other plan tells its kind and kernel name. */
 int olap_diag_plan_describe(const olap_plan *plan, char *buf, size_t cap);
+/* Diagnostic, host-only: the number of plans the plan cache of the store-level calls holds now (at most 128).  A call
+ * whose key is in the cache leaves it unchanged: for tests of what a plan-cache key holds and what it does not. */
+int olap_diag_plan_cache_count(void);
 /* `total` getter (in-memory.js:22-28): float64 sum of the set cells, and their count.
  * Synchronises `stream`. */
 int olap_total(const void *values, const int32_t *status, uint64_t n, int dtype, int default_kind,
@@ -643,6 +646,45 @@ int olap_store_quantile_multi(int n, const olap_store *const *stores, olap_store
  * form does not use a cut.  contiguous: whether every group is a run of neighbouring items (it does not change the
  * cuts today: interleaved groups are staged member by member). */
 int olap_diag_quantile_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner,
+                              uint32_t n_groups, uint32_t longest, int contiguous, uint32_t choice[6]);
+/* Dispersion along one dimension (Cube.variance, Cube.stddev) of n stores, with the arguments, the grouping into
+ * launches and the mask handling of olap_store_quantile_multi: no `methods` list, a measure's rule is not consulted.
+ * out[i] is a new store of outer * G * inner cells of the type and default of stores[i].  Its cell (o, g, i) holds the
+ * variance (kind 0) or the standard deviation (kind 1) of the SET cells (o, k, i) with map[k] == g, by two passes in
+ * float64 — never E[x^2] - E[x]^2.  With the n members in ascending item order as float64 v[0..n):  n - ddof <= 0
+ * gives an unset cell (a group nobody maps to, a group without a set cell, one member with ddof 1); otherwise
+ * s = v[0], s += v[k];  mean = s / n;  m2 = 0, d = v[k] - mean, p = d * d, m2 += p;  r = m2 / (n - ddof);  kind 1:
+ * r = sqrt(r) — every operation rounded on its own, nothing fused — converted to the cell type once, as every other
+ * operation converts; a NaN result is the one quiet NaN (0x7FF8000000000000 before the conversion); a result equal to
+ * the default is unset.  Two consequences: a variance of 0 (one member, equal members) is an UNSET cell under a 0
+ * default and a SET 0 under a NaN default; a group that contains +-Infinity or a set NaN gives NaN.
+ * Forms (olap_variance.hip; olap_diag_variance_choice tells which): where the rows of the largest group (or, for rows
+ * of fewer than four 16-byte slots, a whole series) fit a tile of 32 KiB of LDS, every cell is read from device memory
+ * once and folded twice out of LDS by one lane per output cell; a group beyond a tile is walked twice straight from
+ * device memory by one lane per output cell.  These three one-lane forms equal the definition bit for bit.  At most
+ * 65536 output cells whose largest group has 1024 members or more take a workgroup per output cell, which adds the
+ * members' sum, then m2, by a tree of fixed shape: this is the one RE-ASSOCIATED form (as the reduce regime K1r is
+ * for drillUp) — its additions are grouped differently from the definition's, so its result may differ from it by
+ * rounding, within 4 * (N u + N^2 k^2 u^2) relative for N members (u = 2^-53, k^2 = 1 + mean^2 / variance: twice the sum
+ * of the two sides' two-pass bounds); the grouping is fixed by the plan and never by timing, no atomics on values, and
+ * a second run gives the same bytes.  No shape goes to the host.
+ * Stores that share cell type, default and device share one plan; kind and ddof are NOT part of the plan-cache key
+ * (they travel as launch arguments).  *launches as olap_store_cumulate_multi counts them.  Checked on the host before
+ * any device work, in cumulate's order and with cumulate's messages (`variance` in place of `cumulate`; the list
+ * message is "store list is NULL"); after the axis and before the groups: kind outside {0, 1} ("variance: kind must be
+ * 0 or 1 (got %d)"), then ddof outside {0, 1} ("variance: ddof must be 0 or 1 (got %d)"), both
+ * OLAP_ERR_INVALID_ARGUMENT.  A store that tracks its insertion order is ACCEPTED — the definition walks item order,
+ * not insertion order, and values and mask are dense; the result is an ordinary untracked store.  On an error no
+ * store is created.  The stores are only read. */
+int olap_store_variance_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens,
+                              int axis, int kind /* 0 variance, 1 stddev */, int ddof, uint32_t n_groups,
+                              const uint32_t *map, int *launches);
+/* What olap_store_variance_multi's planner chooses, with the arguments of olap_diag_quantile_choice — host only, no
+ * device needed.  choice: the form (0: column, 1: row, 2: direct, a lane per output cell, 3: direct, a workgroup per
+ * output cell — the re-associated form), the cells a tile may hold (OLAP_VARIANCE_TILE lowers it), series per tile and
+ * LDS pitch between two series (row form), cells per tile row and rows per tile (column form); 0 where a form does not
+ * use a cut.  contiguous does not change the cuts today: interleaved groups are staged member by member. */
+int olap_diag_variance_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner,
                               uint32_t n_groups, uint32_t longest, int contiguous, uint32_t choice[6]);
 
 /* ------------------------------------------------------------------------------------------

@@ -63,6 +63,7 @@ SIGNATURES = {
     "olap_plan_out_cells": (_u64, [_vp]),
     "olap_plan_kernel_name": (C.c_char_p, [_vp]),
     "olap_diag_plan_describe": (_i32, [_vp, C.c_char_p, _sz]),
+    "olap_diag_plan_cache_count": (_i32, []),
     "olap_plan_run": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "olap_diag_tile_placement": (_i32, [_i32, C.c_uint32, C.c_uint32, C.c_uint32, _pu32, _pu32, _pu32, _pu32]),
     "olap_plan_run_batch": (_i32, [_vp, _i32, _pvp, _pvp, _pvp, _pvp, _vp]),
@@ -124,6 +125,8 @@ SIGNATURES = {
     "olap_diag_rolling_choice": (_i32, [_i32, _u64, _u64, _u64, C.c_int32, C.c_int32, _i32, _pu32]),
     "olap_store_quantile_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _i32, _dbl, C.c_uint32, _pu32, C.POINTER(C.c_int)]),
     "olap_diag_quantile_choice": (_i32, [_i32, _i32, _u64, _u64, _u64, C.c_uint32, C.c_uint32, _i32, _pu32]),
+    "olap_store_variance_multi": (_i32, [_i32, _pvp, _pvp, _i32, _pu32, _i32, _i32, _i32, C.c_uint32, _pu32, C.POINTER(C.c_int)]),
+    "olap_diag_variance_choice": (_i32, [_i32, _i32, _u64, _u64, _u64, C.c_uint32, C.c_uint32, _i32, _pu32]),
     "olap_store_blocks_report": (_i32, [_i32, _pvp, _i32, _pu32, C.POINTER(C.c_uint8), _pdbl, C.POINTER(C.c_int)]),
     "olap_store_select_total": (_i32, [_vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32, _pdbl, C.POINTER(C.c_int)]),
     "olap_store_copy_select": (_i32, [_vp, _vp, _i32, _pu32, _i32, C.POINTER(C.c_int), _pu32, _ppi32]),

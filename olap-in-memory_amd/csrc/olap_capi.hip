@@ -1423,7 +1423,8 @@ static int run_typed(olap_plan *p, const void *in_v, const int32_t *in_s, void *
     case PLAN_CUMULATE:
     case PLAN_ROLLING:
     case PLAN_QUANTILE:
-      break;  // never here: their plans are private to olap_store_cumulate_multi / _rolling_multi / _quantile_multi, which launch them themselves (cumulate_run, rolling_run, quantile_run)
+    case PLAN_VARIANCE:
+      break;  // never here: their plans are private to olap_store_cumulate_multi / _rolling_multi / _quantile_multi / _variance_multi, which launch them themselves
     case PLAN_COMPOSE: {  // a batch of one without a fill
       Remap r = p->remap;
       const int vec = remap_for_launch(r, p->vec, all_aligned16(in, in_s, out, out_s));
@@ -1795,7 +1796,7 @@ extern "C" int olap_diag_tile_placement(int dtype, uint32_t K, uint32_t G, uint3
 
 extern "C" int olap_diag_plan_describe(const olap_plan *p, char *buf, size_t cap) {
   if (!p || !buf || cap == 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "plan describe: NULL argument or empty buffer");
-  static const char *const kinds[] = {"drillup_axis", "drillup_generic", "gather", "load", "drilldown", "brick", "gather_reduce", "compose", "cumulate", "rolling", "quantile"};
+  static const char *const kinds[] = {"drillup_axis", "drillup_generic", "gather", "load", "drilldown", "brick", "gather_reduce", "compose", "cumulate", "rolling", "quantile", "variance"};
   if (p->kind != PLAN_DRILLUP_AXIS) {
     snprintf(buf, cap, "kind=%s kernel=%s", kinds[p->kind], p->kernel_name.c_str());
     return OLAP_OK;
@@ -2597,6 +2598,12 @@ PlanCache &plan_cache() {
 }
 }  // namespace
 
+extern "C" int olap_diag_plan_cache_count(void) {
+  PlanCache &c = plan_cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  return (int)c.map.size();
+}
+
 // Runs a (cached) plan into a freshly allocated store.  Everything is enqueued on the null stream
 // and NOT waited for: later operations are ordered behind it by the stream and every host read is a
 // blocking copy on that stream.  Only a drillDown with distributions is waited for, because its
@@ -3165,31 +3172,36 @@ static int cumulate_run(olap_plan *p, const Pairs &q, const int *rules, int *lau
   return OLAP_OK;
 }
 
-// What the calls that run along one dimension share (cumulate, rolling, quantile; `what` names the call in the
-// messages): the checks, on the host and in the order the header lists them, and the walk over the groups of one cell
-// type and default.  window: rolling's {before, after}, or nullptr.  q: quantile's, or nullptr; that call takes no rules
-// (methods == nullptr) and accepts stores that track their insertion order.
+// What the calls that run along one dimension share (cumulate, rolling, quantile, variance; `what` names the call in
+// the messages): the checks, on the host and in the order the header lists them, and the walk over the groups of one
+// cell type and default.  window: rolling's {before, after}, or nullptr.  q: quantile's, or nullptr; kind_ddof:
+// variance's {kind, ddof}, or nullptr; those two calls take no rules (methods == nullptr) and accept stores that track
+// their insertion order.
 static int check_along_axis(const char *what, int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
-                            const uint32_t *lens, int axis, const int32_t *window, const double *q, uint32_t n_groups, const uint32_t *map) {
-  int rc = q ? check_list(n, stores && out, "store list is NULL") : check_list(n, stores && out && methods, "store / method list is NULL");
+                            const uint32_t *lens, int axis, const int32_t *window, const double *q, const int *kind_ddof, uint32_t n_groups,
+                            const uint32_t *map) {
+  const bool ruled = !q && !kind_ddof;
+  int rc = ruled ? check_list(n, stores && out && methods, "store / method list is NULL") : check_list(n, stores && out, "store list is NULL");
   if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   if ((rc = check_entries(n, stores))) return rc;
-  // the lists, the rules, the lengths, the window or q and the map first: refused without looking into a store
-  for (int i = 0; i < n && !q; ++i)
+  // the lists, the rules, the lengths, the window, q or kind and ddof and the map first: refused without looking into a store
+  for (int i = 0; i < n && ruled; ++i)
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
   if ((rc = check_dims(ndim, lens, lens))) return rc;
   if (axis < 0 || axis >= ndim) return fail(OLAP_ERR_INVALID_ARGUMENT, "axis %d out of range [0, %d)", axis, ndim);
   if (window && (int64_t)window[0] + window[1] < 0)
     return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: empty window (before %d, after %d)", what, window[0], window[1]);
   if (q && !(*q >= 0.0 && *q <= 1.0)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: q must lie in [0, 1] (got %g)", what, *q);
+  if (kind_ddof && (kind_ddof[0] < 0 || kind_ddof[0] > 1)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: kind must be 0 or 1 (got %d)", what, kind_ddof[0]);
+  if (kind_ddof && (kind_ddof[1] < 0 || kind_ddof[1] > 1)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: ddof must be 0 or 1 (got %d)", what, kind_ddof[1]);
   // (more groups than items would only be groups without members, and a table of n_groups + 1 entries to build and upload)
   if (map && n_groups > lens[axis])
     return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: %u groups for the %u items of the dimension", what, n_groups, lens[axis]);
   for (uint32_t k = 0; map && k < lens[axis]; ++k)
     if (map[k] >= n_groups)
       return fail(OLAP_ERR_INDEX_RANGE, "%s map: entry %u = %u is outside the groups (%u)", what, k, map[k], n_groups);
-  if (!q && (rc = check_untracked(n, stores, "its key order needs the per-item chain"))) return rc;
+  if (ruled && (rc = check_untracked(n, stores, "its key order needs the per-item chain"))) return rc;
   if ((rc = check_cells(n, stores, product(lens, ndim)))) return rc;
   for (int i = 1; i < n; ++i)
     if (stores[i]->device != stores[0]->device)
@@ -3219,7 +3231,7 @@ static int run_along_axis(int n, const olap_store *const *stores, const int *met
 extern "C" int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
                                          const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int rc = check_along_axis("cumulate", n, stores, methods, out, ndim, lens, axis, nullptr, nullptr, n_groups, map);
+  const int rc = check_along_axis("cumulate", n, stores, methods, out, ndim, lens, axis, nullptr, nullptr, nullptr, n_groups, map);
   if (rc) return rc;
   return run_along_axis(
       n, stores, methods, out, launches, [&](const olap_store *s0) { return cumulate_key(s0, ndim, lens, axis, n_groups, map); },
@@ -3291,7 +3303,7 @@ extern "C" int olap_store_rolling_multi(int n, const olap_store *const *stores, 
                                         int axis, int32_t before, int32_t after, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
   const int32_t window[2] = {before, after};
-  const int rc = check_along_axis("rolling", n, stores, methods, out, ndim, lens, axis, window, nullptr, n_groups, map);
+  const int rc = check_along_axis("rolling", n, stores, methods, out, ndim, lens, axis, window, nullptr, nullptr, n_groups, map);
   if (rc) return rc;
   return run_along_axis(
       n, stores, methods, out, launches, [&](const olap_store *s0) { return rolling_key(s0, ndim, lens, axis, before, after, n_groups, map); },
@@ -3390,7 +3402,7 @@ static int quantile_plan(olap_plan **out, int dtype, int default_kind, int ndim,
 extern "C" int olap_store_quantile_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens, int axis,
                                          double q, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int rc = check_along_axis("quantile", n, stores, nullptr, out, ndim, lens, axis, nullptr, &q, n_groups, map);
+  const int rc = check_along_axis("quantile", n, stores, nullptr, out, ndim, lens, axis, nullptr, &q, nullptr, n_groups, map);
   if (rc) return rc;
   // the pairs of one group in launches of up to kMaxBatch
   auto run = [q](olap_plan *p, const Pairs &pairs, const int *, int *made) {
@@ -3424,6 +3436,120 @@ extern "C" int olap_diag_quantile_choice(int cell_bytes, int has_mask, uint64_t 
   v.tile = quantile_tile_cells(cell_bytes, has_mask != 0);
   v.longest = longest;
   quantile_choose(v, cell_bytes);
+  choice[0] = (uint32_t)v.form, choice[1] = v.tile, choice[2] = v.series, choice[3] = v.pitch, choice[4] = v.cols, choice[5] = v.rows;
+  return OLAP_OK;
+}
+
+// ---- dispersion along one dimension (Cube.variance, Cube.stddev; kernels: olap_variance.hip) --------------------------
+// (kind and ddof are not in the key: they travel as launch arguments.  The tile and the block cut are: OLAP_VARIANCE_TILE
+// and OLAP_VARIANCE_BLOCK change the cuts)
+static PlanKey variance_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map) {
+  PlanKey key;
+  key.i32('V');
+  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
+  key.u32s(lens, ndim);
+  key.i32((int32_t)variance_tile_cells((int)olap_dtype_size(s->dtype), mask_is_primary(s)));
+  key.i32((int32_t)variance_block_members()), key.i32((int32_t)variance_block_cells());
+  key.i32(map != nullptr);
+  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
+  return key;
+}
+
+static const char *variance_kernel_name(int form) {
+  return form == VARIANCE_COLUMN ? "variance_column_kernel" : form == VARIANCE_ROW ? "variance_rows_kernel"
+         : form == VARIANCE_DIRECT_LANES ? "variance_direct_kernel<lanes>" : "variance_direct_kernel<block>";
+}
+
+// the arguments passed olap_store_variance_multi's checks
+static int variance_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
+                         const uint32_t *map) {
+  *out = nullptr;
+  int rc = require_device();
+  if (rc) return rc;
+  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
+  olap_plan *const p = owner.get();
+  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
+  p->kind = PLAN_VARIANCE;
+  p->dtype = dtype;
+  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
+  p->method = OLAP_SUM;
+  VarianceView &v = p->var;
+  v.outer = product(lens, axis);
+  v.K = lens[axis];
+  v.inner = product(lens + axis + 1, ndim - axis - 1);
+  v.G = map ? n_groups : 1;
+  v.def_nan = p->def_nan;
+  p->in_cells = product(lens, ndim);
+  p->out_cells = v.outer * v.G * v.inner;
+  std::vector<uint32_t> gstart, order;
+  bool contiguous = true;
+  if (map) {
+    build_csr(map, lens[axis], n_groups, gstart, order);
+    for (size_t j = 0; j < order.size(); ++j) contiguous = contiguous && order[j] == j;
+  } else {
+    gstart = {0, lens[axis]};
+  }
+  v.tile = variance_tile_cells((int)olap_dtype_size(dtype), p->def_nan && (dtype == OLAP_INT32 || dtype == OLAP_UINT32));
+  v.block_members = variance_block_members(), v.block_cells = variance_block_cells();
+  v.longest = longest_group(gstart);
+  variance_choose(v, (int)olap_dtype_size(dtype));
+  std::vector<uint32_t> tab(gstart);
+  const size_t order_off = tab.size();
+  if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
+  const size_t gtile_off = tab.size();
+  if (v.form == VARIANCE_COLUMN) {
+    const std::vector<uint32_t> gtile = variance_group_tiles(v, gstart.data());
+    v.n_gtile = (uint32_t)gtile.size() - 1;
+    tab.insert(tab.end(), gtile.begin(), gtile.end());
+  }
+  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
+  v.gstart = (const uint32_t *)p->dev_tab;
+  v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
+  v.gtile = v.form == VARIANCE_COLUMN ? (const uint32_t *)p->dev_tab + gtile_off : nullptr;
+  p->kernel_name = variance_kernel_name(v.form);
+  *out = owner.release();
+  return OLAP_OK;
+}
+
+extern "C" int olap_store_variance_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens, int axis,
+                                         int kind, int ddof, uint32_t n_groups, const uint32_t *map, int *launches) {
+  if (launches) *launches = 0;
+  const int kind_ddof[2] = {kind, ddof};
+  const int rc = check_along_axis("variance", n, stores, nullptr, out, ndim, lens, axis, nullptr, nullptr, kind_ddof, n_groups, map);
+  if (rc) return rc;
+  // the pairs of one group in launches of up to kMaxBatch
+  auto run = [kind, ddof](olap_plan *p, const Pairs &pairs, const int *, int *made) {
+    if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
+    if (p->out_cells == 0) return (int)OLAP_OK;
+    int cur;
+    if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
+    for (int first = 0; first < pairs.n; first += kMaxBatch) {
+      const int nb = std::min(pairs.n - first, (int)kMaxBatch);
+      const hipError_t e = launch_variance(p->dtype, pairs.masks(), nb, pairs.in_v + first, pairs.in_s + first, pairs.out_v + first,
+                                           pairs.out_s + first, p->var, kind, ddof, nullptr);
+      if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+      *made += 1;
+    }
+    return (int)OLAP_OK;
+  };
+  return run_along_axis(
+      n, stores, nullptr, out, launches, [&](const olap_store *s0) { return variance_key(s0, ndim, lens, axis, n_groups, map); },
+      [&](olap_plan **p, const olap_store *s0) { return variance_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, run);
+}
+
+extern "C" int olap_diag_variance_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner, uint32_t n_groups,
+                                         uint32_t longest, int contiguous, uint32_t choice[6]) {
+  if (cell_bytes != 4 && cell_bytes != 8) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: cells of %d bytes", cell_bytes);
+  if (!choice) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: NULL result");
+  if (K > 0xFFFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: a dimension of more than 2^32 - 1 items");
+  if (longest > K) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: a group of %u of the dimension's %llu items", longest, (unsigned long long)K);
+  (void)contiguous;  // interleaved groups are staged member by member: the cuts are the same
+  VarianceView v{};
+  v.outer = outer, v.K = K, v.inner = inner, v.G = n_groups;
+  v.tile = variance_tile_cells(cell_bytes, has_mask != 0);
+  v.block_members = variance_block_members(), v.block_cells = variance_block_cells();
+  v.longest = longest;
+  variance_choose(v, cell_bytes);
   choice[0] = (uint32_t)v.form, choice[1] = v.tile, choice[2] = v.series, choice[3] = v.pitch, choice[4] = v.cols, choice[5] = v.rows;
   return OLAP_OK;
 }

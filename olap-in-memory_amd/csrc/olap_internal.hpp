@@ -246,6 +246,43 @@ OLAP_INTERNAL std::vector<uint32_t> quantile_group_tiles(const QuantileView &v, 
 OLAP_INTERNAL hipError_t launch_quantile(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
                                          int32_t *const *st_out, const QuantileView &v, double q, hipStream_t stream);
 
+// ---- dispersion along one axis (olap_variance.hip, K16) --------------------------------------------
+// View [outer, K, inner] with one K -> G map as the CSR of CumulateView; the result is [outer, G, inner].
+constexpr uint32_t kVarianceTileBytes = 32768;    // LDS of one tile: cells, and their mask where it is primary
+constexpr uint32_t kVarianceBlockCells = 65536;   // at most this many output cells ...
+constexpr uint32_t kVarianceBlockMembers = 1024;  // ... of groups at least this long go to a workgroup each (DESIGN K16; OLAP_VARIANCE_BLOCK)
+// VARIANCE_DIRECT_BLOCK is the one RE-ASSOCIATED form: a workgroup adds a group's members up by a tree of fixed shape
+enum VarianceForm { VARIANCE_COLUMN = 0, VARIANCE_ROW = 1, VARIANCE_DIRECT_LANES = 2, VARIANCE_DIRECT_BLOCK = 3 };
+struct VarianceView {
+  uint64_t outer, K, inner, G;
+  const uint32_t *gstart;  // device, [G + 1]
+  const uint32_t *order;   // device, [K], or nullptr
+  const uint32_t *gtile;   // device, [n_gtile + 1]: column form, tile t holds the groups [gtile[t], gtile[t + 1])
+  int def_nan;
+  int form;                // VarianceForm
+  uint32_t tile;           // cells a tile may hold (kVarianceTileBytes' worth, or OLAP_VARIANCE_TILE)
+  uint32_t block_members;  // members of the largest group from which few output cells take a workgroup each
+  uint32_t block_cells;    // ... and how many output cells are few
+  uint32_t longest;        // members of the largest group
+  uint32_t series;         // row form: series per tile
+  uint32_t pitch;          // row form: cells between two series of a tile (odd)
+  uint32_t cols;           // column form: cells of `inner` per tile row
+  uint32_t rows;           // column form: rows a tile may hold
+  uint32_t n_gtile;        // column form: tiles of groups per (outer, slice of inner)
+};
+// cells of one tile for cells of cell_bytes (4 or 8), with a mask tile beside them or not; OLAP_VARIANCE_TILE lowers it
+OLAP_INTERNAL uint32_t variance_tile_cells(int cell_bytes, bool has_mask);
+// kVarianceBlockMembers and kVarianceBlockCells, or OLAP_VARIANCE_BLOCK=members[,cells]
+OLAP_INTERNAL uint32_t variance_block_members();
+OLAP_INTERNAL uint32_t variance_block_cells();
+// chooses form and tile cuts from the shape, the tile and the largest group alone; fills everything but the tables
+OLAP_INTERNAL void variance_choose(VarianceView &v, int cell_bytes);
+// the column form's cut of the groups into tiles of at most v.rows rows (host CSR; needs v.rows >= the largest group)
+OLAP_INTERNAL std::vector<uint32_t> variance_group_tiles(const VarianceView &v, const uint32_t *gstart);
+// nb <= 8 pairs of one cell type and default; masks on all pairs or on none.  kind: 0 variance, 1 stddev; ddof: 0 or 1
+OLAP_INTERNAL hipError_t launch_variance(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
+                                         int32_t *const *st_out, const VarianceView &v, int kind, int ddof, hipStream_t stream);
+
 // ---- insertion order of tracked stores (olap_order.hip) --------------------------------------------
 OLAP_INTERNAL void order_free(olap_store *s);
 OLAP_INTERNAL int order_clone(const olap_store *from, olap_store *to);

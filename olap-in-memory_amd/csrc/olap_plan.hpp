@@ -9,7 +9,7 @@
 #include "olap_internal.hpp"
 #include "olap_kernels.hpp"
 
-enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE, PLAN_ROLLING, PLAN_QUANTILE };
+enum PlanKind { PLAN_DRILLUP_AXIS, PLAN_DRILLUP_GENERIC, PLAN_GATHER, PLAN_LOAD, PLAN_DRILLDOWN, PLAN_BRICK, PLAN_GATHER_REDUCE, PLAN_COMPOSE, PLAN_CUMULATE, PLAN_ROLLING, PLAN_QUANTILE, PLAN_VARIANCE };
 
 struct olap_plan {
   PlanKind kind;
@@ -28,6 +28,7 @@ struct olap_plan {
   CumulateView cum{};                      // PLAN_CUMULATE (olap_cumulate.hip)
   RollingView roll{};                      // PLAN_ROLLING (olap_rolling.hip)
   QuantileView quant{};                    // PLAN_QUANTILE (olap_quantile.hip)
+  VarianceView var{};                      // PLAN_VARIANCE (olap_variance.hip)
   bool xy_ok = false;                      // reorder without a mask: two-axis LDS transpose (olap_transpose.hip; 4- and 8-byte cells)
   TransposeXY xy{};
   olap::DrillUpReduce reduce{};            // S > 0: reduce regime of the one-axis drillUp

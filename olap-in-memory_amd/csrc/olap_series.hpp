@@ -1,5 +1,5 @@
 // olap_series.hpp — what the kernels that walk series along one dimension share (olap_cumulate.hip, K13;
-// olap_rolling.hip, K14; olap_quantile.hip, K15): the per-pair rule dispatch, 16-byte slots at cell-aligned addresses and the move of
+// olap_rolling.hip, K14; olap_quantile.hip, K15; olap_variance.hip, K16): the per-pair rule dispatch, 16-byte slots at cell-aligned addresses and the move of
 // contiguous pieces between global memory and an LDS tile.
 #pragma once
 

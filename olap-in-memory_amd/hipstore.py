@@ -744,6 +744,29 @@ class HipStore:
         check(capi.lib().olap_store_quantile_multi(n, hs, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), float(q), ng, gp, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
+    def variance(self, lens, axis, kind=0, ddof=0, groups=None, n_groups=None):
+        """Variance (kind 0) or standard deviation (kind 1) along dimension `axis` of the cube `lens`
+        (olap_store_variance_multi with one store): a new store of outer * G * inner cells whose cell holds the two-pass
+        variance of the set cells of its group, divided by n - ddof.  `groups`: item -> group (None: one group)."""
+        return HipStore.variance_multi([self], lens, axis, kind, ddof, groups, n_groups)[0][0]
+
+    @staticmethod
+    def variance_multi(stores, lens, axis, kind=0, ddof=0, groups=None, n_groups=None):
+        """Variances of the stored measures of a cube in one call (olap_store_variance_multi): (new stores in order,
+        kernel launches made).  `n_groups` defaults to max(groups) + 1."""
+        lv = _u32(lens)
+        n = len(stores)
+        hs, (outs, launches) = _handles(stores), _new_stores(n)
+        if groups is None:
+            g, gp, ng = None, None, 1
+        else:
+            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
+            gp = g.ctypes.data_as(capi._pu32)
+            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        check(capi.lib().olap_store_variance_multi(n, hs, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), int(kind), int(ddof), ng, gp,
+                                                   C.byref(launches)))
+        return HipStore._multi_result(n, outs, launches)
+
 
 def blocks_report(stores, lens, scanned):
     """Cube.scan / iterateOverDimension for several measures of one cube in one device pass (olap_store_blocks_report):

@@ -1019,6 +1019,122 @@ class Cube {
     }, 'share', (id) => ids.includes(id));
   }
 
+  // ------------------------------------------------------------------ dispersion
+  /** the checks variance, stddev and _varianceHost share; returns the dimension's index */
+  _checkVariance(dimensionId, attribute, ddof) {
+    const index = this._checkAlong('variance', dimensionId, attribute);
+    if (ddof !== 0 && ddof !== 1) throw new Error('variance: ddof must be 0 or 1');
+    return index;
+  }
+
+  /**
+   * Dispersion roll-up of one dimension (the spread of a day's values within its month, the volatility of a region): a
+   * new cube with the dimensions of drillUp(dimensionId, attribute), the same rules and computed measures, in which
+   * every stored measure's cell holds the variance of the SET cells of its group along that dimension, all other
+   * coordinates fixed — two passes in float64, divided by n - ddof (ddof 0: population, 1: sample); _varianceHost is
+   * the definition.  The measure's rule for the dimension is not consulted.  A group with n - ddof <= 0 members gives
+   * an unset cell; a variance of 0 is an unset cell under a 0 default and a set 0 under a NaN default; a group that
+   * contains ±Infinity or a set NaN gives NaN.  The root attribute is not special: every group has one member.  This
+   * cube is untouched.
+   * The stored measures go to the device in one call (HipStore.varianceMany -> olap_store_variance_multi, K16), tracked
+   * ones included; sharded measures and stores of another class are folded on the host (_varianceHost).
+   * HipStore.lastVariancePath says what ran.  On the device, at most 65536 output cells of groups of 1024 members or
+   * more are added up by a workgroup each in a fixed tree (the one re-associated form): such a cell may differ from
+   * _varianceHost's in the last bits, and is the same on every run.
+   */
+  variance(dimensionId, attribute, ddof = 0) {
+    return this._dispersion(dimensionId, attribute, ddof, 0);
+  }
+
+  /** the square root of variance(dimensionId, attribute, ddof), taken in float64 before the one conversion to the cell type */
+  stddev(dimensionId, attribute, ddof = 0) {
+    return this._dispersion(dimensionId, attribute, ddof, 1);
+  }
+
+  /** kind: 0 variance, 1 stddev */
+  _dispersion(dimensionId, attribute, ddof, kind) {
+    const index = this._checkVariance(dimensionId, attribute, ddof);
+    const current = this.dimensions[index];
+    const newDimensions = this._withDimension(index, current.drillUp(attribute));
+    const ids = this.storedMeasureIds;
+    const made = {};
+    HipStore.lastVariancePath = 'host';
+    if (ids.length > 0) {
+      const results = HipStore.varianceMany(ids.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute, kind, ddof);
+      ids.forEach((id, i) => {
+        if (results[i]) made[id] = results[i];
+      });
+    }
+    const rest = ids.filter((id) => !made[id]);
+    const onHost = rest.length > 0 ? this._varianceHost(dimensionId, attribute, ddof, kind, rest) : null;
+    return this._derive(newDimensions, (store, id) => {
+      if (!made[id]) return onHost.storedMeasures[id];
+      // (the device's result is an ordinary store: the order is kept from here on where the rules ask for it, as _newStore does)
+      if (Object.values(this.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last')) made[id].trackOrder();
+      return made[id];
+    });
+  }
+
+  /**
+   * The definition of variance (kind 0) and stddev (kind 1), written out; also the path of the measures the device call
+   * does not take.  For one output cell: (1) the members are the set cells of the group's items, in ascending item
+   * order, as float64 v[0..n); (2) n - ddof <= 0: the cell is unset; (3) s = v[0]; s += v[k]; (4) mean = s / n;
+   * (5) m2 = 0; d = v[k] - mean; p = d * d; m2 += p; (6) r = m2 / (n - ddof); (7) stddev: r = Math.sqrt(r) — every
+   * operation rounded on its own; a NaN result is the one quiet NaN; (8) converted to the store's cell type once (the
+   * `data` setter), a result equal to the default being unset.
+   */
+  _varianceHost(dimensionId, attribute, ddof, kind, measureIds = null) {
+    const index = this._checkVariance(dimensionId, attribute, ddof);
+    if (kind !== 0 && kind !== 1) throw new Error('variance: kind must be 0 or 1');
+    const current = this.dimensions[index];
+    const ids = measureIds || this.storedMeasureIds;
+    const rolled = current.drillUp(attribute);
+    const newDimensions = this._withDimension(index, rolled);
+    const groups = current.getGroupIndexFromRootIndexMap(attribute);
+    const K = current.numItems;
+    const G = rolled.numItems;
+    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
+    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
+    const members = Array.from({ length: G }, () => []);
+    for (let k = 0; k < K; ++k) members[groups[k]].push(k);
+    const target = new Cube(newDimensions);
+    return this._derive(newDimensions, (store, id) => {
+      const cells = store.data;
+      const set = new Uint8Array(cells.length); // the status map: the keys of the set cells
+      for (const at of store._dataMap.keys()) set[at] = 1;
+      const values = new Array(outer * G * inner).fill(store._defaultValue);
+      for (let o = 0; o < outer; ++o) {
+        for (let g = 0; g < G; ++g) {
+          for (let i = 0; i < inner; ++i) {
+            const v = [];
+            for (const k of members[g]) {
+              const at = (o * K + k) * inner + i;
+              if (set[at]) v.push(cells[at]);
+            }
+            const n = v.length;
+            if (n - ddof <= 0) continue;
+            let s = v[0];
+            for (let k = 1; k < n; ++k) s += v[k];
+            const mean = s / n;
+            let m2 = 0;
+            for (let k = 0; k < n; ++k) {
+              const d = v[k] - mean;
+              const p = d * d;
+              m2 += p;
+            }
+            let r = m2 / (n - ddof);
+            if (kind === 1) r = Math.sqrt(r);
+            values[(o * G + g) * inner + i] = r;
+          }
+        }
+      }
+      const rules = this.storedMeasuresRules[id];
+      const fresh = store instanceof HipStore ? target._newStore(store._type, store._defaultValue, rules) : new store.constructor(outer * G * inner, store._type, store._defaultValue);
+      fresh.data = values;
+      return fresh;
+    }, 'share', (id) => ids.includes(id));
+  }
+
   // ------------------------------------------------------------------ dice / slice
   _diced(index, dimension) {
     // eslint-disable-next-line eqeqeq

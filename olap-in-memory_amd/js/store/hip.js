@@ -941,6 +941,50 @@ class HipStore {
     return out;
   }
 
+  /**
+   * The variance (kind 0) or standard deviation (kind 1) along dimension `index` of the stored measures of one cube,
+   * group by group under `attribute` — Cube.variance / Cube.stddev: new stores over the dimensions of
+   * drillUp(dimension, attribute) whose cell holds the two-pass variance, divided by n - ddof, of the SET cells of its
+   * group in item order (Cube._varianceHost is the definition).  A measure's rule is not consulted and its insertion
+   * order does not matter, so measures held whole on one device — tracked or not — with cells of their declared type's
+   * cell type go to the device in ONE call (addon varianceMulti -> olap_store_variance_multi: one launch for up to 8
+   * measures of one cell type and default; DESIGN.md §3 K16).  Pending selections are diced together first
+   * (materializeMany).  Returns the new stores in the order given, with null for a measure the call does not take
+   * (sharded, a store of another class, an addon without the call): the caller takes the host path.  Sets
+   * HipStore.lastBatchLaunches and HipStore.lastVariancePath ('device' when the call ran).
+   */
+  static varianceMany(stores, dimensions, index, attribute, kind, ddof) {
+    const out = new Array(stores.length).fill(null);
+    const addon = backend.load();
+    HipStore.lastVariancePath = 'host';
+    if (typeof addon.varianceMulti !== 'function') return out;
+    const mine = stores.filter((store) => store instanceof HipStore);
+    HipStore.materializeMany(mine);
+    let launches = HipStore.lastBatchLaunches;
+    const whole = (native) => !!native && !native.isSharded;
+    // (a selection alone in its group stays pending there, host-resident cells have no device store yet: both get one now)
+    for (const store of mine) {
+      if (store._pending ? whole(store._pending.source) : !store._nativeStore) store._materialize();
+    }
+    const together = [];
+    stores.forEach((store, i) => {
+      if (store instanceof HipStore && whole(heldStore(store)) && store._cells === cellTypeOf(store._type)) together.push(i);
+    });
+    if (together.length > 0) {
+      const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
+      const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
+      const launchesOut = new Int32Array(1);
+      const made = addon.varianceMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(dimensions), index, kind, ddof, groups, nGroups, launchesOut);
+      together.forEach((i, j) => {
+        out[i] = stores[i]._wrap(made[j]);
+      });
+      launches += launchesOut[0];
+      HipStore.lastVariancePath = 'device';
+    }
+    HipStore.lastBatchLaunches = launches;
+    return out;
+  }
+
   /** in-memory.js:139-176 — mutates this store */
   load(otherStore, myDimensions, hisDimensions) {
     this._loadWith(otherStore, lengthsOf(myDimensions), lengthsOf(hisDimensions), loadTables(myDimensions, hisDimensions));
@@ -1127,6 +1171,9 @@ HipStore.lastRollingPath = null;
 // what the last Cube.quantile / Cube.median did: 'device' when at least one measure left through quantileMulti, 'host' when every
 // measure was selected on the host (Cube._quantileHost)
 HipStore.lastQuantilePath = null;
+// what the last Cube.variance / Cube.stddev did: 'device' when at least one measure left through varianceMulti, 'host' when every
+// measure was folded on the host (Cube._varianceHost)
+HipStore.lastVariancePath = null;
 
 /**
  * What cumulateMany and rollingMany share (`call`: the addon's many-call `name`): the measures held whole on one device,

@@ -1334,6 +1334,37 @@ static napi_value QuantileMulti(napi_env env, napi_callback_info info) {
   return multi_done(env, rc, argc, argv, 6, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
+// varianceMulti(stores: Store[], lens, axis: number, kind: number, ddof: number, groups: Uint32Array | null, nGroups: number, launchesOut?) -> Store[]
+// Dispersion along dimension `axis` (olap_store_variance_multi): new stores of outer * nGroups * inner cells (one group: outer * inner)
+// holding the variance (kind 0) or standard deviation (kind 1) of the set cells of each group, divided by n - ddof; groups[k] < nGroups is
+// the group of item k; null: one group.
+static napi_value VarianceMulti(napi_env env, napi_callback_info info) {
+  const char *usage = "varianceMulti(stores: Store[], lens: Uint32Array, axis: number, kind: number, ddof: number, groups: Uint32Array | null, nGroups: number, launchesOut?: Int32Array)";
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  std::vector<uint32_t> lens, groups;
+  MultiArgs m;
+  bool bad = true;
+  int32_t axis = -1, kind = -1, ddof = -1;
+  uint32_t n_groups = 0;
+  napi_valuetype gt = napi_undefined;
+  if (argc < 7 || !get_u32_vec(env, argv[1], lens) || napi_get_value_int32(env, argv[2], &axis) != napi_ok || napi_get_value_int32(env, argv[3], &kind) != napi_ok ||
+      napi_get_value_int32(env, argv[4], &ddof) != napi_ok || napi_typeof(env, argv[5], &gt) != napi_ok || napi_get_value_uint32(env, argv[6], &n_groups) != napi_ok)
+    return bad_args(env, usage);
+  const bool one_group = gt == napi_null || gt == napi_undefined;
+  if (!one_group && !get_u32_vec(env, argv[5], groups)) return bad_args(env, usage);
+  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
+  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "varianceMulti: one group per item of the dimension");
+  if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
+  std::vector<olap_store *> outs(m.stores.size(), nullptr);
+  static const uint32_t none = 0;
+  int launches = 0;
+  int rc = olap_store_variance_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis, kind, ddof, n_groups,
+                                     one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
+  return multi_done(env, rc, argc, argv, 7, launches) ? wrap_new_stores(env, outs) : nullptr;
+}
+
 // ---- ShardedStore: a measure split along dimension 0 over the devices of setDevices() -----------
 // Wraps olap_sharded_store* (include/olap_hip.h, "Multi-GPU").  Method names and argument shapes are
 // those of Store, so the JS HipStore drives either; what a sharded store cannot do in place throws an
@@ -1916,6 +1947,7 @@ static napi_value Init(napi_env env, napi_value exports) {
       {"drillDownMulti", nullptr, DrillDownMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"cumulateMulti", nullptr, CumulateMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"quantileMulti", nullptr, QuantileMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"varianceMulti", nullptr, VarianceMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"rollingMulti", nullptr, RollingMulti, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"storeFromSparse", nullptr, StoreFromSparse, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"methodFromName", nullptr, MethodFromName, nullptr, nullptr, nullptr, napi_default, nullptr},
