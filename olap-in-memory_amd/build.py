@@ -22,7 +22,7 @@ ARCH = "gfx950"
 
 KERNEL_UNITS = ["olap_kernels_f32.hip", "olap_kernels_f64.hip", "olap_kernels_i32.hip", "olap_kernels_u32.hip",
                 "olap_kernels_load_typed.hip", "olap_kernels_compose.hip", "olap_blocks.hip",
-                "olap_capi.hip", "olap_plan_drillup.hip", "olap_sharded.hip", "olap_transpose.hip", "olap_totals.hip", "olap_order.hip",
+                "olap_capi.hip", "olap_plan_drillup.hip", "olap_plan_along.hip", "olap_sharded.hip", "olap_transpose.hip", "olap_totals.hip", "olap_order.hip",
                 "olap_select.hip", "olap_cumulate.hip", "olap_rolling.hip", "olap_quantile.hip", "olap_variance.hip"]
 HEADERS = ["olap_device.hpp", "olap_kernels.hpp", "olap_internal.hpp", "olap_plan.hpp", "olap_series.hpp", os.path.join(ROOT, "include", "olap_hip.h")]
 

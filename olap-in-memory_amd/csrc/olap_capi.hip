@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -3104,97 +3105,39 @@ extern "C" int olap_store_reorder_multi(int n, const olap_store *const *stores, 
       [&](olap_plan **p, const olap_store *s, int) { return olap_reorder_plan(p, s->dtype, s->default_kind, ndim, old_len, perm); });
 }
 
-// ---- running aggregates along one dimension (Cube.cumulate; kernels: olap_cumulate.hip) -------------------------------
-static PlanKey cumulate_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map) {
+// ---- the calls that run along one dimension: cumulate, rolling, quantile, variance (Cube.cumulate, Cube.rolling and
+// Cube.shift, Cube.quantile and Cube.median, Cube.variance and Cube.stddev; plans: olap_plan_along.hip; kernels:
+// olap_cumulate.hip, olap_rolling.hip, olap_quantile.hip, olap_variance.hip) -----------------------------------------------
+// The key of such a plan: the call's tag, cell type, default, shape and axis, then the call's own words — what its
+// *_choose cuts by — then the map.  What travels with the launch (the rules, q, kind and ddof) is not in a key.
+static PlanKey along_key(char tag, const olap_store *s, int ndim, const uint32_t *lens, int axis, std::initializer_list<int32_t> own, uint32_t n_groups,
+                         const uint32_t *map) {
   PlanKey key;
-  key.i32('K');
+  key.i32(tag);
   key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
   key.u32s(lens, ndim);
+  for (const int32_t word : own) key.i32(word);
   key.i32(map != nullptr);
   if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
   return key;
 }
 
-// the arguments passed olap_store_cumulate_multi's checks; the rule is not part of a plan (a launch takes one per pair)
-static int cumulate_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
-                         const uint32_t *map) {
-  *out = nullptr;
-  int rc = require_device();
-  if (rc) return rc;
-  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
-  olap_plan *const p = owner.get();
-  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
-  p->kind = PLAN_CUMULATE;
-  p->dtype = dtype;
-  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
-  p->method = OLAP_SUM;
-  p->in_cells = p->out_cells = product(lens, ndim);
-  CumulateView &v = p->cum;
-  v.outer = product(lens, axis);
-  v.K = lens[axis];
-  v.inner = product(lens + axis + 1, ndim - axis - 1);
-  v.G = map ? n_groups : 1;
-  v.def_nan = p->def_nan;
-  std::vector<uint32_t> gstart, order;
-  bool contiguous = true;
-  if (map) {
-    build_csr(map, lens[axis], n_groups, gstart, order);
-    for (size_t j = 0; j < order.size(); ++j) contiguous = contiguous && order[j] == j;
-  } else {
-    gstart = {0, lens[axis]};
-  }
-  std::vector<uint32_t> tab(gstart);
-  const size_t order_off = tab.size();
-  if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
-  v.gstart = (const uint32_t *)p->dev_tab;
-  v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
-  cumulate_choose(v, (int)olap_dtype_size(dtype), contiguous);
-  p->kernel_name = v.form == CUMULATE_COLUMN ? (v.vec == 1 ? "cumulate_column_kernel<cell>" : "cumulate_column_kernel")
-                   : v.form == CUMULATE_ROW_WHOLE ? "cumulate_rows_kernel" : "cumulate_rows_kernel<chunked>";
-  *out = owner.release();
-  return OLAP_OK;
-}
-
-// the pairs of one group, a rule each, in launches of up to kMaxBatch
-static int cumulate_run(olap_plan *p, const Pairs &q, const int *rules, int *launches) {
-  if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-  if (p->in_cells == 0) return OLAP_OK;
-  int cur;
-  if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
-  for (int first = 0; first < q.n; first += kMaxBatch) {
-    const int nb = std::min(q.n - first, (int)kMaxBatch);
-    const hipError_t e = launch_cumulate(p->dtype, q.masks(), nb, rules + first, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first,
-                                         p->cum, nullptr);
-    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
-    *launches += 1;
-  }
-  return OLAP_OK;
-}
-
-// What the calls that run along one dimension share (cumulate, rolling, quantile, variance; `what` names the call in
-// the messages): the checks, on the host and in the order the header lists them, and the walk over the groups of one
-// cell type and default.  window: rolling's {before, after}, or nullptr.  q: quantile's, or nullptr; kind_ddof:
-// variance's {kind, ddof}, or nullptr; those two calls take no rules (methods == nullptr) and accept stores that track
-// their insertion order.
-static int check_along_axis(const char *what, int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
-                            const uint32_t *lens, int axis, const int32_t *window, const double *q, const int *kind_ddof, uint32_t n_groups,
-                            const uint32_t *map) {
-  const bool ruled = !q && !kind_ddof;
+// The checks these calls share, on the host and in the order the header lists them (`what` names the call in the
+// messages).  ruled: the call takes a rule per store (cumulate, rolling); the others (quantile, variance) accept stores
+// that track their insertion order.  own_check(): the call's check of its own scalars — the window, q, kind and ddof.
+template <typename OwnCheck>
+static int check_along_axis(const char *what, int n, const olap_store *const *stores, bool ruled, const int *methods, olap_store **out, int ndim,
+                            const uint32_t *lens, int axis, OwnCheck own_check, uint32_t n_groups, const uint32_t *map) {
   int rc = ruled ? check_list(n, stores && out && methods, "store / method list is NULL") : check_list(n, stores && out, "store list is NULL");
   if (rc) return rc;
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   if ((rc = check_entries(n, stores))) return rc;
-  // the lists, the rules, the lengths, the window, q or kind and ddof and the map first: refused without looking into a store
+  // the lists, the rules, the lengths, the call's own scalars and the map first: refused without looking into a store
   for (int i = 0; i < n && ruled; ++i)
     if (methods[i] < OLAP_SUM || methods[i] > OLAP_PRODUCT) return fail(OLAP_ERR_UNSUPPORTED_METHOD, "Unsupported aggregation method: %d", methods[i]);
   if ((rc = check_dims(ndim, lens, lens))) return rc;
   if (axis < 0 || axis >= ndim) return fail(OLAP_ERR_INVALID_ARGUMENT, "axis %d out of range [0, %d)", axis, ndim);
-  if (window && (int64_t)window[0] + window[1] < 0)
-    return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: empty window (before %d, after %d)", what, window[0], window[1]);
-  if (q && !(*q >= 0.0 && *q <= 1.0)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: q must lie in [0, 1] (got %g)", what, *q);
-  if (kind_ddof && (kind_ddof[0] < 0 || kind_ddof[0] > 1)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: kind must be 0 or 1 (got %d)", what, kind_ddof[0]);
-  if (kind_ddof && (kind_ddof[1] < 0 || kind_ddof[1] > 1)) return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: ddof must be 0 or 1 (got %d)", what, kind_ddof[1]);
+  if ((rc = own_check())) return rc;
   // (more groups than items would only be groups without members, and a table of n_groups + 1 entries to build and upload)
   if (map && n_groups > lens[axis])
     return fail(OLAP_ERR_INVALID_ARGUMENT, "%s: %u groups for the %u items of the dimension", what, n_groups, lens[axis]);
@@ -3209,9 +3152,11 @@ static int check_along_axis(const char *what, int n, const olap_store *const *st
   return OLAP_OK;
 }
 
-// key(s0) / build(&plan, s0): the plan of a group, named by its first member; run(plan, pairs, rules, &launches)
-template <typename Key, typename Build, typename Run>
-static int run_along_axis(int n, const olap_store *const *stores, const int *methods, olap_store **out, int *launches, Key key, Build build, Run run) {
+// The walk over the groups of one cell type and default.  key(s0) / build(&plan, s0): the plan of a group, named by its
+// first member; launch(plan, pairs, first, nb, rules): pairs [first, first + nb) of the group, nb <= kMaxBatch, with
+// their rules (methods != nullptr).
+template <typename Key, typename Build, typename Launch>
+static int run_along_axis(int n, const olap_store *const *stores, const int *methods, olap_store **out, int *launches, Key key, Build build, Launch launch) {
   int made = 0;
   const int rc = for_each_group(
       n, [&](int i, int j) { return same_cells(stores[j], stores[i]); },
@@ -3221,7 +3166,21 @@ static int run_along_axis(int n, const olap_store *const *stores, const int *met
         for (size_t k = 0; k < members.size() && methods; ++k) rules[k] = methods[members[k]];
         return run_group(
             (int)members.size(), members.data(), stores, out, [&] { return key(s0); }, 0, [&](olap_plan **p) { return build(p, s0); }, nullptr,
-            [&](olap_plan *plan, const Pairs &q) { return run(plan, q, rules.data(), &made); });
+            [&](olap_plan *p, const Pairs &q) {
+              if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
+              // Nothing to write.  (Not "nothing to read": over a dimension without items and without a map, quantile
+              // and variance read no cell and still write outer * inner unset cells.  Cumulate and rolling write a cell
+              // per cell they read.)
+              if (p->out_cells == 0) return (int)OLAP_OK;
+              int cur;
+              if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
+              for (int first = 0; first < q.n; first += kMaxBatch) {
+                const hipError_t e = launch(p, q, first, std::min(q.n - first, (int)kMaxBatch), rules.data() + first);
+                if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
+                made += 1;
+              }
+              return (int)OLAP_OK;
+            });
       });
   if (rc) return drop_results(n, out, rc);
   if (launches) *launches = made;
@@ -3231,327 +3190,75 @@ static int run_along_axis(int n, const olap_store *const *stores, const int *met
 extern "C" int olap_store_cumulate_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim,
                                          const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int rc = check_along_axis("cumulate", n, stores, methods, out, ndim, lens, axis, nullptr, nullptr, nullptr, n_groups, map);
+  const int rc = check_along_axis("cumulate", n, stores, true, methods, out, ndim, lens, axis, [] { return (int)OLAP_OK; }, n_groups, map);
   if (rc) return rc;
   return run_along_axis(
-      n, stores, methods, out, launches, [&](const olap_store *s0) { return cumulate_key(s0, ndim, lens, axis, n_groups, map); },
-      [&](olap_plan **p, const olap_store *s0) { return cumulate_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, cumulate_run);
-}
-
-// ---- rolling-window aggregates along one dimension (Cube.rolling, Cube.shift; kernels: olap_rolling.hip) --------------
-// before / after as the plan holds them: beyond +-K they act as +-K
-static int64_t window_side(int32_t side, uint32_t K) { return std::max<int64_t>(-(int64_t)K, std::min<int64_t>(side, K)); }
-
-static PlanKey rolling_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, int32_t before, int32_t after, uint32_t n_groups,
-                           const uint32_t *map) {
-  PlanKey key;
-  key.i32('W');
-  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
-  key.u32s(lens, ndim);
-  key.i32((int32_t)window_side(before, lens[axis])), key.i32((int32_t)window_side(after, lens[axis]));
-  key.i32(map != nullptr);
-  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
-  return key;
-}
-
-// the arguments passed olap_store_rolling_multi's checks; the rule is not part of a plan (a launch takes one per pair)
-static int rolling_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, int32_t before, int32_t after,
-                        const uint32_t *map) {
-  *out = nullptr;
-  int rc = require_device();
-  if (rc) return rc;
-  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
-  olap_plan *const p = owner.get();
-  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
-  p->kind = PLAN_ROLLING;
-  p->dtype = dtype;
-  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
-  p->method = OLAP_SUM;
-  p->in_cells = p->out_cells = product(lens, ndim);
-  RollingView &v = p->roll;
-  v.outer = product(lens, axis);
-  v.K = lens[axis];
-  v.inner = product(lens + axis + 1, ndim - axis - 1);
-  v.before = window_side(before, lens[axis]);
-  v.after = window_side(after, lens[axis]);
-  v.def_nan = p->def_nan;
-  if (map && (rc = upload(&p->dev_tab, map, (size_t)lens[axis] * sizeof(uint32_t)))) return rc;
-  v.map = (const uint32_t *)p->dev_tab;
-  rolling_choose(v, (int)olap_dtype_size(dtype));
-  p->kernel_name = v.form == ROLLING_DIRECT ? "rolling_direct_kernel" : v.form == ROLLING_COLUMNS ? "rolling_tiled_kernel<columns>" : "rolling_tiled_kernel<series>";
-  *out = owner.release();
-  return OLAP_OK;
-}
-
-// the pairs of one group, a rule each, in launches of up to kMaxBatch
-static int rolling_run(olap_plan *p, const Pairs &q, const int *rules, int *launches) {
-  if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-  if (p->in_cells == 0) return OLAP_OK;
-  int cur;
-  if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
-  for (int first = 0; first < q.n; first += kMaxBatch) {
-    const int nb = std::min(q.n - first, (int)kMaxBatch);
-    const hipError_t e = launch_rolling(p->dtype, q.masks(), nb, rules + first, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first,
-                                        p->roll, nullptr);
-    if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
-    *launches += 1;
-  }
-  return OLAP_OK;
+      n, stores, methods, out, launches, [&](const olap_store *s0) { return along_key('K', s0, ndim, lens, axis, {}, n_groups, map); },
+      [&](olap_plan **p, const olap_store *s0) { return cumulate_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); },
+      [](olap_plan *p, const Pairs &q, int first, int nb, const int *rules) {
+        return launch_cumulate(p->dtype, q.masks(), nb, rules, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first, p->cum, nullptr);
+      });
 }
 
 extern "C" int olap_store_rolling_multi(int n, const olap_store *const *stores, const int *methods, olap_store **out, int ndim, const uint32_t *lens,
                                         int axis, int32_t before, int32_t after, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int32_t window[2] = {before, after};
-  const int rc = check_along_axis("rolling", n, stores, methods, out, ndim, lens, axis, window, nullptr, nullptr, n_groups, map);
+  const int rc = check_along_axis("rolling", n, stores, true, methods, out, ndim, lens, axis, [&] {
+    if ((int64_t)before + after < 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling: empty window (before %d, after %d)", before, after);
+    return (int)OLAP_OK;
+  }, n_groups, map);
   if (rc) return rc;
   return run_along_axis(
-      n, stores, methods, out, launches, [&](const olap_store *s0) { return rolling_key(s0, ndim, lens, axis, before, after, n_groups, map); },
-      [&](olap_plan **p, const olap_store *s0) { return rolling_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, before, after, map); }, rolling_run);
-}
-
-extern "C" int olap_diag_rolling_choice(int cell_bytes, uint64_t outer, uint64_t K, uint64_t inner, int32_t before, int32_t after, int has_map,
-                                        uint32_t choice[4]) {
-  if (cell_bytes != 4 && cell_bytes != 8) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: cells of %d bytes", cell_bytes);
-  if (!choice) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: NULL result");
-  if (K > 0xFFFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling choice: a dimension of more than 2^32 - 1 items");
-  if ((int64_t)before + after < 0) return fail(OLAP_ERR_INVALID_ARGUMENT, "rolling: empty window (before %d, after %d)", before, after);
-  (void)has_map;  // the map travels as it is: it does not change the cuts
-  RollingView v{};
-  v.outer = outer, v.K = K, v.inner = inner;
-  v.before = window_side(before, (uint32_t)K), v.after = window_side(after, (uint32_t)K);
-  rolling_choose(v, cell_bytes);
-  choice[0] = (uint32_t)v.form, choice[1] = v.series, choice[2] = v.rows, choice[3] = v.cols;
-  return OLAP_OK;
-}
-
-// ---- order statistics along one dimension (Cube.quantile, Cube.median; kernels: olap_quantile.hip) --------------------
-// (q is not in the key: it travels as a launch argument.  The tile is: OLAP_QUANTILE_TILE changes the cuts)
-static PlanKey quantile_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map) {
-  PlanKey key;
-  key.i32('Q');
-  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
-  key.u32s(lens, ndim);
-  key.i32((int32_t)quantile_tile_cells((int)olap_dtype_size(s->dtype), mask_is_primary(s)));
-  key.i32(map != nullptr);
-  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
-  return key;
-}
-
-static uint32_t longest_group(const std::vector<uint32_t> &gstart) {
-  uint32_t longest = 0;
-  for (size_t g = 0; g + 1 < gstart.size(); ++g) longest = std::max(longest, gstart[g + 1] - gstart[g]);
-  return longest;
-}
-
-static const char *quantile_kernel_name(int form) {
-  return form == QUANTILE_COLUMN ? "quantile_column_kernel" : form == QUANTILE_ROW ? "quantile_rows_kernel"
-         : form == QUANTILE_DIRECT_LANES ? "quantile_direct_kernel<lanes>" : "quantile_direct_kernel<block>";
-}
-
-// the arguments passed olap_store_quantile_multi's checks
-static int quantile_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
-                         const uint32_t *map) {
-  *out = nullptr;
-  int rc = require_device();
-  if (rc) return rc;
-  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
-  olap_plan *const p = owner.get();
-  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
-  p->kind = PLAN_QUANTILE;
-  p->dtype = dtype;
-  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
-  p->method = OLAP_SUM;
-  QuantileView &v = p->quant;
-  v.outer = product(lens, axis);
-  v.K = lens[axis];
-  v.inner = product(lens + axis + 1, ndim - axis - 1);
-  v.G = map ? n_groups : 1;
-  v.def_nan = p->def_nan;
-  p->in_cells = product(lens, ndim);
-  p->out_cells = v.outer * v.G * v.inner;
-  std::vector<uint32_t> gstart, order;
-  bool contiguous = true;
-  if (map) {
-    build_csr(map, lens[axis], n_groups, gstart, order);
-    for (size_t j = 0; j < order.size(); ++j) contiguous = contiguous && order[j] == j;
-  } else {
-    gstart = {0, lens[axis]};
-  }
-  v.tile = quantile_tile_cells((int)olap_dtype_size(dtype), p->def_nan && (dtype == OLAP_INT32 || dtype == OLAP_UINT32));
-  v.longest = longest_group(gstart);
-  quantile_choose(v, (int)olap_dtype_size(dtype));
-  std::vector<uint32_t> tab(gstart);
-  const size_t order_off = tab.size();
-  if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
-  const size_t gtile_off = tab.size();
-  if (v.form == QUANTILE_COLUMN) {
-    const std::vector<uint32_t> gtile = quantile_group_tiles(v, gstart.data());
-    v.n_gtile = (uint32_t)gtile.size() - 1;
-    tab.insert(tab.end(), gtile.begin(), gtile.end());
-  }
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
-  v.gstart = (const uint32_t *)p->dev_tab;
-  v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
-  v.gtile = v.form == QUANTILE_COLUMN ? (const uint32_t *)p->dev_tab + gtile_off : nullptr;
-  p->kernel_name = quantile_kernel_name(v.form);
-  *out = owner.release();
-  return OLAP_OK;
+      n, stores, methods, out, launches,
+      [&](const olap_store *s0) {  // the window as the plan holds it
+        return along_key('W', s0, ndim, lens, axis, {(int32_t)window_side(before, lens[axis]), (int32_t)window_side(after, lens[axis])}, n_groups, map);
+      },
+      [&](olap_plan **p, const olap_store *s0) { return rolling_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, before, after, map); },
+      [](olap_plan *p, const Pairs &q, int first, int nb, const int *rules) {
+        return launch_rolling(p->dtype, q.masks(), nb, rules, q.in_v + first, q.in_s + first, q.out_v + first, q.out_s + first, p->roll, nullptr);
+      });
 }
 
 extern "C" int olap_store_quantile_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens, int axis,
                                          double q, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int rc = check_along_axis("quantile", n, stores, nullptr, out, ndim, lens, axis, nullptr, &q, nullptr, n_groups, map);
-  if (rc) return rc;
-  // the pairs of one group in launches of up to kMaxBatch
-  auto run = [q](olap_plan *p, const Pairs &pairs, const int *, int *made) {
-    if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-    if (p->out_cells == 0) return (int)OLAP_OK;
-    int cur;
-    if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
-    for (int first = 0; first < pairs.n; first += kMaxBatch) {
-      const int nb = std::min(pairs.n - first, (int)kMaxBatch);
-      const hipError_t e = launch_quantile(p->dtype, pairs.masks(), nb, pairs.in_v + first, pairs.in_s + first, pairs.out_v + first,
-                                           pairs.out_s + first, p->quant, q, nullptr);
-      if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
-      *made += 1;
-    }
+  const int rc = check_along_axis("quantile", n, stores, false, nullptr, out, ndim, lens, axis, [&] {
+    if (!(q >= 0.0 && q <= 1.0)) return fail(OLAP_ERR_INVALID_ARGUMENT, "quantile: q must lie in [0, 1] (got %g)", q);
     return (int)OLAP_OK;
-  };
-  return run_along_axis(
-      n, stores, nullptr, out, launches, [&](const olap_store *s0) { return quantile_key(s0, ndim, lens, axis, n_groups, map); },
-      [&](olap_plan **p, const olap_store *s0) { return quantile_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, run);
-}
-
-extern "C" int olap_diag_quantile_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner, uint32_t n_groups,
-                                         uint32_t longest, int contiguous, uint32_t choice[6]) {
-  if (cell_bytes != 4 && cell_bytes != 8) return fail(OLAP_ERR_INVALID_ARGUMENT, "quantile choice: cells of %d bytes", cell_bytes);
-  if (!choice) return fail(OLAP_ERR_INVALID_ARGUMENT, "quantile choice: NULL result");
-  if (K > 0xFFFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "quantile choice: a dimension of more than 2^32 - 1 items");
-  if (longest > K) return fail(OLAP_ERR_INVALID_ARGUMENT, "quantile choice: a group of %u of the dimension's %llu items", longest, (unsigned long long)K);
-  (void)contiguous;  // interleaved groups are staged member by member: the cuts are the same
-  QuantileView v{};
-  v.outer = outer, v.K = K, v.inner = inner, v.G = n_groups;
-  v.tile = quantile_tile_cells(cell_bytes, has_mask != 0);
-  v.longest = longest;
-  quantile_choose(v, cell_bytes);
-  choice[0] = (uint32_t)v.form, choice[1] = v.tile, choice[2] = v.series, choice[3] = v.pitch, choice[4] = v.cols, choice[5] = v.rows;
-  return OLAP_OK;
-}
-
-// ---- dispersion along one dimension (Cube.variance, Cube.stddev; kernels: olap_variance.hip) --------------------------
-// (kind and ddof are not in the key: they travel as launch arguments.  The tile and the block cut are: OLAP_VARIANCE_TILE
-// and OLAP_VARIANCE_BLOCK change the cuts)
-static PlanKey variance_key(const olap_store *s, int ndim, const uint32_t *lens, int axis, uint32_t n_groups, const uint32_t *map) {
-  PlanKey key;
-  key.i32('V');
-  key.i32(s->dtype), key.i32(s->default_kind), key.i32(ndim), key.i32(axis);
-  key.u32s(lens, ndim);
-  key.i32((int32_t)variance_tile_cells((int)olap_dtype_size(s->dtype), mask_is_primary(s)));
-  key.i32((int32_t)variance_block_members()), key.i32((int32_t)variance_block_cells());
-  key.i32(map != nullptr);
-  if (map) key.i32((int32_t)n_groups), key.u32s(map, lens[axis]);
-  return key;
-}
-
-static const char *variance_kernel_name(int form) {
-  return form == VARIANCE_COLUMN ? "variance_column_kernel" : form == VARIANCE_ROW ? "variance_rows_kernel"
-         : form == VARIANCE_DIRECT_LANES ? "variance_direct_kernel<lanes>" : "variance_direct_kernel<block>";
-}
-
-// the arguments passed olap_store_variance_multi's checks
-static int variance_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
-                         const uint32_t *map) {
-  *out = nullptr;
-  int rc = require_device();
+  }, n_groups, map);
   if (rc) return rc;
-  PlanOwner owner(new (std::nothrow) olap_plan());  // destroyed on every return but the one that releases it into *out
-  olap_plan *const p = owner.get();
-  if (!p) return fail(OLAP_ERR_OUT_OF_MEMORY, "out of host memory");
-  p->kind = PLAN_VARIANCE;
-  p->dtype = dtype;
-  p->def_nan = default_kind == OLAP_DEFAULT_NAN;
-  p->method = OLAP_SUM;
-  VarianceView &v = p->var;
-  v.outer = product(lens, axis);
-  v.K = lens[axis];
-  v.inner = product(lens + axis + 1, ndim - axis - 1);
-  v.G = map ? n_groups : 1;
-  v.def_nan = p->def_nan;
-  p->in_cells = product(lens, ndim);
-  p->out_cells = v.outer * v.G * v.inner;
-  std::vector<uint32_t> gstart, order;
-  bool contiguous = true;
-  if (map) {
-    build_csr(map, lens[axis], n_groups, gstart, order);
-    for (size_t j = 0; j < order.size(); ++j) contiguous = contiguous && order[j] == j;
-  } else {
-    gstart = {0, lens[axis]};
-  }
-  v.tile = variance_tile_cells((int)olap_dtype_size(dtype), p->def_nan && (dtype == OLAP_INT32 || dtype == OLAP_UINT32));
-  v.block_members = variance_block_members(), v.block_cells = variance_block_cells();
-  v.longest = longest_group(gstart);
-  variance_choose(v, (int)olap_dtype_size(dtype));
-  std::vector<uint32_t> tab(gstart);
-  const size_t order_off = tab.size();
-  if (!contiguous) tab.insert(tab.end(), order.begin(), order.end());
-  const size_t gtile_off = tab.size();
-  if (v.form == VARIANCE_COLUMN) {
-    const std::vector<uint32_t> gtile = variance_group_tiles(v, gstart.data());
-    v.n_gtile = (uint32_t)gtile.size() - 1;
-    tab.insert(tab.end(), gtile.begin(), gtile.end());
-  }
-  if ((rc = upload(&p->dev_tab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
-  v.gstart = (const uint32_t *)p->dev_tab;
-  v.order = contiguous ? nullptr : (const uint32_t *)p->dev_tab + order_off;
-  v.gtile = v.form == VARIANCE_COLUMN ? (const uint32_t *)p->dev_tab + gtile_off : nullptr;
-  p->kernel_name = variance_kernel_name(v.form);
-  *out = owner.release();
-  return OLAP_OK;
+  return run_along_axis(
+      n, stores, nullptr, out, launches,
+      [&](const olap_store *s0) {  // the tile: OLAP_QUANTILE_TILE changes the cuts
+        return along_key('Q', s0, ndim, lens, axis, {(int32_t)quantile_tile_cells((int)olap_dtype_size(s0->dtype), mask_is_primary(s0))}, n_groups, map);
+      },
+      [&](olap_plan **p, const olap_store *s0) { return quantile_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); },
+      [q](olap_plan *p, const Pairs &pairs, int first, int nb, const int *) {
+        return launch_quantile(p->dtype, pairs.masks(), nb, pairs.in_v + first, pairs.in_s + first, pairs.out_v + first, pairs.out_s + first, p->quant, q,
+                               nullptr);
+      });
 }
 
 extern "C" int olap_store_variance_multi(int n, const olap_store *const *stores, olap_store **out, int ndim, const uint32_t *lens, int axis,
                                          int kind, int ddof, uint32_t n_groups, const uint32_t *map, int *launches) {
   if (launches) *launches = 0;
-  const int kind_ddof[2] = {kind, ddof};
-  const int rc = check_along_axis("variance", n, stores, nullptr, out, ndim, lens, axis, nullptr, nullptr, kind_ddof, n_groups, map);
-  if (rc) return rc;
-  // the pairs of one group in launches of up to kMaxBatch
-  auto run = [kind, ddof](olap_plan *p, const Pairs &pairs, const int *, int *made) {
-    if (plan_dry()) return fail(OLAP_ERR_NO_DEVICE, "OLAP_PLAN_DRY is set: plans are built for inspection only; libolapgpu has no CPU fallback");
-    if (p->out_cells == 0) return (int)OLAP_OK;
-    int cur;
-    if (!begin_run(p, nullptr, &cur)) return foreign_device(p, cur);
-    for (int first = 0; first < pairs.n; first += kMaxBatch) {
-      const int nb = std::min(pairs.n - first, (int)kMaxBatch);
-      const hipError_t e = launch_variance(p->dtype, pairs.masks(), nb, pairs.in_v + first, pairs.in_s + first, pairs.out_v + first,
-                                           pairs.out_s + first, p->var, kind, ddof, nullptr);
-      if (e != hipSuccess) return hip_fail(e, p->kernel_name.c_str());
-      *made += 1;
-    }
+  const int rc = check_along_axis("variance", n, stores, false, nullptr, out, ndim, lens, axis, [&] {
+    if (kind < 0 || kind > 1) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance: kind must be 0 or 1 (got %d)", kind);
+    if (ddof < 0 || ddof > 1) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance: ddof must be 0 or 1 (got %d)", ddof);
     return (int)OLAP_OK;
-  };
+  }, n_groups, map);
+  if (rc) return rc;
   return run_along_axis(
-      n, stores, nullptr, out, launches, [&](const olap_store *s0) { return variance_key(s0, ndim, lens, axis, n_groups, map); },
-      [&](olap_plan **p, const olap_store *s0) { return variance_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); }, run);
-}
-
-extern "C" int olap_diag_variance_choice(int cell_bytes, int has_mask, uint64_t outer, uint64_t K, uint64_t inner, uint32_t n_groups,
-                                         uint32_t longest, int contiguous, uint32_t choice[6]) {
-  if (cell_bytes != 4 && cell_bytes != 8) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: cells of %d bytes", cell_bytes);
-  if (!choice) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: NULL result");
-  if (K > 0xFFFFFFFFull) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: a dimension of more than 2^32 - 1 items");
-  if (longest > K) return fail(OLAP_ERR_INVALID_ARGUMENT, "variance choice: a group of %u of the dimension's %llu items", longest, (unsigned long long)K);
-  (void)contiguous;  // interleaved groups are staged member by member: the cuts are the same
-  VarianceView v{};
-  v.outer = outer, v.K = K, v.inner = inner, v.G = n_groups;
-  v.tile = variance_tile_cells(cell_bytes, has_mask != 0);
-  v.block_members = variance_block_members(), v.block_cells = variance_block_cells();
-  v.longest = longest;
-  variance_choose(v, cell_bytes);
-  choice[0] = (uint32_t)v.form, choice[1] = v.tile, choice[2] = v.series, choice[3] = v.pitch, choice[4] = v.cols, choice[5] = v.rows;
-  return OLAP_OK;
+      n, stores, nullptr, out, launches,
+      [&](const olap_store *s0) {  // the tile and the block cut: OLAP_VARIANCE_TILE and OLAP_VARIANCE_BLOCK change the cuts
+        return along_key('V', s0, ndim, lens, axis, {(int32_t)variance_tile_cells((int)olap_dtype_size(s0->dtype), mask_is_primary(s0)),
+                                                    (int32_t)variance_block_members(), (int32_t)variance_block_cells()}, n_groups, map);
+      },
+      [&](olap_plan **p, const olap_store *s0) { return variance_plan(p, s0->dtype, s0->default_kind, ndim, lens, axis, n_groups, map); },
+      [kind, ddof](olap_plan *p, const Pairs &pairs, int first, int nb, const int *) {
+        return launch_variance(p->dtype, pairs.masks(), nb, pairs.in_v + first, pairs.in_s + first, pairs.out_v + first, pairs.out_s + first, p->var, kind,
+                               ddof, nullptr);
+      });
 }
 
 static PlanKey load_key(const olap_store *mine, const olap_store *his, int ndim, const uint32_t *my_len, const uint32_t *his_len,

@@ -227,16 +227,6 @@ __global__ __launch_bounds__(kBlock) void cumulate_rows_kernel(const Batch<T> b,
   SERIES_RULE(b.method[p], (rows_tiles<T, HS, M>(tv, ts, b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, n_tiles)));
 }
 
-// Workgroups of a launch along x: beyond it a workgroup takes several tiles, a lane several items.  OLAP_CUMULATE_GRID=n
-// (a developer knob, NOTEBOOK) lowers it, so that the tests reach those loops with small cubes.
-uint64_t max_grid(uint32_t most) {
-  if (const char *e = getenv("OLAP_CUMULATE_GRID")) {
-    const unsigned long n = strtoul(e, nullptr, 10);
-    if (n >= 1 && n < most) return n;
-  }
-  return most;
-}
-
 template <typename T, bool HS>
 hipError_t launch_typed(int nb, const int *methods, const void *const *in, const int32_t *const *st_in, void *const *out, int32_t *const *st_out,
                         const CumulateView &v, hipStream_t stream) {
@@ -249,12 +239,12 @@ hipError_t launch_typed(int nb, const int *methods, const void *const *in, const
   if (v.form == CUMULATE_COLUMN) {
     const uint64_t items = v.outer * v.G * ((v.inner + v.vec - 1) / v.vec);
     const uint64_t blocks = (items + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)(blocks < max_grid(1u << 22) ? blocks : max_grid(1u << 22)), (unsigned)nb);
+    const dim3 grid((unsigned)(blocks < series_max_grid("OLAP_CUMULATE_GRID", 1u << 22) ? blocks : series_max_grid("OLAP_CUMULATE_GRID", 1u << 22)), (unsigned)nb);
     if (v.vec == 1) cumulate_column_kernel<T, HS, 1><<<grid, kBlock, 0, stream>>>(b, v, items);
     else cumulate_column_kernel<T, HS, 16 / (int)sizeof(T)><<<grid, kBlock, 0, stream>>>(b, v, items);
   } else {
     const uint64_t n_tiles = (v.outer + v.series - 1) / v.series;
-    const dim3 grid((unsigned)(n_tiles < max_grid(1u << 20) ? n_tiles : max_grid(1u << 20)), (unsigned)nb);
+    const dim3 grid((unsigned)(n_tiles < series_max_grid("OLAP_CUMULATE_GRID", 1u << 20) ? n_tiles : series_max_grid("OLAP_CUMULATE_GRID", 1u << 20)), (unsigned)nb);
     cumulate_rows_kernel<T, HS><<<grid, kBlock, 0, stream>>>(b, v, n_tiles);
   }
   return hipGetLastError();
@@ -300,17 +290,7 @@ hipError_t launch_cumulate(int dtype, bool has_status, int nb, const int *method
                            void *const *out, int32_t *const *st_out, const CumulateView &v, hipStream_t stream) {
   if (nb < 1 || nb > kMaxBatch) return hipErrorInvalidValue;
   if (v.outer == 0 || v.K == 0 || v.inner == 0) return hipSuccess;
-  switch (dtype) {
-    case OLAP_INT32:
-      return has_status ? launch_typed<int32_t, true>(nb, methods, in, st_in, out, st_out, v, stream)
-                        : launch_typed<int32_t, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    case OLAP_UINT32:
-      return has_status ? launch_typed<uint32_t, true>(nb, methods, in, st_in, out, st_out, v, stream)
-                        : launch_typed<uint32_t, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    // float cells never hold a mask of their own (mask_is_primary)
-    case OLAP_FLOAT32:
-      return has_status ? hipErrorInvalidValue : launch_typed<float, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    default:
-      return has_status ? hipErrorInvalidValue : launch_typed<double, false>(nb, methods, in, st_in, out, st_out, v, stream);
-  }
+  return series_cell_type(dtype, has_status, [&](auto cell, auto hs) {
+    return launch_typed<decltype(cell), decltype(hs)::value>(nb, methods, in, st_in, out, st_out, v, stream);
+  });
 }

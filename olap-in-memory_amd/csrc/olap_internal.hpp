@@ -240,8 +240,6 @@ struct QuantileView {
 OLAP_INTERNAL uint32_t quantile_tile_cells(int cell_bytes, bool has_mask);
 // chooses form and tile cuts from the shape, the tile and the largest group alone; fills everything but the tables
 OLAP_INTERNAL void quantile_choose(QuantileView &v, int cell_bytes);
-// the column form's cut of the groups into tiles of at most v.rows rows (host CSR; needs v.rows >= the largest group)
-OLAP_INTERNAL std::vector<uint32_t> quantile_group_tiles(const QuantileView &v, const uint32_t *gstart);
 // nb <= 8 pairs of one cell type and default; masks on all pairs or on none
 OLAP_INTERNAL hipError_t launch_quantile(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
                                          int32_t *const *st_out, const QuantileView &v, double q, hipStream_t stream);
@@ -277,8 +275,6 @@ OLAP_INTERNAL uint32_t variance_block_members();
 OLAP_INTERNAL uint32_t variance_block_cells();
 // chooses form and tile cuts from the shape, the tile and the largest group alone; fills everything but the tables
 OLAP_INTERNAL void variance_choose(VarianceView &v, int cell_bytes);
-// the column form's cut of the groups into tiles of at most v.rows rows (host CSR; needs v.rows >= the largest group)
-OLAP_INTERNAL std::vector<uint32_t> variance_group_tiles(const VarianceView &v, const uint32_t *gstart);
 // nb <= 8 pairs of one cell type and default; masks on all pairs or on none.  kind: 0 variance, 1 stddev; ddof: 0 or 1
 OLAP_INTERNAL hipError_t launch_variance(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
                                          int32_t *const *st_out, const VarianceView &v, int kind, int ddof, hipStream_t stream);

@@ -1,7 +1,8 @@
-// olap_plan.hpp — what a plan is and what its builders share (olap_capi.hip, olap_plan_drillup.hip).  Nothing here is
-// exported.
+// olap_plan.hpp — what a plan is and what its builders share (olap_capi.hip, olap_plan_drillup.hip, olap_plan_along.hip).
+// Nothing here is exported.
 #pragma once
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -82,3 +83,17 @@ OLAP_INTERNAL int vec_for(int dtype, uint64_t contiguous);
 OLAP_INTERNAL bool is_identity_u32(const uint32_t *m, uint32_t old_len, uint32_t new_len);
 // CSR of a K->G map: members of each group in ascending order (counting sort, stable)
 OLAP_INTERNAL void build_csr(const uint32_t *m, uint32_t K, uint32_t G, std::vector<uint32_t> &gstart, std::vector<uint32_t> &order);
+
+// ---- plans of the calls along one dimension (olap_plan_along.hip) ----------------------------------------------------
+// The arguments passed the checks of the call's entry point (olap_capi.hip); map == nullptr: the dimension is one group.
+// Rules, q, kind and ddof are not part of a plan: they travel with the launch.
+OLAP_INTERNAL int cumulate_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
+                                const uint32_t *map);
+OLAP_INTERNAL int rolling_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, int32_t before, int32_t after,
+                               const uint32_t *map);
+OLAP_INTERNAL int quantile_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
+                                const uint32_t *map);
+OLAP_INTERNAL int variance_plan(olap_plan **out, int dtype, int default_kind, int ndim, const uint32_t *lens, int axis, uint32_t n_groups,
+                                const uint32_t *map);
+// rolling's before / after as the plan (and its cache key) holds them: beyond +-K they act as +-K
+inline int64_t window_side(int32_t side, uint32_t K) { return std::max<int64_t>(-(int64_t)K, std::min<int64_t>(side, K)); }

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kBlock) void quantile_column_kernel(const Batch<T> 
   for (uint64_t work = blockIdx.x; work < n_work; work += gridDim.x) {
     const uint64_t slice = work % slices, t = (work / slices) % v.n_gtile, o = work / (slices * v.n_gtile);
     const uint32_t g0 = v.gtile[t], g1 = v.gtile[t + 1];
-    const uint32_t ja = v.gstart[g0], rows = v.gstart[g1] - ja;  // rows * cols <= v.tile <= kCells (quantile_group_tiles)
+    const uint32_t ja = v.gstart[g0], rows = v.gstart[g1] - ja;  // rows * cols <= v.tile <= kCells (group_tiles, olap_plan_along.hip)
     const uint64_t c0 = slice * v.cols;
     const uint32_t nc = (uint32_t)(v.inner - c0 < v.cols ? v.inner - c0 : v.cols);
     const uint64_t first = o * v.K * v.inner + c0 + (v.order ? 0 : (uint64_t)ja * v.inner);
@@ -342,18 +342,6 @@ __global__ __launch_bounds__(kBlock) void quantile_direct_kernel(const Batch<T> 
   }
 }
 
-unsigned long env_number(const char *name) {
-  const char *e = getenv(name);
-  return e ? strtoul(e, nullptr, 10) : 0;
-}
-
-// Workgroups of a launch along x: beyond it a workgroup takes several tiles, a lane several cells.  OLAP_QUANTILE_GRID=n
-// (a developer knob, NOTEBOOK) lowers it, so that the tests reach those loops with small cubes.
-uint64_t max_grid(uint32_t most) {
-  const unsigned long n = env_number("OLAP_QUANTILE_GRID");
-  return n >= 1 && n < most ? n : most;
-}
-
 template <typename T, bool HS>
 hipError_t launch_typed(int nb, const void *const *in, const int32_t *const *st_in, void *const *out, int32_t *const *st_out, const QuantileView &v,
                         double q, hipStream_t stream) {
@@ -366,7 +354,7 @@ hipError_t launch_typed(int nb, const void *const *in, const int32_t *const *st_
   uint32_t rank_max = kRankMax;
   if (getenv("OLAP_QUANTILE_RANK")) rank_max = (uint32_t)env_number("OLAP_QUANTILE_RANK");
   const uint64_t cells = v.outer * v.G * v.inner;
-  auto grid = [&](uint64_t want) { return dim3((unsigned)(want < max_grid(1u << 20) ? want : max_grid(1u << 20)), (unsigned)nb); };
+  auto grid = [&](uint64_t want) { return dim3((unsigned)(want < series_max_grid("OLAP_QUANTILE_GRID", 1u << 20) ? want : series_max_grid("OLAP_QUANTILE_GRID", 1u << 20)), (unsigned)nb); };
   switch (v.form) {
     case QUANTILE_COLUMN: {
       const uint64_t n_work = v.outer * v.n_gtile * ((v.inner + v.cols - 1) / v.cols);
@@ -441,34 +429,11 @@ void quantile_choose(QuantileView &v, int cell_bytes) {
   v.team = quantile_team((uint64_t)v.cols * (v.rows / (v.longest ? v.longest : 1)), v.longest);
 }
 
-std::vector<uint32_t> quantile_group_tiles(const QuantileView &v, const uint32_t *gstart) {
-  std::vector<uint32_t> gtile{0};
-  uint32_t g0 = 0;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    if (g > g0 && gstart[g + 1] - gstart[g0] > v.rows) {  // group g no longer fits beside [g0, g): it opens the next tile
-      gtile.push_back(g);
-      g0 = g;
-    }
-  }
-  gtile.push_back((uint32_t)v.G);
-  return gtile;
-}
-
 hipError_t launch_quantile(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
                            int32_t *const *st_out, const QuantileView &v, double q, hipStream_t stream) {
   if (nb < 1 || nb > kMaxBatch) return hipErrorInvalidValue;
   if (v.outer == 0 || v.G == 0 || v.inner == 0) return hipSuccess;
-  switch (dtype) {
-    case OLAP_INT32:
-      return has_status ? launch_typed<int32_t, true>(nb, in, st_in, out, st_out, v, q, stream)
-                        : launch_typed<int32_t, false>(nb, in, st_in, out, st_out, v, q, stream);
-    case OLAP_UINT32:
-      return has_status ? launch_typed<uint32_t, true>(nb, in, st_in, out, st_out, v, q, stream)
-                        : launch_typed<uint32_t, false>(nb, in, st_in, out, st_out, v, q, stream);
-    // float cells never hold a mask of their own (mask_is_primary)
-    case OLAP_FLOAT32:
-      return has_status ? hipErrorInvalidValue : launch_typed<float, false>(nb, in, st_in, out, st_out, v, q, stream);
-    default:
-      return has_status ? hipErrorInvalidValue : launch_typed<double, false>(nb, in, st_in, out, st_out, v, q, stream);
-  }
+  return series_cell_type(dtype, has_status, [&](auto cell, auto hs) {
+    return launch_typed<decltype(cell), decltype(hs)::value>(nb, in, st_in, out, st_out, v, q, stream);
+  });
 }

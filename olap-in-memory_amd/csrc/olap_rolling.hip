@@ -158,16 +158,6 @@ __global__ __launch_bounds__(kBlock) void rolling_direct_kernel(const Batch<T> b
   SERIES_RULE(b.method[p], (direct_walk<T, HS, M>(b.in[p], b.st_in[p], b.out[p], b.st_out[p], v, cells)));
 }
 
-// Workgroups of a launch along x: beyond it a workgroup takes several tiles, a lane several cells.  OLAP_ROLLING_GRID=n
-// (a developer knob, NOTEBOOK) lowers it, so that the tests reach those loops with small cubes.
-uint64_t max_grid(uint32_t most) {
-  if (const char *e = getenv("OLAP_ROLLING_GRID")) {
-    const unsigned long n = strtoul(e, nullptr, 10);
-    if (n >= 1 && n < most) return n;
-  }
-  return most;
-}
-
 template <typename T, bool HS>
 hipError_t launch_typed(int nb, const int *methods, const void *const *in, const int32_t *const *st_in, void *const *out, int32_t *const *st_out,
                         const RollingView &v, hipStream_t stream) {
@@ -180,11 +170,11 @@ hipError_t launch_typed(int nb, const int *methods, const void *const *in, const
   if (v.form == ROLLING_DIRECT) {
     const uint64_t cells = v.outer * v.K * v.inner;
     const uint64_t blocks = (cells + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)std::min<uint64_t>(blocks, max_grid(1u << 22)), (unsigned)nb);
+    const dim3 grid((unsigned)std::min<uint64_t>(blocks, series_max_grid("OLAP_ROLLING_GRID", 1u << 22)), (unsigned)nb);
     rolling_direct_kernel<T, HS><<<grid, kBlock, 0, stream>>>(b, v, cells);
   } else {
     const uint64_t n_tiles = ((v.outer + v.series - 1) / v.series) * ((v.K + v.rows - 1) / v.rows) * ((v.inner + v.cols - 1) / v.cols);
-    const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, max_grid(1u << 20)), (unsigned)nb);
+    const dim3 grid((unsigned)std::min<uint64_t>(n_tiles, series_max_grid("OLAP_ROLLING_GRID", 1u << 20)), (unsigned)nb);
     rolling_tiled_kernel<T, HS><<<grid, kBlock, 0, stream>>>(b, v, n_tiles);
   }
   return hipGetLastError();
@@ -236,17 +226,7 @@ hipError_t launch_rolling(int dtype, bool has_status, int nb, const int *methods
                           void *const *out, int32_t *const *st_out, const RollingView &v, hipStream_t stream) {
   if (nb < 1 || nb > kMaxBatch) return hipErrorInvalidValue;
   if (v.outer == 0 || v.K == 0 || v.inner == 0) return hipSuccess;
-  switch (dtype) {
-    case OLAP_INT32:
-      return has_status ? launch_typed<int32_t, true>(nb, methods, in, st_in, out, st_out, v, stream)
-                        : launch_typed<int32_t, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    case OLAP_UINT32:
-      return has_status ? launch_typed<uint32_t, true>(nb, methods, in, st_in, out, st_out, v, stream)
-                        : launch_typed<uint32_t, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    // float cells never hold a mask of their own (mask_is_primary)
-    case OLAP_FLOAT32:
-      return has_status ? hipErrorInvalidValue : launch_typed<float, false>(nb, methods, in, st_in, out, st_out, v, stream);
-    default:
-      return has_status ? hipErrorInvalidValue : launch_typed<double, false>(nb, methods, in, st_in, out, st_out, v, stream);
-  }
+  return series_cell_type(dtype, has_status, [&](auto cell, auto hs) {
+    return launch_typed<decltype(cell), decltype(hs)::value>(nb, methods, in, st_in, out, st_out, v, stream);
+  });
 }

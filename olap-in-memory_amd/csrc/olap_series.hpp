@@ -1,7 +1,13 @@
 // olap_series.hpp — what the kernels that walk series along one dimension share (olap_cumulate.hip, K13;
-// olap_rolling.hip, K14; olap_quantile.hip, K15; olap_variance.hip, K16): the per-pair rule dispatch, 16-byte slots at cell-aligned addresses and the move of
-// contiguous pieces between global memory and an LDS tile.
+// olap_rolling.hip, K14; olap_quantile.hip, K15; olap_variance.hip, K16).  On the device: the per-pair rule dispatch
+// (SERIES_RULE), 16-byte slots at cell-aligned addresses (load_slot, store_slot) and the move of contiguous pieces
+// between global memory and an LDS tile (tile_move).  On the host, for the launch functions at the units' ends: the
+// dispatch on cell type and mask (series_cell_type), the developer knobs' numbers (env_number) and the grid cap with its
+// knob (series_max_grid).
 #pragma once
+
+#include <cstdlib>
+#include <type_traits>
 
 #include "olap_internal.hpp"
 #include "olap_kernels.hpp"
@@ -19,6 +25,36 @@ namespace olap {
     case OLAP_LAST: { constexpr int M = OLAP_LAST; CALL; break; }        \
     default: { constexpr int M = OLAP_PRODUCT; CALL; break; }            \
   }
+
+// The cell type and mask of a launch, on the host: launch(T{}, HS{}) with T the cell type of `dtype` and HS
+// std::true_type where the pairs carry masks.  Float cells never hold a mask of their own (mask_is_primary).
+template <typename Launch>
+hipError_t series_cell_type(int dtype, bool has_status, Launch launch) {
+  switch (dtype) {
+    case OLAP_INT32:
+      return has_status ? launch(int32_t{}, std::true_type{}) : launch(int32_t{}, std::false_type{});
+    case OLAP_UINT32:
+      return has_status ? launch(uint32_t{}, std::true_type{}) : launch(uint32_t{}, std::false_type{});
+    case OLAP_FLOAT32:
+      return has_status ? hipErrorInvalidValue : launch(float{}, std::false_type{});
+    default:
+      return has_status ? hipErrorInvalidValue : launch(double{}, std::false_type{});
+  }
+}
+
+// the number in a developer knob; 0 where it is not set
+inline unsigned long env_number(const char *name) {
+  const char *e = getenv(name);
+  return e ? strtoul(e, nullptr, 10) : 0;
+}
+
+// Workgroups of a launch along x: beyond `most` a workgroup takes several tiles, a lane several cells.  The knob
+// (OLAP_CUMULATE_GRID=n and its like; developer knobs, NOTEBOOK) lowers it, so that the tests reach those loops with
+// small cubes.  Read at every launch.
+inline uint64_t series_max_grid(const char *knob, uint32_t most) {
+  const unsigned long n = env_number(knob);
+  return n >= 1 && n < most ? n : most;
+}
 
 // n <= VEC cells from a cell-aligned address: one 16-byte access for a whole slot, cell by cell otherwise
 template <typename T, int VEC>

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void variance_column_kernel(const Batch<T> 
   for (uint64_t work = blockIdx.x; work < n_work; work += gridDim.x) {
     const uint64_t slice = work % slices, t = (work / slices) % v.n_gtile, o = work / (slices * v.n_gtile);
     const uint32_t g0 = v.gtile[t], g1 = v.gtile[t + 1];
-    const uint32_t ja = v.gstart[g0], rows = v.gstart[g1] - ja;  // rows * cols <= v.tile <= kCells (variance_group_tiles)
+    const uint32_t ja = v.gstart[g0], rows = v.gstart[g1] - ja;  // rows * cols <= v.tile <= kCells (group_tiles, olap_plan_along.hip)
     const uint64_t c0 = slice * v.cols;
     const uint32_t nc = (uint32_t)(v.inner - c0 < v.cols ? v.inner - c0 : v.cols);
     const uint64_t first = o * v.K * v.inner + c0 + (v.order ? 0 : (uint64_t)ja * v.inner);
@@ -223,18 +223,6 @@ __global__ __launch_bounds__(kBlock) void variance_direct_kernel(const Batch<T> 
   }
 }
 
-unsigned long env_number(const char *name) {
-  const char *e = getenv(name);
-  return e ? strtoul(e, nullptr, 10) : 0;
-}
-
-// Workgroups of a launch along x: beyond it a workgroup takes several tiles, a lane several cells.  OLAP_VARIANCE_GRID=n
-// (a developer knob, NOTEBOOK) lowers it, so that the tests reach those loops with small cubes.
-uint64_t max_grid(uint32_t most) {
-  const unsigned long n = env_number("OLAP_VARIANCE_GRID");
-  return n >= 1 && n < most ? n : most;
-}
-
 template <typename T, bool HS>
 hipError_t launch_typed(int nb, const void *const *in, const int32_t *const *st_in, void *const *out, int32_t *const *st_out, const VarianceView &v,
                         int kind, int ddof, hipStream_t stream) {
@@ -245,7 +233,7 @@ hipError_t launch_typed(int nb, const void *const *in, const int32_t *const *st_
     b.out[k] = (T *)out[k], b.st_out[k] = HS ? st_out[k] : nullptr;
   }
   const uint64_t cells = v.outer * v.G * v.inner;
-  auto grid = [&](uint64_t want) { return dim3((unsigned)(want < max_grid(1u << 20) ? want : max_grid(1u << 20)), (unsigned)nb); };
+  auto grid = [&](uint64_t want) { return dim3((unsigned)(want < series_max_grid("OLAP_VARIANCE_GRID", 1u << 20) ? want : series_max_grid("OLAP_VARIANCE_GRID", 1u << 20)), (unsigned)nb); };
   switch (v.form) {
     case VARIANCE_COLUMN: {
       const uint64_t n_work = v.outer * v.n_gtile * ((v.inner + v.cols - 1) / v.cols);
@@ -326,34 +314,11 @@ void variance_choose(VarianceView &v, int cell_bytes) {
   v.rows = v.tile / v.cols;  // >= longest
 }
 
-std::vector<uint32_t> variance_group_tiles(const VarianceView &v, const uint32_t *gstart) {
-  std::vector<uint32_t> gtile{0};
-  uint32_t g0 = 0;
-  for (uint32_t g = 0; g < v.G; ++g) {
-    if (g > g0 && gstart[g + 1] - gstart[g0] > v.rows) {  // group g no longer fits beside [g0, g): it opens the next tile
-      gtile.push_back(g);
-      g0 = g;
-    }
-  }
-  gtile.push_back((uint32_t)v.G);
-  return gtile;
-}
-
 hipError_t launch_variance(int dtype, bool has_status, int nb, const void *const *in, const int32_t *const *st_in, void *const *out,
                            int32_t *const *st_out, const VarianceView &v, int kind, int ddof, hipStream_t stream) {
   if (nb < 1 || nb > kMaxBatch) return hipErrorInvalidValue;
   if (v.outer == 0 || v.G == 0 || v.inner == 0) return hipSuccess;
-  switch (dtype) {
-    case OLAP_INT32:
-      return has_status ? launch_typed<int32_t, true>(nb, in, st_in, out, st_out, v, kind, ddof, stream)
-                        : launch_typed<int32_t, false>(nb, in, st_in, out, st_out, v, kind, ddof, stream);
-    case OLAP_UINT32:
-      return has_status ? launch_typed<uint32_t, true>(nb, in, st_in, out, st_out, v, kind, ddof, stream)
-                        : launch_typed<uint32_t, false>(nb, in, st_in, out, st_out, v, kind, ddof, stream);
-    // float cells never hold a mask of their own (mask_is_primary)
-    case OLAP_FLOAT32:
-      return has_status ? hipErrorInvalidValue : launch_typed<float, false>(nb, in, st_in, out, st_out, v, kind, ddof, stream);
-    default:
-      return has_status ? hipErrorInvalidValue : launch_typed<double, false>(nb, in, st_in, out, st_out, v, kind, ddof, stream);
-  }
+  return series_cell_type(dtype, has_status, [&](auto cell, auto hs) {
+    return launch_typed<decltype(cell), decltype(hs)::value>(nb, in, st_in, out, st_out, v, kind, ddof, stream);
+  });
 }

@@ -690,12 +690,7 @@ class HipStore:
         n = len(stores)
         hs, (outs, launches) = _handles(stores), _new_stores(n)
         codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
-        if groups is None:
-            g, gp, ng = None, None, 1
-        else:
-            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
-            gp = g.ctypes.data_as(capi._pu32)
-            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        g, gp, ng = _groups_arg(groups, n_groups)  # (g: the array behind gp, held until the call is over)
         check(capi.lib().olap_store_cumulate_multi(n, hs, codes, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), ng, gp, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
@@ -712,12 +707,7 @@ class HipStore:
         n = len(stores)
         hs, (outs, launches) = _handles(stores), _new_stores(n)
         codes = (C.c_int * max(n, 1))(*[_method_code(m) for m in methods])
-        if groups is None:
-            g, gp, ng = None, None, 1
-        else:
-            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
-            gp = g.ctypes.data_as(capi._pu32)
-            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        g, gp, ng = _groups_arg(groups, n_groups)  # (g: the array behind gp, held until the call is over)
         check(capi.lib().olap_store_rolling_multi(n, hs, codes, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), int(before), int(after), ng, gp,
                                                   C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
@@ -735,12 +725,7 @@ class HipStore:
         lv = _u32(lens)
         n = len(stores)
         hs, (outs, launches) = _handles(stores), _new_stores(n)
-        if groups is None:
-            g, gp, ng = None, None, 1
-        else:
-            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
-            gp = g.ctypes.data_as(capi._pu32)
-            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        g, gp, ng = _groups_arg(groups, n_groups)  # (g: the array behind gp, held until the call is over)
         check(capi.lib().olap_store_quantile_multi(n, hs, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), float(q), ng, gp, C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
 
@@ -757,15 +742,19 @@ class HipStore:
         lv = _u32(lens)
         n = len(stores)
         hs, (outs, launches) = _handles(stores), _new_stores(n)
-        if groups is None:
-            g, gp, ng = None, None, 1
-        else:
-            g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
-            gp = g.ctypes.data_as(capi._pu32)
-            ng = int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
+        g, gp, ng = _groups_arg(groups, n_groups)  # (g: the array behind gp, held until the call is over)
         check(capi.lib().olap_store_variance_multi(n, hs, outs, len(lv), lv.ctypes.data_as(capi._pu32), int(axis), int(kind), int(ddof), ng, gp,
                                                    C.byref(launches)))
         return HipStore._multi_result(n, outs, launches)
+
+
+def _groups_arg(groups, n_groups):
+    """The K -> G map of the calls along a dimension as the C ABI takes it: (the uint32 array, its pointer, the number of
+    groups), or (None, None, 1) without groups.  `n_groups` defaults to max(groups) + 1."""
+    if groups is None:
+        return None, None, 1
+    g = np.ascontiguousarray(np.asarray(groups, dtype=np.uint32).ravel())
+    return g, g.ctypes.data_as(capi._pu32), int(n_groups) if n_groups is not None else (int(g.max()) + 1 if g.size else 0)
 
 
 def blocks_report(stores, lens, scanned):

@@ -906,6 +906,78 @@ class Cube {
     }, 'share', (id) => ids.includes(id));
   }
 
+  // ------------------------------------------------------------------ roll-ups of a dimension's groups without a rule
+  /**
+   * What quantile and _dispersion share.  The stored measures leave in one device call — many(stores): HipStore.quantileMany
+   * or varianceMany, null for a measure the call does not take; HipStore[pathField] says what ran — and the rest are
+   * computed on the host: host(ids) is the cube of _quantileHost / _varianceHost over those measures.  Returns the new
+   * cube over the dimensions of drillUp(dimension `index`, attribute).
+   */
+  _rollUpAlong(index, attribute, pathField, many, host) {
+    const newDimensions = this._withDimension(index, this.dimensions[index].drillUp(attribute));
+    const ids = this.storedMeasureIds;
+    const made = {};
+    HipStore[pathField] = 'host';
+    if (ids.length > 0) {
+      const results = many(ids.map((id) => this.storedMeasures[id]));
+      ids.forEach((id, i) => {
+        if (results[i]) made[id] = results[i];
+      });
+    }
+    const rest = ids.filter((id) => !made[id]);
+    const onHost = rest.length > 0 ? host(rest) : null;
+    return this._derive(newDimensions, (store, id) => {
+      if (!made[id]) return onHost.storedMeasures[id];
+      // (the device's result is an ordinary store: the order is kept from here on where the rules ask for it, as _newStore does)
+      if (Object.values(this.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last')) made[id].trackOrder();
+      return made[id];
+    });
+  }
+
+  /**
+   * What _quantileHost and _varianceHost share: the walk over the output cells of the stored measures `ids`.  For every
+   * cell of drillUp(dimension `index`, attribute), cell(v) gets the SET cells of its group's items, in ascending item
+   * order, as float64 (v is its own to reorder) and returns the result, or undefined to leave the cell unset.  A result
+   * is converted to the store's cell type once (the `data` setter), one equal to the default being unset.  The other
+   * measures are shared with this cube.
+   */
+  _groupCellsHost(index, attribute, ids, cell) {
+    const current = this.dimensions[index];
+    const rolled = current.drillUp(attribute);
+    const newDimensions = this._withDimension(index, rolled);
+    const groups = current.getGroupIndexFromRootIndexMap(attribute);
+    const K = current.numItems;
+    const G = rolled.numItems;
+    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
+    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
+    const members = Array.from({ length: G }, () => []);
+    for (let k = 0; k < K; ++k) members[groups[k]].push(k);
+    const target = new Cube(newDimensions);
+    return this._derive(newDimensions, (store, id) => {
+      const cells = store.data;
+      const set = new Uint8Array(cells.length); // the status map: the keys of the set cells
+      for (const at of store._dataMap.keys()) set[at] = 1;
+      const values = new Array(outer * G * inner).fill(store._defaultValue);
+      for (let o = 0; o < outer; ++o) {
+        for (let g = 0; g < G; ++g) {
+          for (let i = 0; i < inner; ++i) {
+            const v = [];
+            for (const k of members[g]) {
+              const at = (o * K + k) * inner + i;
+              if (set[at]) v.push(cells[at]);
+            }
+            const r = cell(v);
+            if (r !== undefined) values[(o * G + g) * inner + i] = r;
+          }
+        }
+      }
+      const rules = this.storedMeasuresRules[id];
+      const fresh = store instanceof HipStore ? target._newStore(store._type, store._defaultValue, rules) : new store.constructor(outer * G * inner, store._type, store._defaultValue);
+      fresh.data = values;
+      return fresh;
+    }, 'share', (id) => ids.includes(id));
+  }
+
   // ------------------------------------------------------------------ order statistics
   /** the checks quantile and _quantileHost share; returns the dimension's index */
   _checkQuantile(dimensionId, attribute, q) {
@@ -928,26 +1000,10 @@ class Cube {
    */
   quantile(dimensionId, attribute, q) {
     const index = this._checkQuantile(dimensionId, attribute, q);
-    const current = this.dimensions[index];
-    if (current.rootAttribute === attribute) return this.clone();
-    const newDimensions = this._withDimension(index, current.drillUp(attribute));
-    const ids = this.storedMeasureIds;
-    const made = {};
-    HipStore.lastQuantilePath = 'host';
-    if (ids.length > 0) {
-      const results = HipStore.quantileMany(ids.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute, q);
-      ids.forEach((id, i) => {
-        if (results[i]) made[id] = results[i];
-      });
-    }
-    const rest = ids.filter((id) => !made[id]);
-    const onHost = rest.length > 0 ? this._quantileHost(dimensionId, attribute, q, rest) : null;
-    return this._derive(newDimensions, (store, id) => {
-      if (!made[id]) return onHost.storedMeasures[id];
-      // (the device's result is an ordinary store: the order is kept from here on where the rules ask for it, as _newStore does)
-      if (Object.values(this.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last')) made[id].trackOrder();
-      return made[id];
-    });
+    if (this.dimensions[index].rootAttribute === attribute) return this.clone();
+    return this._rollUpAlong(index, attribute, 'lastQuantilePath',
+      (stores) => HipStore.quantileMany(stores, this.dimensions, index, attribute, q),
+      (rest) => this._quantileHost(dimensionId, attribute, q, rest));
   }
 
   /** quantile(dimensionId, attribute, 0.5) */
@@ -965,58 +1021,27 @@ class Cube {
    */
   _quantileHost(dimensionId, attribute, q, measureIds = null) {
     const index = this._checkQuantile(dimensionId, attribute, q);
-    const current = this.dimensions[index];
-    const ids = measureIds || this.storedMeasureIds;
-    if (current.rootAttribute === attribute) return this.clone(measureIds || []);
-    const rolled = current.drillUp(attribute);
-    const newDimensions = this._withDimension(index, rolled);
-    const groups = current.getGroupIndexFromRootIndexMap(attribute);
-    const K = current.numItems;
-    const G = rolled.numItems;
-    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
-    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
-    const members = Array.from({ length: G }, () => []);
-    for (let k = 0; k < K; ++k) members[groups[k]].push(k);
+    if (this.dimensions[index].rootAttribute === attribute) return this.clone(measureIds || []);
     // NaN last, -0 before +0, the rest by value
     const ascending = (a, b) => {
       if (Number.isNaN(a) || Number.isNaN(b)) return (Number.isNaN(a) ? 1 : 0) - (Number.isNaN(b) ? 1 : 0);
       if (a === b) return (Object.is(a, -0) ? 0 : 1) - (Object.is(b, -0) ? 0 : 1);
       return a < b ? -1 : 1;
     };
-    const target = new Cube(newDimensions);
-    return this._derive(newDimensions, (store, id) => {
-      const cells = store.data;
-      const set = new Uint8Array(cells.length); // the status map: the keys of the set cells
-      for (const at of store._dataMap.keys()) set[at] = 1;
-      const values = new Array(outer * G * inner).fill(store._defaultValue);
-      for (let o = 0; o < outer; ++o) {
-        for (let g = 0; g < G; ++g) {
-          for (let i = 0; i < inner; ++i) {
-            const v = [];
-            for (const k of members[g]) {
-              const at = (o * K + k) * inner + i;
-              if (set[at]) v.push(cells[at]);
-            }
-            if (v.length === 0) continue;
-            v.sort(ascending);
-            const h = q * (v.length - 1);
-            const lo = Math.floor(h);
-            const frac = h - lo;
-            let r = v[lo];
-            if (frac > 0) {
-              const d = v[lo + 1] - r;
-              const m = frac * d;
-              r += m;
-            }
-            values[(o * G + g) * inner + i] = r;
-          }
-        }
+    return this._groupCellsHost(index, attribute, measureIds || this.storedMeasureIds, (v) => {
+      if (v.length === 0) return undefined;
+      v.sort(ascending);
+      const h = q * (v.length - 1);
+      const lo = Math.floor(h);
+      const frac = h - lo;
+      let r = v[lo];
+      if (frac > 0) {
+        const d = v[lo + 1] - r;
+        const m = frac * d;
+        r += m;
       }
-      const rules = this.storedMeasuresRules[id];
-      const fresh = store instanceof HipStore ? target._newStore(store._type, store._defaultValue, rules) : new store.constructor(outer * G * inner, store._type, store._defaultValue);
-      fresh.data = values;
-      return fresh;
-    }, 'share', (id) => ids.includes(id));
+      return r;
+    });
   }
 
   // ------------------------------------------------------------------ dispersion
@@ -1054,25 +1079,9 @@ class Cube {
   /** kind: 0 variance, 1 stddev */
   _dispersion(dimensionId, attribute, ddof, kind) {
     const index = this._checkVariance(dimensionId, attribute, ddof);
-    const current = this.dimensions[index];
-    const newDimensions = this._withDimension(index, current.drillUp(attribute));
-    const ids = this.storedMeasureIds;
-    const made = {};
-    HipStore.lastVariancePath = 'host';
-    if (ids.length > 0) {
-      const results = HipStore.varianceMany(ids.map((id) => this.storedMeasures[id]), this.dimensions, index, attribute, kind, ddof);
-      ids.forEach((id, i) => {
-        if (results[i]) made[id] = results[i];
-      });
-    }
-    const rest = ids.filter((id) => !made[id]);
-    const onHost = rest.length > 0 ? this._varianceHost(dimensionId, attribute, ddof, kind, rest) : null;
-    return this._derive(newDimensions, (store, id) => {
-      if (!made[id]) return onHost.storedMeasures[id];
-      // (the device's result is an ordinary store: the order is kept from here on where the rules ask for it, as _newStore does)
-      if (Object.values(this.storedMeasuresRules[id] || {}).some((rule) => rule === 'first' || rule === 'last')) made[id].trackOrder();
-      return made[id];
-    });
+    return this._rollUpAlong(index, attribute, 'lastVariancePath',
+      (stores) => HipStore.varianceMany(stores, this.dimensions, index, attribute, kind, ddof),
+      (rest) => this._varianceHost(dimensionId, attribute, ddof, kind, rest));
   }
 
   /**
@@ -1086,53 +1095,22 @@ class Cube {
   _varianceHost(dimensionId, attribute, ddof, kind, measureIds = null) {
     const index = this._checkVariance(dimensionId, attribute, ddof);
     if (kind !== 0 && kind !== 1) throw new Error('variance: kind must be 0 or 1');
-    const current = this.dimensions[index];
-    const ids = measureIds || this.storedMeasureIds;
-    const rolled = current.drillUp(attribute);
-    const newDimensions = this._withDimension(index, rolled);
-    const groups = current.getGroupIndexFromRootIndexMap(attribute);
-    const K = current.numItems;
-    const G = rolled.numItems;
-    const outer = this.dimensions.slice(0, index).reduce((n, d) => n * d.numItems, 1);
-    const inner = this.dimensions.slice(index + 1).reduce((n, d) => n * d.numItems, 1);
-    const members = Array.from({ length: G }, () => []);
-    for (let k = 0; k < K; ++k) members[groups[k]].push(k);
-    const target = new Cube(newDimensions);
-    return this._derive(newDimensions, (store, id) => {
-      const cells = store.data;
-      const set = new Uint8Array(cells.length); // the status map: the keys of the set cells
-      for (const at of store._dataMap.keys()) set[at] = 1;
-      const values = new Array(outer * G * inner).fill(store._defaultValue);
-      for (let o = 0; o < outer; ++o) {
-        for (let g = 0; g < G; ++g) {
-          for (let i = 0; i < inner; ++i) {
-            const v = [];
-            for (const k of members[g]) {
-              const at = (o * K + k) * inner + i;
-              if (set[at]) v.push(cells[at]);
-            }
-            const n = v.length;
-            if (n - ddof <= 0) continue;
-            let s = v[0];
-            for (let k = 1; k < n; ++k) s += v[k];
-            const mean = s / n;
-            let m2 = 0;
-            for (let k = 0; k < n; ++k) {
-              const d = v[k] - mean;
-              const p = d * d;
-              m2 += p;
-            }
-            let r = m2 / (n - ddof);
-            if (kind === 1) r = Math.sqrt(r);
-            values[(o * G + g) * inner + i] = r;
-          }
-        }
+    return this._groupCellsHost(index, attribute, measureIds || this.storedMeasureIds, (v) => {
+      const n = v.length;
+      if (n - ddof <= 0) return undefined;
+      let s = v[0];
+      for (let k = 1; k < n; ++k) s += v[k];
+      const mean = s / n;
+      let m2 = 0;
+      for (let k = 0; k < n; ++k) {
+        const d = v[k] - mean;
+        const p = d * d;
+        m2 += p;
       }
-      const rules = this.storedMeasuresRules[id];
-      const fresh = store instanceof HipStore ? target._newStore(store._type, store._defaultValue, rules) : new store.constructor(outer * G * inner, store._type, store._defaultValue);
-      fresh.data = values;
-      return fresh;
-    }, 'share', (id) => ids.includes(id));
+      let r = m2 / (n - ddof);
+      if (kind === 1) r = Math.sqrt(r);
+      return r;
+    });
   }
 
   // ------------------------------------------------------------------ dice / slice

@@ -910,35 +910,8 @@ class HipStore {
    * HipStore.lastBatchLaunches and HipStore.lastQuantilePath ('device' when the call ran).
    */
   static quantileMany(stores, dimensions, index, attribute, q) {
-    const out = new Array(stores.length).fill(null);
-    const addon = backend.load();
-    HipStore.lastQuantilePath = 'host';
-    if (typeof addon.quantileMulti !== 'function') return out;
-    const mine = stores.filter((store) => store instanceof HipStore);
-    HipStore.materializeMany(mine);
-    let launches = HipStore.lastBatchLaunches;
-    const whole = (native) => !!native && !native.isSharded;
-    // (a selection alone in its group stays pending there, host-resident cells have no device store yet: both get one now)
-    for (const store of mine) {
-      if (store._pending ? whole(store._pending.source) : !store._nativeStore) store._materialize();
-    }
-    const together = [];
-    stores.forEach((store, i) => {
-      if (store instanceof HipStore && whole(heldStore(store)) && store._cells === cellTypeOf(store._type)) together.push(i);
-    });
-    if (together.length > 0) {
-      const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
-      const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
-      const launchesOut = new Int32Array(1);
-      const made = addon.quantileMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(dimensions), index, q, groups, nGroups, launchesOut);
-      together.forEach((i, j) => {
-        out[i] = stores[i]._wrap(made[j]);
-      });
-      launches += launchesOut[0];
-      HipStore.lastQuantilePath = 'device';
-    }
-    HipStore.lastBatchLaunches = launches;
-    return out;
+    return groupedMany(stores, dimensions, index, attribute, 'quantileMulti', 'lastQuantilePath',
+      (addon, natives, lens, groups, nGroups, launchesOut) => addon.quantileMulti(natives, lens, index, q, groups, nGroups, launchesOut));
   }
 
   /**
@@ -954,35 +927,8 @@ class HipStore {
    * HipStore.lastBatchLaunches and HipStore.lastVariancePath ('device' when the call ran).
    */
   static varianceMany(stores, dimensions, index, attribute, kind, ddof) {
-    const out = new Array(stores.length).fill(null);
-    const addon = backend.load();
-    HipStore.lastVariancePath = 'host';
-    if (typeof addon.varianceMulti !== 'function') return out;
-    const mine = stores.filter((store) => store instanceof HipStore);
-    HipStore.materializeMany(mine);
-    let launches = HipStore.lastBatchLaunches;
-    const whole = (native) => !!native && !native.isSharded;
-    // (a selection alone in its group stays pending there, host-resident cells have no device store yet: both get one now)
-    for (const store of mine) {
-      if (store._pending ? whole(store._pending.source) : !store._nativeStore) store._materialize();
-    }
-    const together = [];
-    stores.forEach((store, i) => {
-      if (store instanceof HipStore && whole(heldStore(store)) && store._cells === cellTypeOf(store._type)) together.push(i);
-    });
-    if (together.length > 0) {
-      const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
-      const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
-      const launchesOut = new Int32Array(1);
-      const made = addon.varianceMulti(together.map((i) => stores[i]._nativeStore), lengthsOf(dimensions), index, kind, ddof, groups, nGroups, launchesOut);
-      together.forEach((i, j) => {
-        out[i] = stores[i]._wrap(made[j]);
-      });
-      launches += launchesOut[0];
-      HipStore.lastVariancePath = 'device';
-    }
-    HipStore.lastBatchLaunches = launches;
-    return out;
+    return groupedMany(stores, dimensions, index, attribute, 'varianceMulti', 'lastVariancePath',
+      (addon, natives, lens, groups, nGroups, launchesOut) => addon.varianceMulti(natives, lens, index, kind, ddof, groups, nGroups, launchesOut));
   }
 
   /** in-memory.js:139-176 — mutates this store */
@@ -1176,9 +1122,18 @@ HipStore.lastQuantilePath = null;
 HipStore.lastVariancePath = null;
 
 /**
- * What cumulateMany and rollingMany share (`call`: the addon's many-call `name`): the measures held whole on one device,
- * untracked and with cells of their declared type leave in ONE call; null for the others.  pathField: the HipStore
- * field that says what ran.
+ * The groups of dimension `index` under `attribute` as the many-calls along a dimension take them: groups[k] is the
+ * group of item k (null under 'all': one group), nGroups how many there are.
+ */
+function groupsOf(dimensions, index, attribute) {
+  const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
+  return { groups, nGroups: groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0) };
+}
+
+/**
+ * What the calls along a dimension that take a rule per measure share — cumulateMany and rollingMany (`call`: the
+ * addon's many-call `name`): the measures held whole on one device, untracked and with cells of their declared type
+ * leave in ONE call; null for the others.  pathField: the HipStore field that says what ran ('device' or 'per-item').
  */
 function alongMany(stores, dimensions, index, attribute, methods, name, pathField, call) {
   const out = new Array(stores.length).fill(null);
@@ -1191,8 +1146,7 @@ function alongMany(stores, dimensions, index, attribute, methods, name, pathFiel
   for (const store of stores) {
     if (store._pending && wholeUntracked(store._pending.source)) store._materialize();
   }
-  const groups = attribute === 'all' ? null : asU32(dimensions[index].getGroupIndexFromRootIndexMap(attribute));
-  const nGroups = groups === null ? 1 : groups.reduce((n, g) => Math.max(n, g + 1), 0);
+  const { groups, nGroups } = groupsOf(dimensions, index, attribute);
   const eligible = (i) => stores[i]._cells === cellTypeOf(stores[i]._type);
   const run = (natives, together) => {
     const codes = Int32Array.from(together, (i) => addon.methodFromName(methods[i] === undefined ? 'sum' : methods[i])); // throws 'Unsupported aggregation method: <m>'
@@ -1204,6 +1158,43 @@ function alongMany(stores, dimensions, index, attribute, methods, name, pathFiel
   };
   // (togetherThenSingly sends two or more together; a measure alone among the eligible ones is a batch of one)
   togetherThenSingly(stores, out, eligible, run, (store, i) => (wholeUntracked(heldStore(store)) && eligible(i) ? store._wrap(run([store._nativeStore], [i])[0]) : null));
+  HipStore.lastBatchLaunches = launches;
+  return out;
+}
+
+/**
+ * What the calls along a dimension that roll its groups up without a rule share — quantileMany and varianceMany
+ * (`call`: the addon's many-call `name`): the measures held whole on one device, tracked or not, with cells of their
+ * declared type leave in ONE call; null for the others.  pathField: the HipStore field that says what ran ('device' or
+ * 'host').
+ */
+function groupedMany(stores, dimensions, index, attribute, name, pathField, call) {
+  const out = new Array(stores.length).fill(null);
+  const addon = backend.load();
+  HipStore[pathField] = 'host';
+  if (typeof addon[name] !== 'function') return out;
+  const mine = stores.filter((store) => store instanceof HipStore);
+  HipStore.materializeMany(mine);
+  let launches = HipStore.lastBatchLaunches;
+  const whole = (native) => !!native && !native.isSharded;
+  // (a selection alone in its group stays pending there, host-resident cells have no device store yet: both get one now)
+  for (const store of mine) {
+    if (store._pending ? whole(store._pending.source) : !store._nativeStore) store._materialize();
+  }
+  const together = [];
+  stores.forEach((store, i) => {
+    if (store instanceof HipStore && whole(heldStore(store)) && store._cells === cellTypeOf(store._type)) together.push(i);
+  });
+  if (together.length > 0) {
+    const { groups, nGroups } = groupsOf(dimensions, index, attribute);
+    const launchesOut = new Int32Array(1);
+    const made = call(addon, together.map((i) => stores[i]._nativeStore), lengthsOf(dimensions), groups, nGroups, launchesOut);
+    together.forEach((i, j) => {
+      out[i] = stores[i]._wrap(made[j]);
+    });
+    launches += launchesOut[0];
+    HipStore[pathField] = 'device';
+  }
   HipStore.lastBatchLaunches = launches;
   return out;
 }

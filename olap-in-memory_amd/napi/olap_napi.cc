@@ -1240,6 +1240,40 @@ static napi_value DrillDownMulti(napi_env env, napi_callback_info info) {
   return multi_done(env, rc, argc, argv, 5, launches) ? wrap_new_stores(env, outs) : nullptr;
 }
 
+// What the calls along one dimension share behind their own scalars: lens and axis at argv[lens_at] and the next,
+// groups (null: one group) and nGroups at argv[groups_at] and the next.
+struct AlongArgs {
+  std::vector<uint32_t> lens, groups;
+  int32_t axis = -1;
+  uint32_t n_groups = 0;
+  bool one_group = true;
+  static bool refuse(napi_env env, const char *what) {
+    bad_args(env, what);
+    return false;
+  }
+  // false: refused (a TypeError is pending), with `usage` or with "<name>: one group per item of the dimension"
+  bool decode(napi_env env, const napi_value *argv, size_t lens_at, size_t groups_at, const char *name, const char *usage) {
+    napi_valuetype gt = napi_undefined;
+    if (!get_u32_vec(env, argv[lens_at], lens) || napi_get_value_int32(env, argv[lens_at + 1], &axis) != napi_ok ||
+        napi_typeof(env, argv[groups_at], &gt) != napi_ok || napi_get_value_uint32(env, argv[groups_at + 1], &n_groups) != napi_ok)
+      return refuse(env, usage);
+    one_group = gt == napi_null || gt == napi_undefined;
+    if (!one_group && !get_u32_vec(env, argv[groups_at], groups)) return refuse(env, usage);
+    // one entry per item of the dimension (the C ABI reads lens[axis] of them)
+    if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis]))
+      return refuse(env, (std::string(name) + ": one group per item of the dimension").c_str());
+    return true;
+  }
+  int ndim() const { return (int)lens.size(); }
+  const uint32_t *lens_data() const { return lens.empty() ? &OpArgs::dummy : lens.data(); }
+  const uint32_t *map() const { return one_group ? nullptr : groups.empty() ? &OpArgs::dummy : groups.data(); }
+};
+
+// the end of a *Multi call that makes stores: multi_done, then the results as Store objects
+static napi_value multi_stores(napi_env env, int rc, size_t argc, const napi_value *argv, size_t launches_at, int launches, std::vector<olap_store *> &outs) {
+  return multi_done(env, rc, argc, argv, launches_at, launches) ? wrap_new_stores(env, outs) : nullptr;
+}
+
 // cumulateMulti(stores: Store[], methods: Int32Array, lens, axis: number, groups: Uint32Array | null, nGroups: number, launchesOut?) -> Store[]
 // Running aggregates along dimension `axis` (olap_store_cumulate_multi): groups[k] < nGroups is the group of item k; null: one group.
 static napi_value CumulateMulti(napi_env env, napi_callback_info info) {
@@ -1248,26 +1282,16 @@ static napi_value CumulateMulti(napi_env env, napi_callback_info info) {
   size_t argc = 7;
   napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  std::vector<uint32_t> lens, groups;
+  AlongArgs a;
   MultiArgs m;
   bool bad = true;
-  int32_t axis = -1;
-  uint32_t n_groups = 0;
-  napi_valuetype gt = napi_undefined;
-  if (argc < 6 || !get_u32_vec(env, argv[2], lens) || napi_get_value_int32(env, argv[3], &axis) != napi_ok || napi_typeof(env, argv[4], &gt) != napi_ok ||
-      napi_get_value_uint32(env, argv[5], &n_groups) != napi_ok)
-    return bad_args(env, usage);
-  const bool one_group = gt == napi_null || gt == napi_undefined;
-  if (!one_group && !get_u32_vec(env, argv[4], groups)) return bad_args(env, usage);
-  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
-  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "cumulateMulti: one group per item of the dimension");
+  if (argc < 6) return bad_args(env, usage);
+  if (!a.decode(env, argv, 2, 4, "cumulateMulti", usage)) return nullptr;
   if (!m.decode(env, argv[0], &argv[1], &bad)) return m.miscounted ? bad_args(env, "cumulateMulti: one method per store") : bad ? bad_args(env, usage) : nullptr;
   std::vector<olap_store *> outs(m.stores.size(), nullptr);
-  static const uint32_t none = 0;
   int launches = 0;
-  int rc = olap_store_cumulate_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis,
-                                     n_groups, one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
-  return multi_done(env, rc, argc, argv, 6, launches) ? wrap_new_stores(env, outs) : nullptr;
+  int rc = olap_store_cumulate_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), a.ndim(), a.lens_data(), a.axis, a.n_groups, a.map(), &launches);
+  return multi_stores(env, rc, argc, argv, 6, launches, outs);
 }
 
 // rollingMulti(stores: Store[], methods: Int32Array, lens, axis: number, before: number, after: number, groups: Uint32Array | null, nGroups: number,
@@ -1280,27 +1304,18 @@ static napi_value RollingMulti(napi_env env, napi_callback_info info) {
   size_t argc = 9;
   napi_value argv[9];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  std::vector<uint32_t> lens, groups;
+  AlongArgs a;
   MultiArgs m;
   bool bad = true;
-  int32_t axis = -1, before = 0, after = 0;
-  uint32_t n_groups = 0;
-  napi_valuetype gt = napi_undefined;
-  if (argc < 8 || !get_u32_vec(env, argv[2], lens) || napi_get_value_int32(env, argv[3], &axis) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &before) != napi_ok || napi_get_value_int32(env, argv[5], &after) != napi_ok ||
-      napi_typeof(env, argv[6], &gt) != napi_ok || napi_get_value_uint32(env, argv[7], &n_groups) != napi_ok)
-    return bad_args(env, usage);
-  const bool one_group = gt == napi_null || gt == napi_undefined;
-  if (!one_group && !get_u32_vec(env, argv[6], groups)) return bad_args(env, usage);
-  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
-  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "rollingMulti: one group per item of the dimension");
+  int32_t before = 0, after = 0;
+  if (argc < 8 || napi_get_value_int32(env, argv[4], &before) != napi_ok || napi_get_value_int32(env, argv[5], &after) != napi_ok) return bad_args(env, usage);
+  if (!a.decode(env, argv, 2, 6, "rollingMulti", usage)) return nullptr;
   if (!m.decode(env, argv[0], &argv[1], &bad)) return m.miscounted ? bad_args(env, "rollingMulti: one method per store") : bad ? bad_args(env, usage) : nullptr;
   std::vector<olap_store *> outs(m.stores.size(), nullptr);
-  static const uint32_t none = 0;
   int launches = 0;
-  int rc = olap_store_rolling_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis,
-                                    before, after, n_groups, one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
-  return multi_done(env, rc, argc, argv, 8, launches) ? wrap_new_stores(env, outs) : nullptr;
+  int rc = olap_store_rolling_multi((int)m.stores.size(), m.stores.data(), m.methods, outs.data(), a.ndim(), a.lens_data(), a.axis, before, after, a.n_groups,
+                                    a.map(), &launches);
+  return multi_stores(env, rc, argc, argv, 8, launches, outs);
 }
 
 // quantileMulti(stores: Store[], lens, axis: number, q: number, groups: Uint32Array | null, nGroups: number, launchesOut?) -> Store[]
@@ -1311,27 +1326,17 @@ static napi_value QuantileMulti(napi_env env, napi_callback_info info) {
   size_t argc = 7;
   napi_value argv[7];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  std::vector<uint32_t> lens, groups;
+  AlongArgs a;
   MultiArgs m;
   bool bad = true;
-  int32_t axis = -1;
   double q = 0;
-  uint32_t n_groups = 0;
-  napi_valuetype gt = napi_undefined;
-  if (argc < 6 || !get_u32_vec(env, argv[1], lens) || napi_get_value_int32(env, argv[2], &axis) != napi_ok || napi_get_value_double(env, argv[3], &q) != napi_ok ||
-      napi_typeof(env, argv[4], &gt) != napi_ok || napi_get_value_uint32(env, argv[5], &n_groups) != napi_ok)
-    return bad_args(env, usage);
-  const bool one_group = gt == napi_null || gt == napi_undefined;
-  if (!one_group && !get_u32_vec(env, argv[4], groups)) return bad_args(env, usage);
-  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
-  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "quantileMulti: one group per item of the dimension");
+  if (argc < 6 || napi_get_value_double(env, argv[3], &q) != napi_ok) return bad_args(env, usage);
+  if (!a.decode(env, argv, 1, 4, "quantileMulti", usage)) return nullptr;
   if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
   std::vector<olap_store *> outs(m.stores.size(), nullptr);
-  static const uint32_t none = 0;
   int launches = 0;
-  int rc = olap_store_quantile_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis, q, n_groups,
-                                     one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
-  return multi_done(env, rc, argc, argv, 6, launches) ? wrap_new_stores(env, outs) : nullptr;
+  int rc = olap_store_quantile_multi((int)m.stores.size(), m.stores.data(), outs.data(), a.ndim(), a.lens_data(), a.axis, q, a.n_groups, a.map(), &launches);
+  return multi_stores(env, rc, argc, argv, 6, launches, outs);
 }
 
 // varianceMulti(stores: Store[], lens, axis: number, kind: number, ddof: number, groups: Uint32Array | null, nGroups: number, launchesOut?) -> Store[]
@@ -1343,26 +1348,17 @@ static napi_value VarianceMulti(napi_env env, napi_callback_info info) {
   size_t argc = 8;
   napi_value argv[8];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-  std::vector<uint32_t> lens, groups;
+  AlongArgs a;
   MultiArgs m;
   bool bad = true;
-  int32_t axis = -1, kind = -1, ddof = -1;
-  uint32_t n_groups = 0;
-  napi_valuetype gt = napi_undefined;
-  if (argc < 7 || !get_u32_vec(env, argv[1], lens) || napi_get_value_int32(env, argv[2], &axis) != napi_ok || napi_get_value_int32(env, argv[3], &kind) != napi_ok ||
-      napi_get_value_int32(env, argv[4], &ddof) != napi_ok || napi_typeof(env, argv[5], &gt) != napi_ok || napi_get_value_uint32(env, argv[6], &n_groups) != napi_ok)
-    return bad_args(env, usage);
-  const bool one_group = gt == napi_null || gt == napi_undefined;
-  if (!one_group && !get_u32_vec(env, argv[5], groups)) return bad_args(env, usage);
-  // one entry per item of the dimension (the C ABI reads lens[axis] of them)
-  if (!one_group && (axis < 0 || (size_t)axis >= lens.size() || groups.size() != lens[axis])) return bad_args(env, "varianceMulti: one group per item of the dimension");
+  int32_t kind = -1, ddof = -1;
+  if (argc < 7 || napi_get_value_int32(env, argv[3], &kind) != napi_ok || napi_get_value_int32(env, argv[4], &ddof) != napi_ok) return bad_args(env, usage);
+  if (!a.decode(env, argv, 1, 5, "varianceMulti", usage)) return nullptr;
   if (!m.decode(env, argv[0], nullptr, &bad)) return bad ? bad_args(env, usage) : nullptr;
   std::vector<olap_store *> outs(m.stores.size(), nullptr);
-  static const uint32_t none = 0;
   int launches = 0;
-  int rc = olap_store_variance_multi((int)m.stores.size(), m.stores.data(), outs.data(), (int)lens.size(), lens.empty() ? &none : lens.data(), axis, kind, ddof, n_groups,
-                                     one_group ? nullptr : (groups.empty() ? &none : groups.data()), &launches);
-  return multi_done(env, rc, argc, argv, 7, launches) ? wrap_new_stores(env, outs) : nullptr;
+  int rc = olap_store_variance_multi((int)m.stores.size(), m.stores.data(), outs.data(), a.ndim(), a.lens_data(), a.axis, kind, ddof, a.n_groups, a.map(), &launches);
+  return multi_stores(env, rc, argc, argv, 7, launches, outs);
 }
 
 // ---- ShardedStore: a measure split along dimension 0 over the devices of setDevices() -----------

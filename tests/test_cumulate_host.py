@@ -7,6 +7,7 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import pytest
 
@@ -108,6 +109,15 @@ def test_refusals_that_read_a_store_leave_the_stand_ins_untouched():
         assert (rc, message) == (want_rc, want_message), (kw, rc, message)
         assert all(h is None for h in outs), want_message  # nothing is created
     assert [bytes(x) for x in everyone] == before
+
+
+def test_what_the_plan_keys_of_the_calls_along_a_dimension_hold():
+    """cumulate, rolling, quantile and variance side by side (tests/_along_keys_dry_worker.py, under OLAP_PLAN_DRY=1)"""
+    env = {k: v for k, v in os.environ.items() if not re.match(r"OLAP_(CUMULATE|ROLLING|QUANTILE|VARIANCE)_", k)}
+    env["OLAP_PLAN_DRY"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(HERE, "_along_keys_dry_worker.py")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env,
+                       timeout=300)
+    assert r.returncode == 0 and "along-axis plan keys ok" in r.stdout, r.stdout[-4000:]
 
 
 @pytest.mark.skipif(NODE is None, reason="node is not installed")
